@@ -5,8 +5,11 @@ One "step" = one pass of the hot path over the batch: ring-buffer readout (physi
 (SwimmingHandler.step) -> xfrc glue -> controller -> mj_step, for every env of this rank.
 Inputs are resident in HBM before the timed region.  One process per GPU; envs are independent, so there
 is NO data-path collective: torch.distributed is used only for the barrier and the max-over-ranks time.
+A plain run times exactly --steps steps after --warmup and prints the line; --full adds the other measurements
+(walk / mixed, API paths, CPU baseline; sharded configurations with N > 1), --dump-outputs DIR the last step's outputs.
 
     python bench.py --gpus 1 --steps 1000 --warmup 100
+    python bench.py --gpus 1 --steps 1000 --warmup 100 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -241,6 +244,40 @@ def api_paths(n_envs, chunk, device):
     return out
 
 
+DUMP_LIMIT_BYTES = 60_000_000           # under 64 MB in all, .npy headers included
+
+
+def dump_outputs(sims, out_dir, prefix='', limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives after its last step - the state and derived fields of
+    ``physics.data`` and the ring-buffer rows that step wrote - as ``out_dir/<prefix>[bucket<i>_]<field>.npy`` (float32, env
+    axis first).  Over ``limit`` bytes in all, the arrays of a bucket keep one seeded sample of its envs, whose indices go
+    to ``<prefix>[bucket<i>_]env_index.npy`` (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = []                                        # (bucket, file name, tensor with the env axis first)
+    for i, s_ in enumerate(sims):
+        p = prefix + (f'bucket{i}_' if len(sims) > 1 else '')
+        d, task = s_.physics.data, s_.task
+        for k in ('qpos', 'qvel', 'qacc', 'ctrl', 'time', 'xpos', 'xquat', 'xipos', 'sensordata'):
+            arrays.append((i, p + k, getattr(d, k)))
+        row = (task.sim_iteration//task.substeps - 1) % task.buffer_size      # the ring index of the last iteration
+        for k in ('links', 'joints', 'xfrc', 'contacts'):
+            a = getattr(task.data.sensors, k)
+            if a.names:
+                arrays.append((i, p + k, a.array[row]))
+    n_all = sum(s_.physics.n_envs for s_ in sims)
+    total = sum(t.numel()*4 for _, _, t in arrays)
+    keep = {}
+    if total > limit:                                  # k of n envs per bucket: k/n (array bytes + 8 per index) <= limit
+        for i, s_ in enumerate(sims):
+            n = s_.physics.n_envs
+            keep[i] = np.sort(np.random.default_rng(i).choice(n, max(1, n*limit//(total + 8*n_all)), replace=False))
+            np.save(os.path.join(out_dir, prefix + (f'bucket{i}_' if len(sims) > 1 else '') + 'env_index.npy'),
+                    keep[i].astype(np.float64))
+    for i, name, t in arrays:
+        a = t.detach().cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, name + '.npy'), a[keep[i]] if i in keep else a)
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks as FRESH child processes (one per GPU, through
     torch.distributed.run) before this process makes any GPU call, stream their output through, exit with their code."""
@@ -265,11 +302,17 @@ def main():
                     help='steps per fused launch = ring-buffer length.  1000 = the reference logs a whole 1000-iteration run (AnimatData of n_iterations '
                          'rows, task.py:62,158); 100 was the default up to round 4 and is what every same-box A/B of DESIGN.md used.  Longer launches '
                          'amortise prologue / epilogue and - walking - average the uneven contact load of the waves of the one resident round')
-    ap.add_argument('--min-seconds', type=float, default=6.0,
-                    help='the timed region repeats the --steps block until it lasts at least this long (0: exactly one block); 6 s so that an '
-                         'external sampler with a 5 s period sees the GPU busy (VERDICT round 4: with 2 s the driver\'s gpu_busy read 2 %%)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the short walk / mixed measurements appended to the swim line')
+    ap.add_argument('--min-seconds', type=float, default=0.0,
+                    help='repeat the --steps block until the timed region lasts at least this long (default 0: exactly --steps timed '
+                         'steps); 6 lets an external sampler with a 5 s period see the GPU busy (VERDICT round 4)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the short walk / mixed and API-path measurements and the CPU '
+                         'baseline (one GPU, swim), or the other sharded configurations (N > 1)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the walk / mixed, API-path and sharded measurements')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last step computed (state, poses, sensordata, ring-buffer rows) '
+                         'as DIR/<name>.npy, float32, at most 64 MB (a seeded sample of the envs beyond that)')
     ap.add_argument('--workload', default='swim', choices=['swim', 'walk', 'mixed', 'walk_pairs', 'walk_hfield', 'walk_mesh', 'walk_newton', 'walk_cg', 'walk_elliptic', 'walk_pairs_newton', 'walk_elliptic_pgs', 'walk_noslip'],
                     help='swim = headline (BASELINE configs[1]); walk = configs[3]; mixed = configs[4] eel + centipede; walk_pairs / '
                          'walk_hfield / walk_mesh = the walker with self-collision pairs / on a heightfield / on convex-mesh feet')
@@ -338,13 +381,15 @@ def main():
             done += c
         return evs
 
-    # warm-up; its event timings also size the timed region: the K-step block is repeated R times so that the region
-    # lasts >= --min-seconds (a single 20-step block is one 0.5 ms launch, which is not a measurement)
+    # warm-up; with --min-seconds one more warm launch sizes the timed region: the K-step block is repeated R times so that
+    # the region lasts >= --min-seconds (a single 20-step block is one 0.5 ms launch, which is not a measurement)
     run(max(W, 1))
-    evw = run(chunk)                  # one more launch, warm, to size the timed region
-    torch.cuda.synchronize()
-    est = evw[0][0].elapsed_time(evw[0][1])*1e-3/chunk
-    R = max(1, int(np.ceil(args.min_seconds/max(K*est, 1e-9)))) if args.min_seconds > 0 else 1
+    R = 1
+    if args.min_seconds > 0:
+        evw = run(chunk)
+        torch.cuda.synchronize()
+        est = evw[0][0].elapsed_time(evw[0][1])*1e-3/chunk
+        R = max(1, int(np.ceil(args.min_seconds/max(K*est, 1e-9))))
     if world > 1:                                                   # every rank must time the same number of steps
         t = torch.tensor([R], device=device if args.dist_backend == 'nccl' else 'cpu')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -370,15 +415,17 @@ def main():
         rank_s = [float(x) for x in t.cpu()]
     for s_ in sims:
         s_.physics.check_invalid_state()
+    if args.dump_outputs:
+        dump_outputs(sims, args.dump_outputs, prefix=f'rank{rank}_' if world > 1 else '', limit=DUMP_LIMIT_BYTES//world)
 
-    # N > 1: the other sharded BASELINE configurations next to the 4096-per-GPU headline, so that ONE driver run records them
+    # N > 1 (--full): the other sharded BASELINE configurations next to the 4096-per-GPU headline, so that ONE driver run records them
     # (VERDICT round 4 item 6): configs[2] = 8192 swimming salamanders per GPU, configs[4] = the mixed batch, bucket then split (every
     # rank holds its share of the eels and of the centipedes).  Same protocol: barrier, K steps in launches of `chunk`, barrier, MAX.
     b = algorithmic_bytes_per_env_step(m, sim, args.workload, sims)
     info = sim.physics.kernel_info()
     has_constraints = sim.physics.has_constraints
     sharded = None
-    if world > 1 and not args.no_extras and args.workload == 'swim':
+    if world > 1 and args.full and not args.no_extras and args.workload == 'swim':
         sharded = {}
         del batch, sims, sim
         torch.cuda.empty_cache()
@@ -495,18 +542,18 @@ def main():
         }
         if sharded is not None:
             out['sharded_configs'] = sharded
-        if world == 1 and not args.no_extras and args.workload == 'swim':
+        if world == 1 and args.full and not args.no_extras and args.workload == 'swim':
             # the other BASELINE configurations, briefly, so that the driver's record carries them too (never the headline)
             try:
                 out['other_workloads'] = other_workloads(n_envs, chunk, device)
             except Exception as e:
                 out['other_workloads'] = {'error': repr(e)}
-        if world == 1 and not args.no_extras and args.workload == 'swim':
+        if world == 1 and args.full and not args.no_extras and args.workload == 'swim':
             try:
                 out['api_paths'] = api_paths(n_envs, chunk, device)
             except Exception as e:
                 out['api_paths'] = {'error': repr(e)}
-        if world == 1 and not args.no_cpu_baseline and args.workload == 'swim':
+        if world == 1 and args.full and not args.no_cpu_baseline and args.workload == 'swim':
             try:
                 out['cpu_baseline'] = cpu_baseline(m, sim)
             except Exception as e:      # the baseline is reported, never required

@@ -50,3 +50,51 @@ def test_usable_cores_and_build_id():
     assert 1 <= n <= (os.cpu_count() or 1)
     b = _lib.build_id()
     assert len(b) == 16 and b == _lib.build_id()
+
+
+def _fake_sim(n_envs, nq, buffer_size, sim_iteration, seed):
+    """The fields dump_outputs reads, as CPU tensors: physics.data, the task's counters and its ring of sensor rows."""
+    import torch
+    from types import SimpleNamespace as NS
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.rand(*s, generator=g)
+    data = NS(qpos=r(n_envs, nq), qvel=r(n_envs, nq - 1), qacc=r(n_envs, nq - 1), ctrl=r(n_envs, 3), time=r(n_envs),
+              xpos=r(n_envs, 5, 3), xquat=r(n_envs, 5, 4), xipos=r(n_envs, 5, 3), sensordata=r(n_envs, 7))
+    sensors = NS(links=NS(names=['a', 'b'], array=r(buffer_size, n_envs, 2, 20)), joints=NS(names=['j'], array=r(buffer_size, n_envs, 1, 12)),
+                 xfrc=NS(names=['a', 'b'], array=r(buffer_size, n_envs, 2, 6)), contacts=NS(names=[], array=r(buffer_size, n_envs, 0, 12)))
+    task = NS(sim_iteration=sim_iteration, substeps=1, buffer_size=buffer_size, data=NS(sensors=sensors))
+    return NS(physics=NS(data=data, n_envs=n_envs), task=task)
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs: physics.data and the ring row of the launch's last iteration, float32, one .npy per field and bucket."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    sims = [_fake_sim(6, 4, 10, 23, 0), _fake_sim(5, 3, 10, 23, 1)]
+    bench.dump_outputs(sims, str(tmp_path))
+    for i, s in enumerate(sims):
+        q = np.load(tmp_path/f'bucket{i}_qpos.npy')
+        assert q.dtype == np.float32 and np.array_equal(q, s.physics.data.qpos.numpy())
+        assert np.array_equal(np.load(tmp_path/f'bucket{i}_links.npy'), s.task.data.sensors.links.array[2].numpy())     # iteration 22 -> row 2
+        assert not (tmp_path/f'bucket{i}_contacts.npy').exists() and not (tmp_path/f'bucket{i}_env_index.npy').exists()
+
+
+def test_dump_outputs_samples_envs_over_the_limit(tmp_path):
+    """Over the size limit every array keeps the same seeded sample of envs, the same from run to run, and stays within it."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    limit = 20000
+    sim = _fake_sim(64, 4, 3, 3, 0)
+    for d in ('a', 'b'):
+        bench.dump_outputs([sim], str(tmp_path/d), limit=limit)
+    files = sorted(os.listdir(tmp_path/'a'))
+    assert files == sorted(os.listdir(tmp_path/'b')) and 'env_index.npy' in files
+    idx = np.load(tmp_path/'a'/'env_index.npy').astype(int)
+    assert 1 <= idx.size < 64 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path/'a'/'xquat.npy'), sim.physics.data.xquat.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path/'a'/'xfrc.npy'), sim.task.data.sensors.xfrc.array[2].numpy()[idx])
+    assert sum(np.load(tmp_path/'a'/f).nbytes for f in files) <= limit
+    for f in files:
+        assert np.array_equal(np.load(tmp_path/'a'/f), np.load(tmp_path/'b'/f))
