@@ -140,6 +140,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
         dev = [int(x) for x in os.environ.get('FMJ_DEV_MAXD', '').split(',') if x.strip()]
         jobs = [(os.path.join(objdir, 'host.o'), [])] + [(os.path.join(objdir, f'k{n}.o'), [f'-DFMJ_TU_MAXD={n}'])
                                                          for n in range(4, 65, 4)]      # 36 .. 64: the unconstrained one-env kernel only
+        jobs += [(os.path.join(objdir, f'kw{n}.o'), [f'-DFMJ_TU_WIDE={n}']) for n in (32, 64)]      # the two-wave kernel (csrc/fmj_wide.inc)
         if dev:
             todo = [j for j in jobs if not j[1] or int(j[1][0].split('=')[1]) in dev or not os.path.exists(j[0])]
         else:

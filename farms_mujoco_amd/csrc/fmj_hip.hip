@@ -29,6 +29,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <array>
 #include <string>
 #include <vector>
 
@@ -38,6 +39,7 @@
 #define FMJ_MAXD 32         // max dof-chain length (register row length) of models with limits / contacts and of the two-env kernel
 #define FMJ_MAXD_DEEP 64    // ... of the one-env kernel without constraints (long swimmers: an eel of 58 joints)
 #define FMJ_MAXBD 32        // max body-chain length
+#define FMJ_TAB_ROWS 128    // rows of the per-body / per-dof tables: bodies and dofs of the two-wave kernel (fmj_wide.inc)
 
 static thread_local std::string g_err;
 static int set_err(int code, const std::string& msg) { g_err = msg; return code; }
@@ -64,6 +66,12 @@ struct WideRound {
   unsigned long long anc[6];
 };
 
+// The same for the two-wave kernel (fmj_wide.inc): lane masks of 128 bits, anc[c][w] = the ancestors of p[c] among the lanes of wave w
+struct WideRoundW {
+  int p[6], depth, np;
+  unsigned long long anc[6][2];
+};
+
 struct DevModel {
   int nbody, nv, nq, nu, njnt, nM;
   int max_bdepth;     // pointer-jumping rounds = ceil(log2(longest root->body chain))
@@ -75,8 +83,8 @@ struct DevModel {
   int n_links, n_joints, n_xfrc, ns;
   int anc_stride;     // bytes per chain row (multiple of 4)
   float h, gx, gy, gz, mtot_inv;
-  const float4* btab;         // [64][BT_STRIDE]
-  const float4* dtab;         // [64][DT_STRIDE]
+  const float4* btab;         // [FMJ_TAB_ROWS][BT_STRIDE]
+  const float4* dtab;         // [FMJ_TAB_ROWS][DT_STRIDE]
   const float4* atab;         // [nu][AT_STRIDE]
   const float4* stab;         // [ns][ST_STRIDE]
   const float4* gtab;         // [ngeom][GT_STRIDE]
@@ -120,6 +128,10 @@ struct DevModel {
   int maxdep1;                         // deepest dof depth
   const uint32_t* dual_ancl;           // [32][rs / 4] per lane dof: 4 * (lane of its ancestor at each absolute depth), own lane elsewhere
   int dual_maxdep;                     // deepest absolute depth of a lane dof
+  // ---- two-wave kernel (fmj_wide.inc): models of up to 128 bodies / dofs without constraints
+  const struct WideRoundW* roundsw;    // [nroundw] elimination rounds, up to six dofs each
+  int nroundw;
+  const uint32_t* anclw;               // [128][rs / 4] per dof, per depth: lane of its ancestor at that depth (one byte; own lane where there is none)
 };
 
 
@@ -192,6 +204,8 @@ struct fmj_ctx {
   DevModel dm;
   std::vector<void*> allocs;
   size_t lds_bytes, lds_bytes_dual2, lds_bytes_cons2;
+  int wide;                   // every step launch runs the two-wave kernel (fmj_wide.inc): nbody or nv above 64, or FMJ_WIDE=1
+  size_t lds_bytes_wide;
   int* d_resume;              // [n_envs] hand-over of the two-env constraint kernel to the one-env kernel
   int rk4;                    // integrator = RK4: fmj_step runs four forward launches per step (fmj_rk4_stage_kernel between them)
   float *rk_q0, *rk_v0, *rk_sv, *rk_sa, *rk_sd;      // [n_envs][nq | nv | nv | nv | nsensordata] X[0], sum B F, the sensordata the later passes may scribble on
@@ -1966,12 +1980,20 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
 static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TORQUE == 8 && FMJ_JOINT_LIMIT_FORCE == 9 && FMJ_JOINT_SIZE == 12, "the fused kernels store a joints row as three float4");
 #include "fmj_dual2.inc"
 #include "fmj_cons2.inc"
+#include "fmj_wide.inc"
 
 // ---------------------------------------------------------------------------------------------
-// Build layout: this file is compiled once per register row length with -DFMJ_TU_MAXD=<4..32> (only the step-kernel
-// instantiations of that MAXD and a getter for their host stubs) and once without it (standalone operators and all
-// host code), in parallel, and the objects are linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
-#ifdef FMJ_TU_MAXD
+// Build layout: this file is compiled once per register row length with -DFMJ_TU_MAXD=<4..64> (only the step-kernel
+// instantiations of that MAXD and a getter for their host stubs), once per row length of the two-wave kernel with
+// -DFMJ_TU_WIDE=<32|64>, and once without either (standalone operators and all host code), in parallel, and the objects are
+// linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
+#if defined(FMJ_TU_WIDE)
+#define FMJ_CAT2(a, b) a##b
+#define FMJ_CAT(a, b) FMJ_CAT2(a, b)
+extern "C" __attribute__((visibility("hidden"))) void* FMJ_CAT(fmj_tu_wide_, FMJ_TU_WIDE)(int fused) {
+  return fused ? (void*)fmj_step_wide_kernel<true, FMJ_TU_WIDE> : (void*)fmj_step_wide_kernel<false, FMJ_TU_WIDE>;
+}
+#elif defined(FMJ_TU_MAXD)
 #define FMJ_CAT2(a, b) a##b
 #define FMJ_CAT(a, b) FMJ_CAT2(a, b)
 extern "C" __attribute__((visibility("hidden"))) void* FMJ_CAT(fmj_tu_kernel_, FMJ_TU_MAXD)(int fused, int cons, int dual) {
@@ -2275,7 +2297,15 @@ static step_kernel_t pick_kernel(const fmj_ctx* c, bool fused) {
                                       : (c->dm.cone == FMJ_CONE_ELLIPTIC ? (c->dm.npair > 0 ? 9 : 8) : (c->dm.npair > 0 ? 2 : (c->dm.any_mesh ? 4 : 1))));
   return tu_kernel(c->dm.rs, fused, cons, 0);
 }
+extern "C" { void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int); }
+static step_kernel_t wide_kernel(int rs, bool fused) { return (step_kernel_t)(rs <= 32 ? fmj_tu_wide_32(fused) : fmj_tu_wide_64(fused)); }
 static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream) {
+  if (c->wide) {           // one workgroup of two waves per env (fmj_wide.inc): every launch of the context, fmj_forward included
+    hipLaunchKernelGGL(wide_kernel(c->dm.rs, fused), dim3(c->n_envs), dim3(128), c->lds_bytes_wide, (hipStream_t)stream, c->dm, A);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_err(FMJ_ERR_HIP, std::string("two-wave step kernel launch: ") + hipGetErrorString(e));
+    return FMJ_OK;
+  }
   if (c->dm.dual_ok && A.integrate) {      // two envs per wave (fmj_dual2.inc); fmj_forward keeps the single-env kernel
     step_kernel_t k = tu_kernel(c->dm.rs, fused, 0, (c->dual_wps == 2 ? 4 : (c->dual_wps == 3 ? 3 : 2)) + (((fused && A.substeps > 1) || c->dm.implicitfast) ? 16 : 0));      // + 16: the instantiation with the rare options (sub-steps, implicitfast)
     hipLaunchKernelGGL(k, dim3((c->n_envs + 1) / 2), dim3(64), c->lds_bytes_dual2, (hipStream_t)stream, c->dm, A);
@@ -2318,8 +2348,8 @@ static int sync_readout_maps(fmj_ctx* c) {
 
 // re-pack the host-mutable int fields (link row / swim slot / joint row) and refresh the device tables
 static int sync_tables(fmj_ctx* c) {
-  for (int b = 0; b < 64; b++) c->h_btab[b * BT_STRIDE + 8] = make_float4(ibits(c->h_b_info2[4 * b]), ibits(c->h_b_info2[4 * b + 1]), ibits(c->h_b_info2[4 * b + 2]), ibits(c->h_b_info2[4 * b + 3]));
-  for (int d = 0; d < 64; d++) c->h_dtab[d * DT_STRIDE] = make_float4(ibits(c->h_d_info[4 * d]), ibits(c->h_d_info[4 * d + 1]), ibits(c->h_d_info[4 * d + 2]), ibits(c->h_d_info[4 * d + 3]));
+  for (int b = 0; b < FMJ_TAB_ROWS; b++) c->h_btab[b * BT_STRIDE + 8] = make_float4(ibits(c->h_b_info2[4 * b]), ibits(c->h_b_info2[4 * b + 1]), ibits(c->h_b_info2[4 * b + 2]), ibits(c->h_b_info2[4 * b + 3]));
+  for (int d = 0; d < FMJ_TAB_ROWS; d++) c->h_dtab[d * DT_STRIDE] = make_float4(ibits(c->h_d_info[4 * d]), ibits(c->h_d_info[4 * d + 1]), ibits(c->h_d_info[4 * d + 2]), ibits(c->h_d_info[4 * d + 3]));
   HIP_TRY(hipMemcpy(c->d_btab, c->h_btab.data(), c->h_btab.size() * sizeof(float4), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(c->d_dtab, c->h_dtab.data(), c->h_dtab.size() * sizeof(float4), hipMemcpyHostToDevice));
   return FMJ_OK;
@@ -2342,7 +2372,8 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   *out = nullptr;
   if (m->abi_version != FMJ_ABI_VERSION) return set_err(FMJ_ERR_ARG, "fmj_create: abi_version mismatch");
   const int nb = m->nbody, nv = m->nv, nq = m->nq, nu = m->nu, nj = m->njnt;
-  if (nb < 2 || nb > 64 || nv < 1 || nv > 64) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: need 2 <= nbody <= 64 and 1 <= nv <= 64 (one wavefront per environment)");
+  if (nb < 2 || nb > 128 || nv < 1 || nv > 128) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: need 2 <= nbody <= 128 and 1 <= nv <= 128 (two wavefronts per environment at most)");
+  const bool big = nb > 64 || nv > 64;      // past one wavefront: the two-wave kernel (fmj_wide.inc), unconstrained models only
   int any_limit = 0, nplane = 0, any_box = 0, n_hfield = 0, any_mesh = 0, any_polypair = 0;     // nplane counts the ground geoms: planes and the heightfield
   for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) any_limit = 1;
   for (int g = 0; g < m->ngeom; g++) {
@@ -2384,6 +2415,7 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
     if (m->geom_bodyid[g1] == m->geom_bodyid[g2]) return set_err(FMJ_ERR_ARG, "fmj_create: a contact pair joins geoms of two bodies");
   }
   const int cons = any_limit || (nplane > 0 && m->ngeom > nplane) || m->npair > 0;
+  if (big && cons) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: nbody or nv above 64 with limits, contacts or pairs (one wavefront per environment on the constraint path)");
   if (cons && m->solver != FMJ_SOLVER_PGS && m->solver != FMJ_SOLVER_NEWTON && m->solver != FMJ_SOLVER_CG) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: solver must be FMJ_SOLVER_PGS, FMJ_SOLVER_CG or FMJ_SOLVER_NEWTON");
   if (cons && m->cone != FMJ_CONE_PYRAMIDAL && m->cone != FMJ_CONE_ELLIPTIC) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: cone must be FMJ_CONE_PYRAMIDAL or FMJ_CONE_ELLIPTIC");
   // Pyramid rows carry R = 2 mu^2 R0: below mu ~ 1e-3 (the reference's arena has friction 0, mjcf.py:1202, so a contact's friction is
@@ -2404,6 +2436,7 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   if (m->noslip_iterations < 0 || !(m->noslip_tolerance >= 0)) return set_err(FMJ_ERR_ARG, "fmj_create: noslip_iterations / noslip_tolerance must not be negative");
   if (m->integrator != FMJ_INT_EULER && m->integrator != FMJ_INT_IMPLICITFAST && m->integrator != FMJ_INT_RK4)
     return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: integrator must be FMJ_INT_EULER, FMJ_INT_IMPLICITFAST or FMJ_INT_RK4 (implicit keeps the Coriolis derivatives, a non-symmetric matrix outside this path's tree-sparse factorisation)");
+  if (big && m->integrator == FMJ_INT_RK4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: RK4 on a model with more than 64 bodies or dofs (its stage kernel holds one dof per lane of one wavefront)");
   if (cons && (m->ngeom > nplane || m->npair > 0) && !any_limit && m->max_contacts < 1) return set_err(FMJ_ERR_ARG, "fmj_create: max_contacts must be >= 1 with collision geoms");
   if ((m->npair > 0 || (nplane > 0 && m->ngeom > nplane)) && m->max_contacts < 1) return set_err(FMJ_ERR_ARG, "fmj_create: max_contacts must be >= 1 with collision geoms");
   // structure checks: single tree rooted at body 1, DFS pre-order, <= 1 joint per body
@@ -2445,7 +2478,8 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   }
   for (int d = nv - 1; d >= 0; d--) if (m->dof_parentid[d] >= 0) dsub[m->dof_parentid[d]] += dsub[d];
   if (max_ddepth + 1 > (cons ? FMJ_MAXD : FMJ_MAXD_DEEP))
-    return set_err(FMJ_ERR_UNSUPPORTED, cons ? "fmj_create: dof chain longer than 32 in a model with limits / contacts (64 without)" : "fmj_create: dof chain longer than 64");
+    return set_err(FMJ_ERR_UNSUPPORTED, cons ? "fmj_create: dof chain longer than 32 in a model with limits / contacts (64 without)"
+                                             : "fmj_create: dof chain longer than 64 (a row of the inertia matrix is held by one wavefront lane)");
   std::vector<int> nact(nj, 0);
   for (int a = 0; a < nu; a++) {
     int j = m->actuator_jntid[a];
@@ -2467,6 +2501,11 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   { int rounds = 0; while ((1 << rounds) < max_bdepth) rounds++; D.max_bdepth = rounds; }   // pointer-jumping rounds
   D.max_subsize = max_sub;
   D.rs = r4(max_ddepth + 1);
+  {   // FMJ_WIDE=1: the two-wave kernel on any unconstrained model (tests hold it against the one-wave kernel; scripts measure the second wave)
+    const char* wenv = getenv("FMJ_WIDE");
+    c->wide = big || (!cons && m->integrator != FMJ_INT_RK4 && wenv && wenv[0] == '1');
+    if (c->wide) D.rs = D.rs <= 32 ? 32 : 64;     // the row lengths the two-wave kernel is instantiated at
+  }
   D.root_free = m->body_jntadr[1] >= 0 && m->jnt_type[m->body_jntadr[1]] == FMJ_JNT_FREE;
   D.h = (float)m->timestep; D.gx = (float)m->gravity[0]; D.gy = (float)m->gravity[1]; D.gz = (float)m->gravity[2];
   double mtot = 0; for (int i = 1; i < nb; i++) mtot += m->body_mass[i];
@@ -2478,14 +2517,15 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   c->layout.actuatorfrc_adr = 6 * (nb - 1) + 3 * njs; c->layout.first_link_body = 1;
   c->layout.first_sensor_jnt = D.root_free ? 1 : 0;
 
-  std::vector<float4> b_pos_mass(64), b_quat(64), b_ipos(64), b_iquat(64), b_inertia(64), j_axis_q0(64), j_pos_k(64);
-  std::vector<int4> b_info(64), b_info2(64), d_info(64), d_act(64);
-  std::vector<float4> d_prm(64);
+  constexpr int NT = FMJ_TAB_ROWS;
+  std::vector<float4> b_pos_mass(NT), b_quat(NT), b_ipos(NT), b_iquat(NT), b_inertia(NT), j_axis_q0(NT), j_pos_k(NT);
+  std::vector<int4> b_info(NT), b_info2(NT), d_info(NT), d_act(NT);
+  std::vector<float4> d_prm(NT);
   std::vector<uint8_t> b_anc((size_t)r4(nb * D.anc_stride), 0);
   c->body_link_row.assign(nb, -1); c->dof_joint_row.assign(nv, -1); c->body_swim.assign(nb, -1);
   c->jnt_dofadr.assign(m->jnt_dofadr, m->jnt_dofadr + nj); c->jnt_type.assign(m->jnt_type, m->jnt_type + nj);
   int any_k = 0;
-  for (int i = 0; i < 64; i++) {
+  for (int i = 0; i < NT; i++) {
     b_pos_mass[i] = f4(0, 0, 0, 0); b_quat[i] = f4(1, 0, 0, 0); b_ipos[i] = f4(0, 0, 0, 0); b_iquat[i] = f4(1, 0, 0, 0);
     b_inertia[i] = f4(0, 0, 0, 0); j_axis_q0[i] = f4(0, 0, 1, 0); j_pos_k[i] = f4(0, 0, 0, 0);
     b_info[i] = make_int4(0, -1, 0, 0); b_info2[i] = make_int4(-1, 0, -1, -1);
@@ -2555,8 +2595,8 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
     for (int j = i; j >= 0; j = m->dof_parentid[j]) e++;
   }
   if (e != m->nM) { fmj_destroy(c); return set_err(FMJ_ERR_ARG, "fmj_create: nM inconsistent"); }
-  c->h_b_info2.assign((int*)b_info2.data(), (int*)b_info2.data() + 64 * 4);
-  c->h_d_info.assign((int*)d_info.data(), (int*)d_info.data() + 64 * 4);
+  c->h_b_info2.assign((int*)b_info2.data(), (int*)b_info2.data() + NT * 4);
+  c->h_d_info.assign((int*)d_info.data(), (int*)d_info.data() + NT * 4);
 
   {   // subtree mass (a model constant) rides in ipos.w
     std::vector<double> smass(nb, 0.0);
@@ -2597,11 +2637,11 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   D.ls_tolerance = (float)(m->ls_tolerance > 0 ? m->ls_tolerance : 0.01);
   D.impratio_isqrt = (float)(1.0 / sqrt(m->impratio > 0 ? m->impratio : 1.0));
   D.pgs_scale = (float)(1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1)));
-  std::vector<int> d_parent(64, -1);
+  std::vector<int> d_parent(NT, -1);
   for (int d = 0; d < nv; d++) d_parent[d] = m->dof_parentid[d];
   std::vector<int4> g_info(m->ngeom ? m->ngeom : 1); std::vector<float4> g_size(g_info.size()), g_pos(g_info.size()), g_quat(g_info.size()), g_sol0(g_info.size()), g_sol1(g_info.size());
   std::vector<float4> p_plane(nplane ? nplane : 1), p_prm(nplane ? nplane : 1), p_hq(nplane ? nplane : 1, f4(1, 0, 0, 0)), p_hs(nplane ? nplane : 1, f4(1, 1, 0, 0));
-  std::vector<float4> d_lim(64, f4(0, 0, 0, 0)), d_sol0(64, f4(0.02, 1, 0.9, 0.95)), d_sol1(64, f4(0.001, 0.5, 2, 0));
+  std::vector<float4> d_lim(NT, f4(0, 0, 0, 0)), d_sol0(NT, f4(0.02, 1, 0.9, 0.95)), d_sol1(NT, f4(0.001, 0.5, 2, 0));
   if (cons) {
     int ip = 0;
     for (int g = 0; g < m->ngeom; g++) {
@@ -2651,13 +2691,13 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   }
   // ---- pack the tables (one device array per family)
   auto i4f = [](int4 v) { return make_float4(ibits(v.x), ibits(v.y), ibits(v.z), ibits(v.w)); };
-  c->h_btab.assign(64 * BT_STRIDE, f4(0, 0, 0, 0)); c->h_dtab.assign(64 * DT_STRIDE, f4(0, 0, 0, 0));
-  for (int b = 0; b < 64; b++) {
+  c->h_btab.assign(NT * BT_STRIDE, f4(0, 0, 0, 0)); c->h_dtab.assign(NT * DT_STRIDE, f4(0, 0, 0, 0));
+  for (int b = 0; b < NT; b++) {
     float4* t = &c->h_btab[b * BT_STRIDE];
     t[0] = b_pos_mass[b]; t[1] = b_quat[b]; t[2] = b_ipos[b]; t[3] = b_iquat[b]; t[4] = b_inertia[b]; t[5] = j_axis_q0[b]; t[6] = j_pos_k[b];
     t[7] = i4f(b_info[b]); t[8] = i4f(b_info2[b]);
   }
-  for (int d = 0; d < 64; d++) {
+  for (int d = 0; d < NT; d++) {
     float4* t = &c->h_dtab[d * DT_STRIDE];
     int4 act = d_act[d]; act.w = d_parent[d];
     t[0] = i4f(d_info[d]); t[1] = d_prm[d]; t[2] = i4f(act); t[3] = d_lim[d]; t[4] = d_sol0[d]; t[5] = d_sol1[d];
@@ -2705,14 +2745,14 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
     D.dual_t0 = t0;
     const bool halves_ok = nb <= 32 && nv - t0 <= 32 && !(envv && envv[0] == '0');      // bodies / lane dofs of an env fit half a wave
     const bool rk4 = m->integrator == FMJ_INT_RK4;      // four forward launches of the one-env kernel per step: no two-env kernel, no fused launch
-    D.dual_ok = !cons && halves_ok && !rk4;
+    D.dual_ok = !cons && halves_ok && !rk4 && !c->wide;
     // the two-env constraint kernel covers what BASELINE configs[3] needs: limits + ground contacts of sphere / capsule / box / cylinder
     // geoms on ONE ground geom, pyramidal cone, PGS; everything else (pairs, meshes, Newton / CG, the elliptic cone) keeps the one-env kernel
     D.cons2_ok = cons && halves_ok && !rk4 && D.rs <= FMJ_MAXD && m->solver == FMJ_SOLVER_PGS && !dual_instead && m->cone == FMJ_CONE_PYRAMIDAL && m->noslip_iterations == 0 && m->npair == 0 &&
                  !any_mesh && nplane <= 1 && m->ngeom <= 32;
     for (int t = 0; t < 3; t++) D.dual_tadd[t] = t < t0 ? (float)(mtot + m->dof_armature[t] + m->timestep * m->dof_damping[t]) : 1.0f;
     for (int t = 0; t < 3; t++) D.dual_taddm[t] = t < t0 ? (float)(mtot + m->dof_armature[t]) : 1.0f;
-    {   // elimination rounds of the one-env kernel (lane = dof): dofs grouped by depth, deepest first, <= 3 per round
+    if (nv <= 64) {   // elimination rounds of the one-env kernel (lane = dof): dofs grouped by depth, deepest first, <= 3 per round
       std::vector<DualRound> rounds;
       std::vector<unsigned long long> ancm(nv, 0ull), descm(nv, 0ull);
       int maxdep = 0;
@@ -2762,6 +2802,37 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
         D.maxdep1 = maxdep;
         UP(ancl, ancl1);
       }
+    }
+    if (c->wide) {   // the two-wave kernel: rounds with 128-bit lane masks, ancestor lanes as one byte each
+      std::vector<std::array<unsigned long long, 2>> ancm(nv);
+      for (int i = 0; i < nv; i++) {
+        ancm[i] = {0ull, 0ull};
+        for (int a = m->dof_parentid[i]; a >= 0; a = m->dof_parentid[a]) ancm[i][a >> 6] |= 1ull << (a & 63);
+      }
+      std::vector<WideRoundW> rounds;
+      for (int dep = max_ddepth; dep >= 0; dep--) {
+        std::vector<int> lvl;
+        for (int i = 0; i < nv; i++) if (ddepth[i] == dep) lvl.push_back(i);
+        for (size_t q = 0; q < lvl.size(); q += 6) {
+          WideRoundW R; memset(&R, 0, sizeof R);
+          R.depth = dep; R.np = (int)std::min<size_t>(6, lvl.size() - q);
+          for (int k = 0; k < 6; k++) {
+            if (q + k < lvl.size()) { R.p[k] = lvl[q + k]; R.anc[k][0] = ancm[lvl[q + k]][0]; R.anc[k][1] = ancm[lvl[q + k]][1]; }
+            else R.p[k] = lvl[q];                   // under empty masks
+          }
+          rounds.push_back(R);
+        }
+      }
+      D.nroundw = (int)rounds.size();
+      UP(rounds, roundsw);
+      std::vector<uint32_t> ancl((size_t)FMJ_WIDE_LANES * (D.rs / 4), 0u);
+      for (int i = 0; i < FMJ_WIDE_LANES; i++) {
+        uint8_t* row = (uint8_t*)&ancl[(size_t)i * (D.rs / 4)];
+        for (int l = 0; l < D.rs; l++) row[l] = (uint8_t)i;
+        if (i < nv) for (int a = m->dof_parentid[i]; a >= 0; a = m->dof_parentid[a]) row[ddepth[a]] = (uint8_t)a;
+      }
+      UP(ancl, anclw);
+      D.maxdep1 = max_ddepth;
     }
     {   // elimination rounds: lane dofs grouped by depth, deepest first, at most three per round
       const int nd = nv - t0 > 0 ? nv - t0 : 0;
@@ -2843,6 +2914,8 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   c->lds_bytes = (size_t)L.total * sizeof(float);
   c->lds_bytes_dual2 = D.dual_ok ? (size_t)(2 * lds2_layout(nb, nv, nq, D.rs, D.dual_t0).total + r4(nb * D.anc_stride) / 4) * sizeof(float) : 0;
   c->lds_bytes_cons2 = 0; c->d_resume = nullptr;
+  c->lds_bytes_wide = c->wide ? (size_t)ldsw_layout(nb, nv, nq, D.rs, D.anc_stride).total * sizeof(float) : 0;
+  if (c->lds_bytes_wide > 64 * 1024) { fmj_destroy(c); return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: two-wave kernel LDS above 64 KB"); }     // (cannot happen within the size limits above)
   if (D.cons2_ok) {
     c->lds_bytes_cons2 = (size_t)lds3_layout(nb, nv, nq, D.rs, D.dual_t0, D.max_contacts, D.anc_stride).total * sizeof(float);
     void* pr = nullptr;
@@ -2868,7 +2941,7 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
     const char* w = getenv("FMJ_WPS");
     if (w && (w[0] == '2' || w[0] == '3' || w[0] == '4')) c->dual_wps = w[0] - '0';
   }
-  if (c->lds_bytes > 64 * 1024) {
+  if (!c->wide && c->lds_bytes > 64 * 1024) {
     hipError_t e1 = hipFuncSetAttribute((const void*)pick_kernel(c, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     hipError_t e2 = hipFuncSetAttribute((const void*)pick_kernel(c, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     if (e1 != hipSuccess || e2 != hipSuccess) { fmj_destroy(c); return set_err(FMJ_ERR_HIP, "fmj_create: LDS request too large"); }
@@ -2884,6 +2957,11 @@ int fmj_get_sensor_layout(const fmj_ctx* c, fmj_sensor_layout_t* out) {
 
 int fmj_kernel_info(const fmj_ctx* c, int32_t* lds_bytes_per_env, int32_t* threads_per_env) {
   if (!c) return set_err(FMJ_ERR_ARG, "fmj_kernel_info: NULL ctx");
+  if (c->wide) {           // one workgroup of two waves per env (fmj_wide.inc)
+    if (lds_bytes_per_env) *lds_bytes_per_env = (int32_t)c->lds_bytes_wide;
+    if (threads_per_env) *threads_per_env = 128;
+    return FMJ_OK;
+  }
   if (lds_bytes_per_env) *lds_bytes_per_env = (int32_t)(c->dm.dual_ok ? c->lds_bytes_dual2 / 2 : (c->dm.cons2_ok ? c->lds_bytes_cons2 / 2 : c->lds_bytes));
   if (threads_per_env) *threads_per_env = (c->dm.dual_ok || c->dm.cons2_ok) ? 32 : 64;   // the integrating step packs two envs per wave when it can
   return FMJ_OK;
@@ -2896,7 +2974,7 @@ int fmj_set_swimming(fmj_ctx* c, int32_t ns, int32_t n_xfrc_rows, const int32_t*
     return set_err(FMJ_ERR_ARG, "fmj_set_swimming: NULL argument");
   HIP_TRY(hipSetDevice(c->device));
   std::vector<float4> c0(ns ? ns : 1), c1(ns ? ns : 1), c2(ns ? ns : 1);
-  for (int b = 0; b < 64; b++) c->h_b_info2[4 * b + 3] = -1;
+  for (int b = 0; b < FMJ_TAB_ROWS; b++) c->h_b_info2[4 * b + 3] = -1;
   for (int s = 0; s < ns; s++) {
     int b = body_index[s];
     if (b < 1 || b >= c->nbody) return set_err(FMJ_ERR_ARG, "fmj_set_swimming: body index out of range");
@@ -2941,8 +3019,8 @@ int fmj_set_actuator_forcerange(fmj_ctx* c, int32_t nu, const int32_t* forcelimi
 int fmj_set_readout_maps(fmj_ctx* c, int32_t n_links, const int32_t* links_body, int32_t n_joints, const int32_t* joints_jnt) {
   if (!c || n_links < 0 || n_joints < 0 || (n_links && !links_body) || (n_joints && !joints_jnt)) return set_err(FMJ_ERR_ARG, "fmj_set_readout_maps: NULL argument");
   HIP_TRY(hipSetDevice(c->device));
-  for (int b = 0; b < 64; b++) c->h_b_info2[4 * b + 2] = -1;
-  for (int d = 0; d < 64; d++) c->h_d_info[4 * d + 3] = -1;
+  for (int b = 0; b < FMJ_TAB_ROWS; b++) c->h_b_info2[4 * b + 2] = -1;
+  for (int d = 0; d < FMJ_TAB_ROWS; d++) c->h_d_info[4 * d + 3] = -1;
   for (int i = 0; i < n_links; i++) {
     int b = links_body[i];
     if (b < 1 || b >= c->nbody) return set_err(FMJ_ERR_ARG, "fmj_set_readout_maps: link body out of range");

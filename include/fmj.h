@@ -288,13 +288,18 @@ typedef struct fmj_ctx fmj_ctx;   /* opaque */
 
 /* ---- lifecycle ---------------------------------------------------------------------------- */
 /* Replaces mjcf.Physics.from_mjcf_model (reference simulation.py:53): validates the model,
- * builds the level / ancestor tables, uploads the fp32 device copy. `device` = HIP ordinal. */
+ * builds the level / ancestor tables, uploads the fp32 device copy. `device` = HIP ordinal.
+ * Model size: nbody <= 128 and nv <= 128, a dof chain of at most 64 (32 with limits / contacts).  A model past 64 bodies or dofs
+ * steps on one workgroup of two wavefronts per environment and must have no limits, contacts or pairs and not use RK4; these
+ * are FMJ_ERR_UNSUPPORTED with the limit named in fmj_last_error().  FMJ_WIDE=1 in the environment at fmj_create runs the
+ * two-wave kernel on any unconstrained, non-RK4 model (to compare it with the one-wave kernels). */
 int fmj_create(const fmj_model* model, int32_t n_envs, int32_t device, fmj_ctx** out);
 void fmj_destroy(fmj_ctx* ctx);
 const char* fmj_last_error(void);
 int fmj_abi_version(void);
 int fmj_get_sensor_layout(const fmj_ctx* ctx, fmj_sensor_layout_t* out);
-/* LDS bytes / VGPR-independent facts the host needs for reporting */
+/* LDS bytes / VGPR-independent facts the host needs for reporting; threads_per_env is 32 (two envs per wave), 64 (one wave) or
+ * 128 (two waves: models past 64 bodies / dofs, or FMJ_WIDE=1) */
 int fmj_kernel_info(const fmj_ctx* ctx, int32_t* lds_bytes_per_env, int32_t* threads_per_env);
 
 /* ---- swimming links (SwimmingHandler.__init__, reference drag.pyx:333-387) ------------------
