@@ -811,8 +811,9 @@ def eel(n_joints: int = 20, timestep: float = 1e-3) -> Model:
     return b.compile()
 
 
-def centipede(n_segments: int = 10, n_spine_joints: int = 15, timestep: float = 1e-3) -> Model:
-    """Config-5 centipede: free + 15 spine hinges + 2x2-DoF legs on 10 segments (nv = 61)."""
+def centipede(n_segments: int = 10, n_spine_joints: int = 15, timestep: float = 1e-3, full_actuators: bool = False) -> Model:
+    """Config-5 centipede: free + 15 spine hinges + 2x2-DoF legs on 10 segments (nv = 61).  ``full_actuators``: the position /
+    velocity / motor triple of mjcf.py:819-854 on every joint (salamander33's layout) instead of the position actuator alone."""
     b = ModelBuilder('centipede', timestep=timestep)
     L, r = 0.03, 0.006
     n = n_spine_joints + 1
@@ -840,7 +841,11 @@ def centipede(n_segments: int = 10, n_spine_joints: int = 15, timestep: float = 
                 b.set_swimming(up, drag_coefficients=[[-1e-4]*3, [-1e-7]*3], height=0.001)
                 b.set_swimming(lo, drag_coefficients=[[-0.02, -0.0002, -0.02], [-1e-7]*3], height=0.004)
     for jn in [x for x in [bd.joint['name'] for bd in b.bodies[1:] if bd.joint] if not x.startswith('root_')]:
-        b.add_position_actuator(jn, kp=0.2 if jn.startswith('joint_body_') else 0.05)
+        kp = 0.2 if jn.startswith('joint_body_') else 0.05
+        if full_actuators:
+            b.add_joint_actuators(jn, kp=kp, kv=0.0)
+        else:
+            b.add_position_actuator(jn, kp=kp)
     return b.compile()
 
 
