@@ -161,7 +161,10 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
                 if os.path.exists(tmp):
                     os.remove(tmp)
             return obj
-        with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 1)) as ex:
+        # MAX_JOBS caps the parallel compiles (a shared machine's os.cpu_count() is not this process's share of it)
+        cap = os.environ.get('MAX_JOBS', '').strip()
+        workers = int(cap) if cap.isdigit() and int(cap) > 0 else (os.cpu_count() or 1)
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(todo), workers)) as ex:
             list(ex.map(cc, todo))
         tmp_target = f'{target}.{os.getpid()}.tmp'
         cmd = ['hipcc', '--offload-arch=gfx950', '-shared', '-fPIC'] + [j[0] for j in jobs] + ['-o', tmp_target]

@@ -30,6 +30,7 @@
 #include <string.h>
 
 #include <array>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -199,28 +200,45 @@ struct StepArgs {
 static_assert(alignof(DevModel) == 8 && alignof(StepArgs) == 8, "kernarg layout of (DevModel, StepArgs)");
 #define FMJ_KARG_A_OFF ((sizeof(DevModel) + 7) & ~(size_t)7)
 
+// The step-kernel instantiations of one row length (fmj_tu_kernel_<rs>): the one-env kernel by what its constraint code covers
+// (fmj_step_kernel<.., CONS, PAIRS, NEWTON, MESH, ELL>), the two-env kernel (fmj_dual2.inc) by the waves per SIMD its registers are
+// budgeted for, without and with the rare options (sub-steps, implicitfast), and the two-env constraint kernel (fmj_cons2.inc).
+// ELL: the elliptic cone (+ meshes); PAIRS: explicit pairs (+ meshes); MESH: meshes without pairs.
+enum StepVariant {
+  SV_PLAIN, SV_PGS, SV_PGS_PAIRS, SV_NEWTON, SV_PGS_MESH, SV_NEWTON_MESH, SV_NEWTON_ELL, SV_NEWTON_PAIRS, SV_PGS_ELL, SV_PGS_ELL_PAIRS,
+  SV_DUAL_W2, SV_DUAL_W3, SV_DUAL_W4, SV_DUAL_W2_RARE, SV_DUAL_W3_RARE, SV_DUAL_W4_RARE, SV_CONS2,
+};
+
+// The kernels the step launches of a context run (fmj_create chooses, launch_step launches)
+enum StepPath {
+  PATH_ONE_ENV,         // one wave per env: the one-env kernel (fmj_ctx::variant)
+  PATH_TWO_ENV,         // integrating steps: two envs per wave (fmj_dual2.inc); fmj_forward: the one-env kernel
+  PATH_CONS2_ONE_ENV,   // integrating steps: the two-env constraint kernel (fmj_cons2.inc), then the one-env kernel for the envs it hands over
+  PATH_TWO_WAVE,        // one workgroup of two waves per env (fmj_wide.inc), fmj_forward included: nbody or nv above 64, or FMJ_WIDE=1
+};
+
 struct fmj_ctx {
-  int device, n_envs;
-  DevModel dm;
-  std::vector<void*> allocs;
-  size_t lds_bytes, lds_bytes_dual2, lds_bytes_cons2;
-  int wide;                   // every step launch runs the two-wave kernel (fmj_wide.inc): nbody or nv above 64, or FMJ_WIDE=1
-  size_t lds_bytes_wide;
-  int* d_resume;              // [n_envs] hand-over of the two-env constraint kernel to the one-env kernel
-  int rk4;                    // integrator = RK4: fmj_step runs four forward launches per step (fmj_rk4_stage_kernel between them)
-  float *rk_q0, *rk_v0, *rk_sv, *rk_sa, *rk_sd;      // [n_envs][nq | nv | nv | nv | nsensordata] X[0], sum B F, the sensordata the later passes may scribble on
-  int solver_requested;       // fmj_model.solver as handed in (fmj_create may run the dual solver instead: fmj_solver_info)
-  int dual_wps;               // waves per SIMD the dual2 build is registered for: 4, or 3 when the batch cannot fill more (FMJ_WPS overrides)
-  fmj_sensor_layout_t layout;
+  int device = 0, n_envs = 0;
+  DevModel dm = {};
+  std::vector<void*> allocs;  // device memory of the context (fmj_destroy)
+  StepPath path = PATH_ONE_ENV;
+  StepVariant variant = SV_PLAIN;        // of the one-env kernel
+  int dual_wps = 4;           // waves per SIMD the dual2 build is registered for: 2, 3 or 4, the most the batch fills (FMJ_WPS overrides)
+  size_t lds_bytes = 0, lds_bytes_dual2 = 0, lds_bytes_cons2 = 0, lds_bytes_wide = 0;
+  int* d_resume = nullptr;    // [n_envs] hand-over of the two-env constraint kernel to the one-env kernel
+  int rk4 = 0;                // integrator = RK4: fmj_step runs four forward launches per step (fmj_rk4_stage_kernel between them)
+  float *rk_q0 = nullptr, *rk_v0 = nullptr, *rk_sv = nullptr, *rk_sa = nullptr, *rk_sd = nullptr;      // [n_envs][nq | nv | nv | nv | nsensordata] X[0], sum B F, the sensordata the later passes may scribble on
+  int solver_requested = 0;   // fmj_model.solver as handed in (fmj_create may run the dual solver instead: fmj_solver_info)
+  fmj_sensor_layout_t layout = {};
   // host copies needed later
   std::vector<int> body_link_row, dof_joint_row, body_swim;
   std::vector<int> h_b_info2;     // mutable table mirror
   std::vector<int> h_d_info;
-  float4* d_btab; float4* d_dtab; std::vector<float4> h_btab, h_dtab;
-  int nbody, nv, nu, njnt;
+  float4* d_btab = nullptr; float4* d_dtab = nullptr; std::vector<float4> h_btab, h_dtab;
+  int nbody = 0, nv = 0, nu = 0, njnt = 0;
   std::vector<int> jnt_dofadr, jnt_type;
-  int ngeom, n_contact_rows, n_pairs; std::vector<int> geom_sensor, geom_is_plane; int* d_geom_sensor; int* d_pairs;
-  int* d_links_body; int* d_joints_dof;      // row -> body / dof maps of the standalone readout operator
+  int ngeom = 0, n_contact_rows = 0, n_pairs = 0; std::vector<int> geom_sensor, geom_is_plane; int* d_geom_sensor = nullptr; int* d_pairs = nullptr;
+  int* d_links_body = nullptr; int* d_joints_dof = nullptr;      // row -> body / dof maps of the standalone readout operator
   std::vector<float4> h_atab; std::vector<int> a_src;   // actuator table mirror (fmj_set_actuator_forcerange)
 };
 
@@ -1987,59 +2005,60 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 // instantiations of that MAXD and a getter for their host stubs), once per row length of the two-wave kernel with
 // -DFMJ_TU_WIDE=<32|64>, and once without either (standalone operators and all host code), in parallel, and the objects are
 // linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
-#if defined(FMJ_TU_WIDE)
+
 #define FMJ_CAT2(a, b) a##b
 #define FMJ_CAT(a, b) FMJ_CAT2(a, b)
+#if defined(FMJ_TU_WIDE)
 extern "C" __attribute__((visibility("hidden"))) void* FMJ_CAT(fmj_tu_wide_, FMJ_TU_WIDE)(int fused) {
   return fused ? (void*)fmj_step_wide_kernel<true, FMJ_TU_WIDE> : (void*)fmj_step_wide_kernel<false, FMJ_TU_WIDE>;
 }
 #elif defined(FMJ_TU_MAXD)
-#define FMJ_CAT2(a, b) a##b
-#define FMJ_CAT(a, b) FMJ_CAT2(a, b)
-extern "C" __attribute__((visibility("hidden"))) void* FMJ_CAT(fmj_tu_kernel_, FMJ_TU_MAXD)(int fused, int cons, int dual) {
-#if FMJ_TU_MAXD > 32        // rows longer than 32: the unconstrained one-env kernel only (FMJ_MAXD_DEEP)
-  (void)cons; (void)dual;
-  return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, false> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, false>;
-#elif defined(FMJ_DEV_DUAL2_ONLY)      // development build: only the fused two-env kernels (compile time)
-  (void)cons;
-  if (dual == 2) return fused ? (void*)fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 4> : nullptr;
-  if (dual == 4) return fused ? (void*)fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 2> : nullptr;
-  if (dual == 3) return fused ? (void*)fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 3> : nullptr;
-  return nullptr;
-#elif defined(FMJ_DEV_CONS2_FUSED_ONLY)      // development build: the fused two-env constraint kernel alone (resource remarks, ISA listings)
-  (void)cons;
-  if (dual == 5) return fused ? (void*)fmj_step_cons2_kernel<true, FMJ_TU_MAXD> : nullptr;
-  return nullptr;
-#elif defined(FMJ_DEV_PGSOPT_ONLY)      // development build: the one-env constraint kernels of the PGS options (elliptic cone, noslip)
-  if (dual) return nullptr;
-  if (cons == 9) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, true, false, true, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, true, false, true, true>;
-  if (cons == 8) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, false, false, true, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, false, false, true, true>;
-  if (cons == 1) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true>;
-  return nullptr;
-#elif defined(FMJ_DEV_CONS2_ONLY)      // development build: only the two-env constraint kernel and its one-env fallback (compile time)
-  if (dual == 5) return fused ? (void*)fmj_step_cons2_kernel<true, FMJ_TU_MAXD> : (void*)fmj_step_cons2_kernel<false, FMJ_TU_MAXD>;
-  if (cons == 1 && dual == 0) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true>;
-  return nullptr;
+// the instantiations this translation unit compiles: rows longer than 32 serve the unconstrained one-env kernel only (FMJ_MAXD_DEEP);
+// the development builds keep a subset (compile time, resource remarks, ISA listings)
+constexpr bool tu_builds([[maybe_unused]] StepVariant v, [[maybe_unused]] bool fused) {
+#if FMJ_TU_MAXD > 32
+  return v == SV_PLAIN;
+#elif defined(FMJ_DEV_DUAL2_ONLY)          // the fused two-env kernels
+  return fused && (v == SV_DUAL_W4 || v == SV_DUAL_W2 || v == SV_DUAL_W3);
+#elif defined(FMJ_DEV_CONS2_FUSED_ONLY)    // the fused two-env constraint kernel alone
+  return fused && v == SV_CONS2;
+#elif defined(FMJ_DEV_PGSOPT_ONLY)         // the one-env constraint kernels of the PGS options (elliptic cone, noslip)
+  return v == SV_PGS_ELL_PAIRS || v == SV_PGS_ELL || v == SV_PGS;
+#elif defined(FMJ_DEV_CONS2_ONLY)          // the two-env constraint kernel and its one-env fallback
+  return v == SV_CONS2 || v == SV_PGS;
 #else
-  if (dual == 5) return fused ? (void*)fmj_step_cons2_kernel<true, FMJ_TU_MAXD> : (void*)fmj_step_cons2_kernel<false, FMJ_TU_MAXD>;
-  if (dual >= 16 && !fused) return (void*)fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 4, true>;      // single steps with the rare options (implicitfast): one register tier is enough, they are launch-bound
-  if (dual == 16 + 2) return (void*)fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 4, true>;      // fused launches with sub-steps / implicitfast
-  if (dual == 16 + 4) return (void*)fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 2, true>;
-  if (dual == 16 + 3) return (void*)fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 3, true>;
-  if (dual == 2) return fused ? (void*)fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 4> : (void*)fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 4>;
-  if (dual == 4) return fused ? (void*)fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 2> : (void*)fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 2>;
-  if (dual == 3) return fused ? (void*)fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 3> : (void*)fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 3>;
-  if (cons == 9) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, true, false, true, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, true, false, true, true>;
-  if (cons == 8) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, false, false, true, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, false, false, true, true>;
-  if (cons == 7) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, true, true, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, true, true, true>;
-  if (cons == 6) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, false, true, true, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, false, true, true, true>;
-  if (cons == 5) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, false, true, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, false, true, true>;
-  if (cons == 4) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, false, false, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, false, false, true>;
-  if (cons == 3) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, false, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, false, true>;
-  if (cons == 2) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true, true>;
-  if (cons) return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, true> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, true>;
-  return fused ? (void*)fmj_step_kernel<true, FMJ_TU_MAXD, false> : (void*)fmj_step_kernel<false, FMJ_TU_MAXD, false>;
+  return true;
 #endif
+}
+// K, or nullptr where tu_builds leaves it out (a discarded branch instantiates nothing).  The cases below name the kernels in the
+// order their device code is emitted in.
+#define FMJ_OR_NULL(V, FUSED, K) if constexpr (tu_builds(V, FUSED)) return (void*)K; else return nullptr
+#define FMJ_PICK(V, KT, KF) do { if (fused) { FMJ_OR_NULL(V, true, KT); } FMJ_OR_NULL(V, false, KF); } while (0)
+// the rare options (fused sub-steps, implicitfast): single steps run one register tier, they are launch-bound
+#define FMJ_PICK_RARE(V, KT) do { if (!fused) { FMJ_OR_NULL(V, false, (fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 4, true>)); } FMJ_OR_NULL(V, true, KT); } while (0)
+#define FMJ_PICK_ONE(V, ...) FMJ_PICK(V, (fmj_step_kernel<true, FMJ_TU_MAXD, __VA_ARGS__>), (fmj_step_kernel<false, FMJ_TU_MAXD, __VA_ARGS__>))
+extern "C" __attribute__((visibility("hidden"))) void* FMJ_CAT(fmj_tu_kernel_, FMJ_TU_MAXD)(int fused, int variant) {
+  switch ((StepVariant)variant) {
+    case SV_CONS2:         FMJ_PICK(SV_CONS2, (fmj_step_cons2_kernel<true, FMJ_TU_MAXD>), (fmj_step_cons2_kernel<false, FMJ_TU_MAXD>));
+    case SV_DUAL_W4_RARE:  FMJ_PICK_RARE(SV_DUAL_W4_RARE, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 4, true>));
+    case SV_DUAL_W2_RARE:  FMJ_PICK_RARE(SV_DUAL_W2_RARE, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 2, true>));
+    case SV_DUAL_W3_RARE:  FMJ_PICK_RARE(SV_DUAL_W3_RARE, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 3, true>));
+    case SV_DUAL_W4:       FMJ_PICK(SV_DUAL_W4, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 4>), (fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 4>));
+    case SV_DUAL_W2:       FMJ_PICK(SV_DUAL_W2, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 2>), (fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 2>));
+    case SV_DUAL_W3:       FMJ_PICK(SV_DUAL_W3, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 3>), (fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 3>));
+    //                                                CONS  PAIRS  NEWTON MESH  ELL
+    case SV_PGS_ELL_PAIRS: FMJ_PICK_ONE(SV_PGS_ELL_PAIRS, true, true,  false, true, true);
+    case SV_PGS_ELL:       FMJ_PICK_ONE(SV_PGS_ELL,       true, false, false, true, true);
+    case SV_NEWTON_PAIRS:  FMJ_PICK_ONE(SV_NEWTON_PAIRS,  true, true,  true,  true);
+    case SV_NEWTON_ELL:    FMJ_PICK_ONE(SV_NEWTON_ELL,    true, false, true,  true, true);
+    case SV_NEWTON_MESH:   FMJ_PICK_ONE(SV_NEWTON_MESH,   true, false, true,  true);
+    case SV_PGS_MESH:      FMJ_PICK_ONE(SV_PGS_MESH,      true, false, false, true);
+    case SV_NEWTON:        FMJ_PICK_ONE(SV_NEWTON,        true, false, true);
+    case SV_PGS_PAIRS:     FMJ_PICK_ONE(SV_PGS_PAIRS,     true, true);
+    case SV_PGS:           FMJ_PICK_ONE(SV_PGS,           true);
+    case SV_PLAIN:         FMJ_PICK_ONE(SV_PLAIN,         false);
+  }
+  return nullptr;
 }
 #else
 
@@ -2247,91 +2266,68 @@ __global__ void __launch_bounds__(64) fmj_contacts2data_kernel(const DevModel M,
 // ---------------------------------------------------------------------------------------------
 // host side
 
+// one device allocation of a context, freed by fmj_destroy
+static hipError_t dev_alloc(fmj_ctx* c, size_t bytes, void** d) {
+  *d = nullptr;
+  const hipError_t e = hipMalloc(d, bytes);
+  if (e == hipSuccess) c->allocs.push_back(*d);
+  return e;
+}
+
 template <class T>
 static int upload(fmj_ctx* c, const std::vector<T>& h, const T** dptr) {
   void* d = nullptr;
-  size_t bytes = (h.size() ? h.size() : 1) * sizeof(T);
-  HIP_TRY(hipMalloc(&d, bytes));
-  c->allocs.push_back(d);
+  HIP_TRY(dev_alloc(c, (h.size() ? h.size() : 1) * sizeof(T), &d));
   if (h.size()) HIP_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
   *dptr = (const T*)d;
   return FMJ_OK;
 }
-#define UP(vec, field) do { int rc_ = upload(c, vec, &c->dm.field); if (rc_) { fmj_destroy(c); return rc_; } } while (0)
+#define UP(vec, field) do { if (int rc_ = upload(c, vec, &c->dm.field)) return rc_; } while (0)
 
 static float4 f4(double a, double b, double c, double d) { return make_float4((float)a, (float)b, (float)c, (float)d); }
 static float ibits(int i) { float f; memcpy(&f, &i, 4); return f; }
+static float4 i4f(int4 v) { return make_float4(ibits(v.x), ibits(v.y), ibits(v.z), ibits(v.w)); }
 
 // pick the instantiation whose register row length matches the model's dof-chain length
 typedef void (*step_kernel_t)(const DevModel, const StepArgs);
 extern "C" {
-void* fmj_tu_kernel_4(int, int, int);  void* fmj_tu_kernel_8(int, int, int);  void* fmj_tu_kernel_12(int, int, int); void* fmj_tu_kernel_16(int, int, int);
-void* fmj_tu_kernel_20(int, int, int); void* fmj_tu_kernel_24(int, int, int); void* fmj_tu_kernel_28(int, int, int); void* fmj_tu_kernel_32(int, int, int);
-void* fmj_tu_kernel_36(int, int, int); void* fmj_tu_kernel_40(int, int, int); void* fmj_tu_kernel_44(int, int, int); void* fmj_tu_kernel_48(int, int, int);
-void* fmj_tu_kernel_52(int, int, int); void* fmj_tu_kernel_56(int, int, int); void* fmj_tu_kernel_60(int, int, int); void* fmj_tu_kernel_64(int, int, int);
+void* fmj_tu_kernel_4(int, int);  void* fmj_tu_kernel_8(int, int);  void* fmj_tu_kernel_12(int, int); void* fmj_tu_kernel_16(int, int);
+void* fmj_tu_kernel_20(int, int); void* fmj_tu_kernel_24(int, int); void* fmj_tu_kernel_28(int, int); void* fmj_tu_kernel_32(int, int);
+void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu_kernel_44(int, int); void* fmj_tu_kernel_48(int, int);
+void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
+void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
 }
-static step_kernel_t tu_kernel(int rs, bool fused, int cons, int dual) {      // cons: 0 none, 1 limits / ground contacts, 2 + explicit pairs (and meshes), 3 Newton / CG solver, 4 + meshes only, 5 Newton / CG + meshes, 6 Newton / CG + elliptic cone (+ meshes), 7 Newton / CG + explicit pairs (+ meshes), 8 PGS + elliptic cone (+ meshes), 9 PGS + elliptic cone + explicit pairs
-  void* k;
-  switch (rs) {
-    case 4: k = fmj_tu_kernel_4(fused, cons, dual); break;
-    case 8: k = fmj_tu_kernel_8(fused, cons, dual); break;
-    case 12: k = fmj_tu_kernel_12(fused, cons, dual); break;
-    case 16: k = fmj_tu_kernel_16(fused, cons, dual); break;
-    case 20: k = fmj_tu_kernel_20(fused, cons, dual); break;
-    case 24: k = fmj_tu_kernel_24(fused, cons, dual); break;
-    case 28: k = fmj_tu_kernel_28(fused, cons, dual); break;
-    case 32: k = fmj_tu_kernel_32(fused, cons, dual); break;
-    case 36: k = fmj_tu_kernel_36(fused, cons, dual); break;
-    case 40: k = fmj_tu_kernel_40(fused, cons, dual); break;
-    case 44: k = fmj_tu_kernel_44(fused, cons, dual); break;
-    case 48: k = fmj_tu_kernel_48(fused, cons, dual); break;
-    case 52: k = fmj_tu_kernel_52(fused, cons, dual); break;
-    case 56: k = fmj_tu_kernel_56(fused, cons, dual); break;
-    case 60: k = fmj_tu_kernel_60(fused, cons, dual); break;
-    default: k = fmj_tu_kernel_64(fused, cons, dual); break;
-  }
-  return (step_kernel_t)k;
-}
-static step_kernel_t pick_kernel(const fmj_ctx* c, bool fused) {
-  const int cons = !c->dm.cons ? 0 : (c->dm.solver != FMJ_SOLVER_PGS ? (c->dm.cone == FMJ_CONE_ELLIPTIC ? 6 : (c->dm.npair > 0 ? 7 : (c->dm.any_mesh ? 5 : 3)))
-                                      : (c->dm.cone == FMJ_CONE_ELLIPTIC ? (c->dm.npair > 0 ? 9 : 8) : (c->dm.npair > 0 ? 2 : (c->dm.any_mesh ? 4 : 1))));
-  return tu_kernel(c->dm.rs, fused, cons, 0);
-}
-extern "C" { void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int); }
+static void* (*const tu_kernels[16])(int, int) = {
+  fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
+  fmj_tu_kernel_36, fmj_tu_kernel_40, fmj_tu_kernel_44, fmj_tu_kernel_48, fmj_tu_kernel_52, fmj_tu_kernel_56, fmj_tu_kernel_60, fmj_tu_kernel_64};
+static step_kernel_t step_kernel(int rs, bool fused, StepVariant v) { return (step_kernel_t)tu_kernels[rs / 4 - 1](fused, v); }
 static step_kernel_t wide_kernel(int rs, bool fused) { return (step_kernel_t)(rs <= 32 ? fmj_tu_wide_32(fused) : fmj_tu_wide_64(fused)); }
+
+static int launch(const char* what, step_kernel_t k, int blocks, int threads, size_t lds, void* stream, const DevModel& M, const StepArgs& A) {
+  hipLaunchKernelGGL(k, dim3(blocks), dim3(threads), lds, (hipStream_t)stream, M, A);
+  if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+  return FMJ_OK;
+}
+
 static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream) {
-  if (c->wide) {           // one workgroup of two waves per env (fmj_wide.inc): every launch of the context, fmj_forward included
-    hipLaunchKernelGGL(wide_kernel(c->dm.rs, fused), dim3(c->n_envs), dim3(128), c->lds_bytes_wide, (hipStream_t)stream, c->dm, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(FMJ_ERR_HIP, std::string("two-wave step kernel launch: ") + hipGetErrorString(e));
-    return FMJ_OK;
+  const DevModel& D = c->dm;
+  const int pairs = (c->n_envs + 1) / 2;
+  if (c->path == PATH_TWO_WAVE) return launch("two-wave step kernel", wide_kernel(D.rs, fused), c->n_envs, 128, c->lds_bytes_wide, stream, D, A);
+  if (c->path == PATH_TWO_ENV && A.integrate) {      // the build registered for the batch's waves per SIMD, or the one with the rare options
+    static const StepVariant dual[2][3] = {{SV_DUAL_W2, SV_DUAL_W3, SV_DUAL_W4}, {SV_DUAL_W2_RARE, SV_DUAL_W3_RARE, SV_DUAL_W4_RARE}};
+    const bool rare = (fused && A.substeps > 1) || D.implicitfast;
+    return launch("dual step kernel", step_kernel(D.rs, fused, dual[rare][c->dual_wps - 2]), pairs, 64, c->lds_bytes_dual2, stream, D, A);
   }
-  if (c->dm.dual_ok && A.integrate) {      // two envs per wave (fmj_dual2.inc); fmj_forward keeps the single-env kernel
-    step_kernel_t k = tu_kernel(c->dm.rs, fused, 0, (c->dual_wps == 2 ? 4 : (c->dual_wps == 3 ? 3 : 2)) + (((fused && A.substeps > 1) || c->dm.implicitfast) ? 16 : 0));      // + 16: the instantiation with the rare options (sub-steps, implicitfast)
-    hipLaunchKernelGGL(k, dim3((c->n_envs + 1) / 2), dim3(64), c->lds_bytes_dual2, (hipStream_t)stream, c->dm, A);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err(FMJ_ERR_HIP, std::string("dual step kernel launch: ") + hipGetErrorString(e));
-    return FMJ_OK;
-  }
-  if (c->dm.cons && (!A.qacc_warmstart || !A.contact || !A.ncon))
+  if (D.cons && (!A.qacc_warmstart || !A.contact || !A.ncon))
     return set_err(FMJ_ERR_ARG, "fmj_data: qacc_warmstart, contact and ncon are required for models with limits / contacts");
-  if (c->dm.cons2_ok && A.integrate && !(fused && A.do_drag)) {
-    // two envs per wave (fmj_cons2.inc), then the one-env kernel for whatever that kernel handed over (resume[env] < n_steps: an
-    // env with more rows than a wave holds on chip); envs it completed cost the second launch one early exit each
+  if (c->path == PATH_CONS2_ONE_ENV && A.integrate && !(fused && A.do_drag)) {
+    // envs the two-env constraint kernel completed cost the second launch one early exit each (resume[env] = n_steps)
     StepArgs A2 = A;
     A2.resume = c->d_resume;
-    hipLaunchKernelGGL(tu_kernel(c->dm.rs, fused, 0, 5), dim3((c->n_envs + 1) / 2), dim3(64), c->lds_bytes_cons2, (hipStream_t)stream, c->dm, A2);
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) return set_err(FMJ_ERR_HIP, std::string("two-env constraint kernel launch: ") + hipGetErrorString(e2));
-    hipLaunchKernelGGL(pick_kernel(c, fused), dim3(c->n_envs), dim3(64), c->lds_bytes, (hipStream_t)stream, c->dm, A2);
-    e2 = hipGetLastError();
-    if (e2 != hipSuccess) return set_err(FMJ_ERR_HIP, std::string("step kernel launch: ") + hipGetErrorString(e2));
-    return FMJ_OK;
+    if (int rc = launch("two-env constraint kernel", step_kernel(D.rs, fused, SV_CONS2), pairs, 64, c->lds_bytes_cons2, stream, D, A2)) return rc;
+    return launch("step kernel", step_kernel(D.rs, fused, c->variant), c->n_envs, 64, c->lds_bytes, stream, D, A2);
   }
-  hipLaunchKernelGGL(pick_kernel(c, fused), dim3(c->n_envs), dim3(64), c->lds_bytes, (hipStream_t)stream, c->dm, A);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_err(FMJ_ERR_HIP, std::string("step kernel launch: ") + hipGetErrorString(e));
-  return FMJ_OK;
+  return launch("step kernel", step_kernel(D.rs, fused, c->variant), c->n_envs, 64, c->lds_bytes, stream, D, A);
 }
 
 // device copies of the row -> body / dof maps used by fmj_physics2data (rebuilt from the host mirrors; tiny)
@@ -2355,26 +2351,24 @@ static int sync_tables(fmj_ctx* c) {
   return FMJ_OK;
 }
 
-extern "C" {
+// ---- fmj_create, stage 1: every check of the model (host only, before any device call) and the facts the later stages build on
+struct ModelFacts {
+  int cons = 0, big = 0;      // limits, contacts or pairs (the constraint kernels); nbody or nv above 64 (past one wavefront)
+  int wide = 0;               // every step launch runs the two-wave kernel (fmj_wide.inc): big, or FMJ_WIDE=1
+  int nplane = 0, n_hfield = 0, any_mesh = 0, any_box = 0, any_polypair = 0;     // nplane counts the ground geoms: planes and the heightfield
+  bool dual_instead = false;  // Newton / CG requested, solved on the dual problem (PGS)
+  std::vector<int> bdepth, subsize, ddepth, dsub;      // body / dof depth and subtree size
+  int max_bdepth = 0, max_sub = 0, max_ddepth = 0;     // longest root->body chain (bodies), largest subtree, deepest dof
+  int jump_rounds = 0, anc_stride = 0, rs = 0;         // pointer-jumping rounds, bytes per chain row of b_anc, register row length
+  int max_contacts = 0, maxefc = 0;
+};
 
-const char* fmj_last_error(void) { return g_err.c_str(); }
-int fmj_abi_version(void) { return FMJ_ABI_VERSION; }
-
-void fmj_destroy(fmj_ctx* c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  for (void* p : c->allocs) (void)hipFree(p);
-  delete c;
-}
-
-int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out) {
-  if (!m || !out || n_envs <= 0) return set_err(FMJ_ERR_ARG, "fmj_create: NULL model/out or n_envs <= 0");
-  *out = nullptr;
+static int check_model(const fmj_model* m, ModelFacts* F) {
   if (m->abi_version != FMJ_ABI_VERSION) return set_err(FMJ_ERR_ARG, "fmj_create: abi_version mismatch");
   const int nb = m->nbody, nv = m->nv, nq = m->nq, nu = m->nu, nj = m->njnt;
   if (nb < 2 || nb > 128 || nv < 1 || nv > 128) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: need 2 <= nbody <= 128 and 1 <= nv <= 128 (two wavefronts per environment at most)");
   const bool big = nb > 64 || nv > 64;      // past one wavefront: the two-wave kernel (fmj_wide.inc), unconstrained models only
-  int any_limit = 0, nplane = 0, any_box = 0, n_hfield = 0, any_mesh = 0, any_polypair = 0;     // nplane counts the ground geoms: planes and the heightfield
+  int any_limit = 0; int& nplane = F->nplane; int& n_hfield = F->n_hfield;
   for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) any_limit = 1;
   for (int g = 0; g < m->ngeom; g++) {
     int t = m->geom_type[g];
@@ -2391,11 +2385,11 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
       if (m->geom_vertnum[g] < 1 || m->geom_vertadr[g] < 0 || m->geom_vertadr[g] + m->geom_vertnum[g] > m->nmeshvert)
         return set_err(FMJ_ERR_ARG, "fmj_create: mesh vertex range out of bounds");
       if (m->geom_bodyid[g] < 1 || m->geom_bodyid[g] >= nb) return set_err(FMJ_ERR_ARG, "fmj_create: geom_bodyid out of range");
-      any_mesh = 1;
+      F->any_mesh = 1;
     }
     else if (t != FMJ_GEOM_SPHERE && t != FMJ_GEOM_CAPSULE && t != FMJ_GEOM_BOX && t != FMJ_GEOM_CYLINDER) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: only plane / heightfield / sphere / capsule / cylinder / box / convex mesh geoms are in the HIP path");
     else if (m->geom_bodyid[g] < 1 || m->geom_bodyid[g] >= nb) return set_err(FMJ_ERR_ARG, "fmj_create: geom_bodyid out of range");
-    if (t == FMJ_GEOM_BOX || t == FMJ_GEOM_CYLINDER) any_box = 1;      // geoms with up to 4 contacts
+    if (t == FMJ_GEOM_BOX || t == FMJ_GEOM_CYLINDER) F->any_box = 1;      // geoms with up to 4 contacts
   }
   if (m->npair < 0 || (m->npair > 0 && (!m->pair_geom1 || !m->pair_geom2 || !m->pair_friction || !m->pair_solref || !m->pair_solimp)))
     return set_err(FMJ_ERR_ARG, "fmj_create: pair arrays missing");
@@ -2407,7 +2401,7 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
     for (int k = 0; k < 2; k++) {
       const int tt = k ? t2 : t1, gg = k ? g2 : g1;
       if (tt == FMJ_GEOM_PLANE || tt == FMJ_GEOM_HFIELD) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: explicit contact pairs join two animat geoms (sphere / capsule / box / cylinder / convex mesh); the ground meets every geom already");
-      if (tt == FMJ_GEOM_BOX || tt == FMJ_GEOM_CYLINDER || tt == FMJ_GEOM_MESH) any_polypair = 1;
+      if (tt == FMJ_GEOM_BOX || tt == FMJ_GEOM_CYLINDER || tt == FMJ_GEOM_MESH) F->any_polypair = 1;
       if (tt == FMJ_GEOM_MESH && (m->nmeshface < 4 || !m->mesh_face || !m->geom_faceadr || !m->geom_facenum || m->geom_facenum[gg] < 4 ||
                                   m->geom_faceadr[gg] < 0 || m->geom_faceadr[gg] + m->geom_facenum[gg] > m->nmeshface))
         return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: an explicit pair with a mesh geom needs the planes of its convex hull (mesh_face / geom_faceadr / geom_facenum, at least 4: a flat or collinear vertex cloud has no hull)");
@@ -2422,7 +2416,7 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   // its link's - 1e-5 after MuJoCo's clamp when the link has none) a contact force is a residual too small for an fp32 primal
   // iteration (see fmj_cons_rows.inc on the friction-0 pairs).  Such a model is solved on the dual problem throughout: the PGS
   // kernels, run to the solver's tolerance (up to 10 x solver_iterations sweeps) - the same convex problem, the same minimiser.
-  bool dual_instead = false;
+  bool& dual_instead = F->dual_instead;
   if (cons && m->solver != FMJ_SOLVER_PGS && m->cone == FMJ_CONE_PYRAMIDAL && nplane > 0) {
     double gmu = 0;
     const double isq = 1.0 / sqrt(m->impratio > 0 ? m->impratio : 1.0);      // the rule uses mu = friction / sqrt(impratio)
@@ -2451,7 +2445,7 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
     bdepth[i] = bdepth[p] + 1;
   }
   for (int i = nb - 1; i >= 2; i--) subsize[m->body_parentid[i]] += subsize[i];
-  int max_bdepth = 0, max_sub = 0;
+  int& max_bdepth = F->max_bdepth; int& max_sub = F->max_sub;
   for (int i = 1; i < nb; i++) { if (bdepth[i] + 1 > max_bdepth) max_bdepth = bdepth[i] + 1; if (subsize[i] > max_sub) max_sub = subsize[i]; }
   if (max_bdepth > 255) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: body chain too long");
   int expect_dof = 0, expect_q = 0;
@@ -2469,7 +2463,7 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
   }
   if (expect_dof != nv || expect_q != nq) return set_err(FMJ_ERR_ARG, "fmj_create: nv/nq do not match the joints");
   std::vector<int> ddepth(nv, 0), dsub(nv, 1);
-  int max_ddepth = 0;
+  int& max_ddepth = F->max_ddepth;
   for (int d = 0; d < nv; d++) {
     int p = m->dof_parentid[d];
     if (p >= d) return set_err(FMJ_ERR_ARG, "fmj_create: dof_parentid must precede the dof");
@@ -2486,51 +2480,106 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
     if (j < 0 || j >= nj || m->jnt_type[j] == FMJ_JNT_FREE) return set_err(FMJ_ERR_ARG, "fmj_create: actuator must act on a hinge/slide joint");
     if (++nact[j] > 4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: more than 4 actuators on one joint");
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_err(FMJ_ERR_NODEVICE, "fmj_create: no HIP device visible");
-  if (device < 0 || device >= ndev) return set_err(FMJ_ERR_ARG, "fmj_create: bad device ordinal");
-  HIP_TRY(hipSetDevice(device));
-
-  fmj_ctx* c = new fmj_ctx();
-  c->solver_requested = cons ? m->solver : FMJ_SOLVER_PGS;
-  c->device = device; c->n_envs = n_envs; c->nbody = nb; c->nv = nv; c->nu = nu; c->njnt = nj;
-  c->d_btab = nullptr; c->d_dtab = nullptr; c->d_links_body = nullptr; c->d_joints_dof = nullptr;
-  DevModel& D = c->dm;
-  memset(&D, 0, sizeof D);
-  D.nbody = nb; D.nv = nv; D.nq = nq; D.nu = nu; D.njnt = nj; D.nM = m->nM;
-  { int rounds = 0; while ((1 << rounds) < max_bdepth) rounds++; D.max_bdepth = rounds; }   // pointer-jumping rounds
-  D.max_subsize = max_sub;
-  D.rs = r4(max_ddepth + 1);
-  {   // FMJ_WIDE=1: the two-wave kernel on any unconstrained model (tests hold it against the one-wave kernel; scripts measure the second wave)
-    const char* wenv = getenv("FMJ_WIDE");
-    c->wide = big || (!cons && m->integrator != FMJ_INT_RK4 && wenv && wenv[0] == '1');
-    if (c->wide) D.rs = D.rs <= 32 ? 32 : 64;     // the row lengths the two-wave kernel is instantiated at
+  // the caller's sparse layout of M (mjModel dof_Madr / nM) must describe the same tree
+  int e = 0;
+  for (int i = 0; i < nv; i++) {
+    if (m->dof_Madr[i] != e) return set_err(FMJ_ERR_ARG, "fmj_create: dof_Madr inconsistent");
+    for (int j = i; j >= 0; j = m->dof_parentid[j]) e++;
   }
+  if (e != m->nM) return set_err(FMJ_ERR_ARG, "fmj_create: nM inconsistent");
+  F->cons = cons; F->big = big; F->bdepth = bdepth; F->subsize = subsize; F->ddepth = ddepth; F->dsub = dsub;
+  while ((1 << F->jump_rounds) < max_bdepth) F->jump_rounds++;
+  F->anc_stride = r4(F->jump_rounds > 4 ? F->jump_rounds : 4);
+  F->rs = r4(max_ddepth + 1);
+  // FMJ_WIDE=1: the two-wave kernel on any unconstrained model (tests hold it against the one-wave kernel; scripts measure the second wave)
+  const char* wenv = getenv("FMJ_WIDE");
+  F->wide = big || (!cons && m->integrator != FMJ_INT_RK4 && wenv && wenv[0] == '1');
+  if (F->wide) F->rs = F->rs <= 32 ? 32 : 64;     // the row lengths the two-wave kernel is instantiated at
+  F->max_contacts = cons ? (m->max_contacts > 0 ? m->max_contacts : 1) : 0;
+  int nlimj = 0; for (int j = 0; j < nj; j++) nlimj += (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE);
+  F->maxefc = cons ? nlimj + 4 * F->max_contacts : 0;
+  // the HBM constraint path keeps A in rows of AG_LD floats and three 64-row slots per lane (fmj_cons_rows.inc)
+  if (F->maxefc > AG_LD) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: more than 192 constraint rows possible (limited joints + 4 * max_contacts): lower max_contacts");
+  // the block solvers (elliptic PGS, noslip) keep forces, b, R and mu of every row in the LDS staging area of the row code: min(maxefc, 64) * rs floats
+  if (cons && (m->noslip_iterations > 0 || (m->cone == FMJ_CONE_ELLIPTIC && (m->solver == FMJ_SOLVER_PGS || dual_instead))) && std::min(F->maxefc, FMJ_NA) * F->rs < 4 * F->maxefc)
+    return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: PGS with the elliptic cone / noslip: too many constraint rows for this model's row length (needs min(maxefc, 64) * rs >= 4 * maxefc): lower max_contacts");
+  if (F->wide && (size_t)ldsw_layout(nb, nv, nq, F->rs, F->anc_stride).total * sizeof(float) > 64 * 1024)
+    return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: two-wave kernel LDS above 64 KB");     // (cannot happen within the size limits above)
+  return FMJ_OK;
+}
+
+// ---- stage 2: the model constants of DevModel, the sensor layout, and which two-env kernels the model is eligible for
+static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  const int nb = m->nbody, nv = m->nv, nj = m->njnt;
+  DevModel& D = c->dm;
+  c->solver_requested = F.cons ? m->solver : FMJ_SOLVER_PGS;
+  c->nbody = nb; c->nv = nv; c->nu = m->nu; c->njnt = nj;
+  c->rk4 = m->integrator == FMJ_INT_RK4;
+  D.nbody = nb; D.nv = nv; D.nq = m->nq; D.nu = m->nu; D.njnt = nj; D.nM = m->nM;
+  D.max_bdepth = F.jump_rounds;       // pointer-jumping rounds
+  D.max_subsize = F.max_sub;
+  D.rs = F.rs;
   D.root_free = m->body_jntadr[1] >= 0 && m->jnt_type[m->body_jntadr[1]] == FMJ_JNT_FREE;
   D.h = (float)m->timestep; D.gx = (float)m->gravity[0]; D.gy = (float)m->gravity[1]; D.gz = (float)m->gravity[2];
   double mtot = 0; for (int i = 1; i < nb; i++) mtot += m->body_mass[i];
   D.mtot_inv = (float)(1.0 / mtot);
-  D.anc_stride = r4(D.max_bdepth > 4 ? D.max_bdepth : 4);
+  D.anc_stride = F.anc_stride;
   int njs = 0; for (int j = 0; j < nj; j++) njs += m->jnt_type[j] != FMJ_JNT_FREE;
-  D.njs = njs; D.nsensordata = 6 * (nb - 1) + 3 * njs + nu;
+  D.njs = njs; D.nsensordata = 6 * (nb - 1) + 3 * njs + m->nu;
   c->layout.nsensordata = D.nsensordata; c->layout.framelinvel_adr = 0; c->layout.jointpos_adr = 6 * (nb - 1);
-  c->layout.actuatorfrc_adr = 6 * (nb - 1) + 3 * njs; c->layout.first_link_body = 1;
-  c->layout.first_sensor_jnt = D.root_free ? 1 : 0;
+  c->layout.actuatorfrc_adr = 6 * (nb - 1) + 3 * njs; c->layout.first_link_body = 1; c->layout.first_sensor_jnt = D.root_free ? 1 : 0;
+  D.any_box = F.any_box;
+  for (int i = 1; i < nb; i++) {
+    const int j = m->body_jntadr[i];
+    if (j >= 0 && m->jnt_type[j] != FMJ_JNT_FREE && (m->jnt_pos[3 * j] != 0 || m->jnt_pos[3 * j + 1] != 0 || m->jnt_pos[3 * j + 2] != 0)) D.any_jpos = 1;
+    const bool freeb = j >= 0 && m->jnt_type[j] == FMJ_JNT_FREE;
+    if (!freeb && !(fabs(m->body_quat[4 * i]) == 1.0 && m->body_quat[4 * i + 1] == 0 && m->body_quat[4 * i + 2] == 0 && m->body_quat[4 * i + 3] == 0)) D.any_bquat = 1;
+    if (!(m->body_iquat[4 * i] == 1.0 && m->body_iquat[4 * i + 1] == 0 && m->body_iquat[4 * i + 2] == 0 && m->body_iquat[4 * i + 3] == 0)) D.any_iquat = 1;
+  }
+  D.n_links = nb - 1; D.n_joints = njs; D.n_xfrc = nb - 1; D.ns = 0;
+  // ---- constraint path
+  const int cons = F.cons;
+  D.cons = cons; D.ngeom = m->ngeom; D.nplane = F.nplane; D.nvs = nv | 1;
+  D.max_contacts = F.max_contacts; D.maxefc = F.maxefc;
+  D.implicitfast = m->integrator == FMJ_INT_IMPLICITFAST;
+  D.hdamp = m->integrator == FMJ_INT_RK4 ? 0.0f : (float)m->timestep;
+  D.solver_iterations = F.dual_instead ? 10 * m->solver_iterations : m->solver_iterations; D.solver_tolerance = (float)m->solver_tolerance;
+  D.cone = cons ? m->cone : FMJ_CONE_PYRAMIDAL;
+  D.noslip_iterations = cons ? m->noslip_iterations : 0; D.noslip_tolerance = (float)m->noslip_tolerance;
+  D.solver = (cons && !F.dual_instead) ? m->solver : FMJ_SOLVER_PGS; D.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
+  D.ls_tolerance = (float)(m->ls_tolerance > 0 ? m->ls_tolerance : 0.01);
+  D.impratio_isqrt = (float)(1.0 / sqrt(m->impratio > 0 ? m->impratio : 1.0));
+  D.pgs_scale = (float)(1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1)));
+  D.npair = cons ? m->npair : 0;
+  D.any_polypair = cons ? F.any_polypair : 0;
+  D.any_mesh = cons ? F.any_mesh : 0;
+  D.maxdep1 = F.max_ddepth;
+  // ---- two envs per wave: bodies and the dofs minus a free root's translational dofs must fit 32 lanes, and a row 32 floats
+  const int t0 = D.root_free ? 3 : 0;
+  const char* envv = getenv("FMJ_DUAL");
+  D.dual_t0 = t0;
+  const bool halves_ok = nb <= 32 && nv - t0 <= 32 && D.rs <= FMJ_MAXD && !(envv && envv[0] == '0');
+  D.dual_ok = !cons && halves_ok && !c->rk4 && !F.wide;      // RK4: four forward launches of the one-env kernel per step, no fused launch
+  // the two-env constraint kernel covers what BASELINE configs[3] needs: limits + ground contacts of sphere / capsule / box / cylinder
+  // geoms on ONE ground geom, pyramidal cone, PGS; everything else (pairs, meshes, Newton / CG, the elliptic cone) keeps the one-env kernel
+  D.cons2_ok = cons && halves_ok && !c->rk4 && m->solver == FMJ_SOLVER_PGS && !F.dual_instead && m->cone == FMJ_CONE_PYRAMIDAL && m->noslip_iterations == 0 &&
+               m->npair == 0 && !F.any_mesh && F.nplane <= 1 && m->ngeom <= 32;
+  for (int t = 0; t < 3; t++) D.dual_tadd[t] = t < t0 ? (float)(mtot + m->dof_armature[t] + m->timestep * m->dof_damping[t]) : 1.0f;
+  for (int t = 0; t < 3; t++) D.dual_taddm[t] = t < t0 ? (float)(mtot + m->dof_armature[t]) : 1.0f;
+}
 
+// ---- stage 3: the per-body / per-dof / per-actuator tables, the pointer-jumping table and the shared-chain depths
+static int pack_body_dof_tables(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  const int nb = m->nbody, nv = m->nv, nu = m->nu, nj = m->njnt;
+  DevModel& D = c->dm;
   constexpr int NT = FMJ_TAB_ROWS;
-  std::vector<float4> b_pos_mass(NT), b_quat(NT), b_ipos(NT), b_iquat(NT), b_inertia(NT), j_axis_q0(NT), j_pos_k(NT);
-  std::vector<int4> b_info(NT), b_info2(NT), d_info(NT), d_act(NT);
-  std::vector<float4> d_prm(NT);
+  const float4 zero = f4(0, 0, 0, 0), unit = f4(1, 0, 0, 0);
+  std::vector<float4> b_pos_mass(NT, zero), b_quat(NT, unit), b_ipos(NT, zero), b_iquat(NT, unit), b_inertia(NT, zero), j_axis_q0(NT, f4(0, 0, 1, 0)), j_pos_k(NT, zero);
+  std::vector<int4> b_info(NT, make_int4(0, -1, 0, 0)), b_info2(NT, make_int4(-1, 0, -1, -1)), d_info(NT, make_int4(0, 0, 0, -1)), d_act(NT, make_int4(0, 0, 0, 0));
+  std::vector<float4> d_prm(NT, zero);
   std::vector<uint8_t> b_anc((size_t)r4(nb * D.anc_stride), 0);
   c->body_link_row.assign(nb, -1); c->dof_joint_row.assign(nv, -1); c->body_swim.assign(nb, -1);
   c->jnt_dofadr.assign(m->jnt_dofadr, m->jnt_dofadr + nj); c->jnt_type.assign(m->jnt_type, m->jnt_type + nj);
-  int any_k = 0;
-  for (int i = 0; i < NT; i++) {
-    b_pos_mass[i] = f4(0, 0, 0, 0); b_quat[i] = f4(1, 0, 0, 0); b_ipos[i] = f4(0, 0, 0, 0); b_iquat[i] = f4(1, 0, 0, 0);
-    b_inertia[i] = f4(0, 0, 0, 0); j_axis_q0[i] = f4(0, 0, 1, 0); j_pos_k[i] = f4(0, 0, 0, 0);
-    b_info[i] = make_int4(0, -1, 0, 0); b_info2[i] = make_int4(-1, 0, -1, -1);
-    d_info[i] = make_int4(0, 0, 0, -1); d_prm[i] = f4(0, 0, 0, 0); d_act[i] = make_int4(0, 0, 0, 0);
-  }
   for (int i = 1; i < nb; i++) {
     b_pos_mass[i] = f4(m->body_pos[3 * i], m->body_pos[3 * i + 1], m->body_pos[3 * i + 2], m->body_mass[i]);
     b_quat[i] = f4(m->body_quat[4 * i], m->body_quat[4 * i + 1], m->body_quat[4 * i + 2], m->body_quat[4 * i + 3]);
@@ -2542,40 +2591,34 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
       double q0 = m->jnt_type[j] == FMJ_JNT_FREE ? 0.0 : m->qpos0[m->jnt_qposadr[j]];
       j_axis_q0[i] = f4(m->jnt_axis[3 * j], m->jnt_axis[3 * j + 1], m->jnt_axis[3 * j + 2], q0);
       j_pos_k[i] = f4(m->jnt_pos[3 * j], m->jnt_pos[3 * j + 1], m->jnt_pos[3 * j + 2], m->jnt_stiffness[j]);
-      if (m->jnt_type[j] != FMJ_JNT_FREE && m->jnt_stiffness[j] != 0) any_k = 1;
+      if (m->jnt_type[j] != FMJ_JNT_FREE && m->jnt_stiffness[j] != 0) D.any_stiffness = 1;
       b_info[i] = make_int4(m->body_parentid[i], m->jnt_type[j], m->jnt_qposadr[j], m->jnt_dofadr[j]);
     } else b_info[i] = make_int4(m->body_parentid[i], -1, 0, 0);
     c->body_link_row[i] = i - 1;
-    b_info2[i] = make_int4(bdepth[i], subsize[i], i - 1, -1);
-    {   // pointer-jumping table: ancestor at distance 2^r (0 = world, which holds the identity)
-      for (int r = 0; r < D.max_bdepth; r++) {
-        int a = i, hops = 1 << r;
-        while (hops-- > 0 && a > 0) a = m->body_parentid[a];
-        b_anc[(size_t)i * D.anc_stride + r] = (uint8_t)a;
-      }
+    b_info2[i] = make_int4(F.bdepth[i], F.subsize[i], i - 1, -1);
+    for (int r = 0; r < D.max_bdepth; r++) {      // pointer-jumping table: ancestor at distance 2^r (0 = world, which holds the identity)
+      int a = i, hops = 1 << r;
+      while (hops-- > 0 && a > 0) a = m->body_parentid[a];
+      b_anc[(size_t)i * D.anc_stride + r] = (uint8_t)a;
     }
   }
-  D.any_stiffness = any_k; D.any_box = any_box;
-  D.any_jpos = D.any_bquat = D.any_iquat = 0;
-  for (int i = 1; i < nb; i++) {
-    const int j = m->body_jntadr[i];
-    if (j >= 0 && m->jnt_type[j] != FMJ_JNT_FREE && (m->jnt_pos[3 * j] != 0 || m->jnt_pos[3 * j + 1] != 0 || m->jnt_pos[3 * j + 2] != 0)) D.any_jpos = 1;
-    const bool freeb = j >= 0 && m->jnt_type[j] == FMJ_JNT_FREE;
-    if (!freeb && !(fabs(m->body_quat[4 * i]) == 1.0 && m->body_quat[4 * i + 1] == 0 && m->body_quat[4 * i + 2] == 0 && m->body_quat[4 * i + 3] == 0)) D.any_bquat = 1;
-    if (!(m->body_iquat[4 * i] == 1.0 && m->body_iquat[4 * i + 1] == 0 && m->body_iquat[4 * i + 2] == 0 && m->body_iquat[4 * i + 3] == 0)) D.any_iquat = 1;
+  {   // subtree mass (a model constant) rides in ipos.w
+    std::vector<double> smass(nb, 0.0);
+    for (int i = 1; i < nb; i++) smass[i] = m->body_mass[i];
+    for (int i = nb - 1; i >= 2; i--) smass[m->body_parentid[i]] += smass[i];
+    for (int i = 1; i < nb; i++) b_ipos[i].w = (float)smass[i];
   }
-  D.n_links = nb - 1; D.n_joints = njs; D.n_xfrc = nb - 1; D.ns = 0;
   // actuators sorted by dof
   std::vector<float4> a_prm, a_lim; std::vector<int> a_src;
   int sj = 0;
   for (int j = 0; j < nj; j++) {
     int d0 = m->jnt_dofadr[j];
     if (m->jnt_type[j] == FMJ_JNT_FREE) {
-      for (int k = 0; k < 6; k++) { d_info[d0 + k] = make_int4(m->jnt_bodyid[j], ddepth[d0 + k], dsub[d0 + k], -1);
+      for (int k = 0; k < 6; k++) { d_info[d0 + k] = make_int4(m->jnt_bodyid[j], F.ddepth[d0 + k], F.dsub[d0 + k], -1);
         d_prm[d0 + k] = f4(m->dof_armature[d0 + k], m->dof_damping[d0 + k], 0, 0); d_act[d0 + k] = make_int4(0, 0, 0, 0); }
       continue;
     }
-    d_info[d0] = make_int4(m->jnt_bodyid[j], ddepth[d0], dsub[d0], sj);
+    d_info[d0] = make_int4(m->jnt_bodyid[j], F.ddepth[d0], F.dsub[d0], sj);
     c->dof_joint_row[d0] = sj;
     d_prm[d0] = make_float4((float)m->dof_armature[d0], (float)m->dof_damping[d0], ibits(m->jnt_qposadr[j]), 1.0f);
     int first = (int)a_src.size(), cnt = 0;
@@ -2588,61 +2631,55 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
     d_act[d0] = make_int4(first, cnt, sj, 0);
     sj++;
   }
-  // the caller's sparse layout of M (mjModel dof_Madr / nM) must describe the same tree
-  int e = 0;
-  for (int i = 0; i < nv; i++) {
-    if (m->dof_Madr[i] != e) { fmj_destroy(c); return set_err(FMJ_ERR_ARG, "fmj_create: dof_Madr inconsistent"); }
-    for (int j = i; j >= 0; j = m->dof_parentid[j]) e++;
-  }
-  if (e != m->nM) { fmj_destroy(c); return set_err(FMJ_ERR_ARG, "fmj_create: nM inconsistent"); }
+  // joint limits of the constraint path
+  std::vector<float4> d_lim(NT, f4(0, 0, 0, 0)), d_sol0(NT, f4(0.02, 1, 0.9, 0.95)), d_sol1(NT, f4(0.001, 0.5, 2, 0));
+  if (F.cons)
+    for (int j = 0; j < nj; j++) {
+      if (m->jnt_type[j] == FMJ_JNT_FREE) continue;
+      int d = m->jnt_dofadr[j];
+      d_lim[d] = f4(m->jnt_limited[j] ? 1 : 0, m->jnt_range[2 * j], m->jnt_range[2 * j + 1], m->jnt_margin[j]);
+      d_sol0[d] = f4(m->jnt_solref[2 * j], m->jnt_solref[2 * j + 1], m->jnt_solimp[5 * j], m->jnt_solimp[5 * j + 1]);
+      d_sol1[d] = f4(m->jnt_solimp[5 * j + 2], m->jnt_solimp[5 * j + 3], m->jnt_solimp[5 * j + 4], m->dof_invweight0[d]);
+    }
   c->h_b_info2.assign((int*)b_info2.data(), (int*)b_info2.data() + NT * 4);
   c->h_d_info.assign((int*)d_info.data(), (int*)d_info.data() + NT * 4);
-
-  {   // subtree mass (a model constant) rides in ipos.w
-    std::vector<double> smass(nb, 0.0);
-    for (int i = 1; i < nb; i++) smass[i] = m->body_mass[i];
-    for (int i = nb - 1; i >= 2; i--) smass[m->body_parentid[i]] += smass[i];
-    for (int i = 1; i < nb; i++) b_ipos[i].w = (float)smass[i];
+  // ---- pack the tables (one device array per family)
+  c->h_btab.assign(NT * BT_STRIDE, f4(0, 0, 0, 0)); c->h_dtab.assign(NT * DT_STRIDE, f4(0, 0, 0, 0));
+  for (int b = 0; b < NT; b++) {
+    float4* t = &c->h_btab[b * BT_STRIDE];
+    t[0] = b_pos_mass[b]; t[1] = b_quat[b]; t[2] = b_ipos[b]; t[3] = b_iquat[b]; t[4] = b_inertia[b]; t[5] = j_axis_q0[b]; t[6] = j_pos_k[b];
+    t[7] = i4f(b_info[b]); t[8] = i4f(b_info2[b]);
   }
+  for (int d = 0; d < NT; d++) {
+    float4* t = &c->h_dtab[d * DT_STRIDE];
+    int4 act = d_act[d]; act.w = d < nv ? m->dof_parentid[d] : -1;
+    t[0] = i4f(d_info[d]); t[1] = d_prm[d]; t[2] = i4f(act); t[3] = d_lim[d]; t[4] = d_sol0[d]; t[5] = d_sol1[d];
+  }
+  std::vector<float4> atab((a_src.size() ? a_src.size() : 1) * AT_STRIDE, f4(0, 0, 0, 0));
+  for (size_t a = 0; a < a_src.size(); a++) { atab[a * AT_STRIDE] = a_prm[a]; atab[a * AT_STRIDE + 1] = a_lim[a]; atab[a * AT_STRIDE + 2] = make_float4(ibits(a_src[a]), 0.f, 0.f, 0.f); }
+  c->h_atab = atab; c->a_src = a_src;
+  UP(c->h_btab, btab); UP(c->h_dtab, dtab); UP(atab, atab);
+  c->d_btab = (float4*)D.btab; c->d_dtab = (float4*)D.dtab;
   UP(b_anc, b_anc);
-  {   // depth of the deepest dof shared by the root chains of two dofs (constraint rows couple only through it)
-    std::vector<int8_t> lcad((size_t)r4(nv * nv), (int8_t)-1);
-    for (int a = 0; a < nv; a++)
-      for (int b = 0; b < nv; b++) {
-        int x = a, y = b;
-        while (x >= 0 && y >= 0 && x != y) { if (ddepth[x] > ddepth[y]) x = m->dof_parentid[x]; else if (ddepth[y] > ddepth[x]) y = m->dof_parentid[y]; else { x = m->dof_parentid[x]; y = m->dof_parentid[y]; } }
-        lcad[(size_t)a * nv + b] = (x >= 0 && x == y) ? (int8_t)ddepth[x] : (int8_t)-1;
-      }
-    UP(lcad, lcad);
-  }
-  // ---- constraint tables
-  D.cons = cons; D.ngeom = m->ngeom; D.nplane = nplane; D.nvs = nv | 1;
-  D.max_contacts = cons ? (m->max_contacts > 0 ? m->max_contacts : 1) : 0;
-  {
-    int nlimj = 0; for (int j = 0; j < nj; j++) nlimj += (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE);
-    D.maxefc = cons ? nlimj + 4 * D.max_contacts : 0;
-    // the HBM constraint path keeps A in rows of AG_LD floats and three 64-row slots per lane (fmj_cons_rows.inc)
-    if (D.maxefc > AG_LD) { fmj_destroy(c); return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: more than 192 constraint rows possible (limited joints + 4 * max_contacts): lower max_contacts"); }
-    // the block solvers (elliptic PGS, noslip) keep forces, b, R and mu of every row in the LDS staging area of the row code: min(maxefc, 64) * rs floats
-    if (cons && (m->noslip_iterations > 0 || (m->cone == FMJ_CONE_ELLIPTIC && (m->solver == FMJ_SOLVER_PGS || dual_instead))) && std::min(D.maxefc, FMJ_NA) * D.rs < 4 * D.maxefc) {
-      fmj_destroy(c); return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: PGS with the elliptic cone / noslip: too many constraint rows for this model's row length (needs min(maxefc, 64) * rs >= 4 * maxefc): lower max_contacts");
+  // depth of the deepest dof shared by the root chains of two dofs (constraint rows couple only through it)
+  std::vector<int8_t> lcad((size_t)r4(nv * nv), (int8_t)-1);
+  for (int a = 0; a < nv; a++)
+    for (int b = 0; b < nv; b++) {
+      int x = a, y = b;
+      while (x >= 0 && y >= 0 && x != y) { if (F.ddepth[x] > F.ddepth[y]) x = m->dof_parentid[x]; else if (F.ddepth[y] > F.ddepth[x]) y = m->dof_parentid[y]; else { x = m->dof_parentid[x]; y = m->dof_parentid[y]; } }
+      lcad[(size_t)a * nv + b] = (x >= 0 && x == y) ? (int8_t)F.ddepth[x] : (int8_t)-1;
     }
-  }
-  D.implicitfast = m->integrator == FMJ_INT_IMPLICITFAST;
-  D.hdamp = m->integrator == FMJ_INT_RK4 ? 0.0f : (float)m->timestep;
-  D.solver_iterations = dual_instead ? 10 * m->solver_iterations : m->solver_iterations; D.solver_tolerance = (float)m->solver_tolerance;
-  D.cone = cons ? m->cone : FMJ_CONE_PYRAMIDAL;
-  D.noslip_iterations = cons ? m->noslip_iterations : 0; D.noslip_tolerance = (float)m->noslip_tolerance;
-  D.solver = (cons && !dual_instead) ? m->solver : FMJ_SOLVER_PGS; D.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
-  D.ls_tolerance = (float)(m->ls_tolerance > 0 ? m->ls_tolerance : 0.01);
-  D.impratio_isqrt = (float)(1.0 / sqrt(m->impratio > 0 ? m->impratio : 1.0));
-  D.pgs_scale = (float)(1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1)));
-  std::vector<int> d_parent(NT, -1);
-  for (int d = 0; d < nv; d++) d_parent[d] = m->dof_parentid[d];
+  UP(lcad, lcad);
+  return FMJ_OK;
+}
+
+// ---- stage 4: geoms, ground geoms, explicit pairs, mesh hulls, the heightfield, the (empty) swimming table, contact-row maps
+static int pack_geom_tables(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  DevModel& D = c->dm;
+  const int nplane = F.nplane;      // ground geoms: planes and the heightfield
   std::vector<int4> g_info(m->ngeom ? m->ngeom : 1); std::vector<float4> g_size(g_info.size()), g_pos(g_info.size()), g_quat(g_info.size()), g_sol0(g_info.size()), g_sol1(g_info.size());
   std::vector<float4> p_plane(nplane ? nplane : 1), p_prm(nplane ? nplane : 1), p_hq(nplane ? nplane : 1, f4(1, 0, 0, 0)), p_hs(nplane ? nplane : 1, f4(1, 1, 0, 0));
-  std::vector<float4> d_lim(NT, f4(0, 0, 0, 0)), d_sol0(NT, f4(0.02, 1, 0.9, 0.95)), d_sol1(NT, f4(0.001, 0.5, 2, 0));
-  if (cons) {
+  if (F.cons) {
     int ip = 0;
     for (int g = 0; g < m->ngeom; g++) {
       int b = m->geom_bodyid[g];
@@ -2681,272 +2718,236 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
         ip++;
       }
     }
-    for (int j = 0; j < nj; j++) {
-      if (m->jnt_type[j] == FMJ_JNT_FREE) continue;
-      int d = m->jnt_dofadr[j];
-      d_lim[d] = f4(m->jnt_limited[j] ? 1 : 0, m->jnt_range[2 * j], m->jnt_range[2 * j + 1], m->jnt_margin[j]);
-      d_sol0[d] = f4(m->jnt_solref[2 * j], m->jnt_solref[2 * j + 1], m->jnt_solimp[5 * j], m->jnt_solimp[5 * j + 1]);
-      d_sol1[d] = f4(m->jnt_solimp[5 * j + 2], m->jnt_solimp[5 * j + 3], m->jnt_solimp[5 * j + 4], m->dof_invweight0[d]);
-    }
   }
-  // ---- pack the tables (one device array per family)
-  auto i4f = [](int4 v) { return make_float4(ibits(v.x), ibits(v.y), ibits(v.z), ibits(v.w)); };
-  c->h_btab.assign(NT * BT_STRIDE, f4(0, 0, 0, 0)); c->h_dtab.assign(NT * DT_STRIDE, f4(0, 0, 0, 0));
-  for (int b = 0; b < NT; b++) {
-    float4* t = &c->h_btab[b * BT_STRIDE];
-    t[0] = b_pos_mass[b]; t[1] = b_quat[b]; t[2] = b_ipos[b]; t[3] = b_iquat[b]; t[4] = b_inertia[b]; t[5] = j_axis_q0[b]; t[6] = j_pos_k[b];
-    t[7] = i4f(b_info[b]); t[8] = i4f(b_info2[b]);
-  }
-  for (int d = 0; d < NT; d++) {
-    float4* t = &c->h_dtab[d * DT_STRIDE];
-    int4 act = d_act[d]; act.w = d_parent[d];
-    t[0] = i4f(d_info[d]); t[1] = d_prm[d]; t[2] = i4f(act); t[3] = d_lim[d]; t[4] = d_sol0[d]; t[5] = d_sol1[d];
-  }
-  std::vector<float4> atab((a_src.size() ? a_src.size() : 1) * AT_STRIDE, f4(0, 0, 0, 0));
-  for (size_t a = 0; a < a_src.size(); a++) { atab[a * AT_STRIDE] = a_prm[a]; atab[a * AT_STRIDE + 1] = a_lim[a]; atab[a * AT_STRIDE + 2] = make_float4(ibits(a_src[a]), 0.f, 0.f, 0.f); }
   std::vector<float4> gtab(g_info.size() * GT_STRIDE), ptab(p_plane.size() * PT_STRIDE);
   for (size_t g = 0; g < g_info.size(); g++) { float4* t = &gtab[g * GT_STRIDE]; t[0] = i4f(g_info[g]); t[1] = g_size[g]; t[2] = g_pos[g]; t[3] = g_quat[g]; t[4] = g_sol0[g]; t[5] = g_sol1[g]; }
   for (size_t p = 0; p < p_plane.size(); p++) { ptab[p * PT_STRIDE] = p_plane[p]; ptab[p * PT_STRIDE + 1] = p_prm[p]; ptab[p * PT_STRIDE + 2] = p_hq[p]; ptab[p * PT_STRIDE + 3] = p_hs[p]; }
-  D.npair = cons ? m->npair : 0; D.nfl = 0; D.qtab = nullptr;
-  {
-    std::vector<float4> qtab((m->npair ? m->npair : 1) * QT_STRIDE, f4(0, 0, 0, 0));
-    for (int p = 0; p < m->npair; p++) {
-      const double mu = m->pair_friction[p] > 1e-5 ? m->pair_friction[p] : 1e-5;       // mjMINMU
-      qtab[p * QT_STRIDE] = make_float4(ibits(m->pair_geom1[p]), ibits(m->pair_geom2[p]), (float)mu, 0.f);
-      qtab[p * QT_STRIDE + 1] = f4(m->pair_solref[2 * p], m->pair_solref[2 * p + 1], m->pair_solimp[5 * p], m->pair_solimp[5 * p + 1]);
-      qtab[p * QT_STRIDE + 2] = f4(m->pair_solimp[5 * p + 2], m->pair_solimp[5 * p + 3], m->pair_solimp[5 * p + 4], 0);
-    }
-    UP(qtab, qtab);
+  UP(gtab, gtab); UP(ptab, ptab);
+  std::vector<float4> qtab((m->npair ? m->npair : 1) * QT_STRIDE, f4(0, 0, 0, 0));
+  for (int p = 0; p < m->npair; p++) {
+    const double mu = m->pair_friction[p] > 1e-5 ? m->pair_friction[p] : 1e-5;       // mjMINMU
+    qtab[p * QT_STRIDE] = make_float4(ibits(m->pair_geom1[p]), ibits(m->pair_geom2[p]), (float)mu, 0.f);
+    qtab[p * QT_STRIDE + 1] = f4(m->pair_solref[2 * p], m->pair_solref[2 * p + 1], m->pair_solimp[5 * p], m->pair_solimp[5 * p + 1]);
+    qtab[p * QT_STRIDE + 2] = f4(m->pair_solimp[5 * p + 2], m->pair_solimp[5 * p + 3], m->pair_solimp[5 * p + 4], 0);
   }
-  D.any_polypair = cons ? any_polypair : 0; D.mesh_face = nullptr;
-  if (cons && any_polypair) {
+  UP(qtab, qtab);
+  if (F.cons && F.any_polypair) {
     std::vector<float4> mf(m->nmeshface > 0 ? m->nmeshface : 1, f4(0, 0, 1, 0));
     for (int i = 0; i < m->nmeshface; i++) mf[i] = f4(m->mesh_face[4 * i], m->mesh_face[4 * i + 1], m->mesh_face[4 * i + 2], m->mesh_face[4 * i + 3]);
     UP(mf, mesh_face);
   }
-  D.any_mesh = cons ? any_mesh : 0; D.mesh_vert = nullptr;
-  if (any_mesh) {
+  if (F.any_mesh) {
     std::vector<float4> mv((size_t)m->nmeshvert);
     for (int i = 0; i < m->nmeshvert; i++) mv[i] = f4(m->mesh_vert[3 * i], m->mesh_vert[3 * i + 1], m->mesh_vert[3 * i + 2], 0);
     UP(mv, mesh_vert);
   }
-  D.hf_nrow = D.hf_ncol = 0; D.hf_data = nullptr;
-  if (n_hfield) {
+  if (F.n_hfield) {
     std::vector<float> hf((size_t)m->hfield_nrow * m->hfield_ncol);
     for (size_t i = 0; i < hf.size(); i++) hf[i] = (float)m->hfield_data[i];
     D.hf_nrow = m->hfield_nrow; D.hf_ncol = m->hfield_ncol;
     UP(hf, hf_data);
   }
-  c->h_atab = atab; c->a_src = a_src;
-  UP(c->h_btab, btab); UP(c->h_dtab, dtab); UP(atab, atab); UP(gtab, gtab); UP(ptab, ptab);
-  {   // two envs per wave: bodies and the dofs minus a free root's translational dofs must fit 32 lanes
-    const int t0 = D.root_free ? 3 : 0;
-    const char* envv = getenv("FMJ_DUAL");
-    D.dual_t0 = t0;
-    const bool halves_ok = nb <= 32 && nv - t0 <= 32 && !(envv && envv[0] == '0');      // bodies / lane dofs of an env fit half a wave
-    const bool rk4 = m->integrator == FMJ_INT_RK4;      // four forward launches of the one-env kernel per step: no two-env kernel, no fused launch
-    D.dual_ok = !cons && halves_ok && !rk4 && !c->wide;
-    // the two-env constraint kernel covers what BASELINE configs[3] needs: limits + ground contacts of sphere / capsule / box / cylinder
-    // geoms on ONE ground geom, pyramidal cone, PGS; everything else (pairs, meshes, Newton / CG, the elliptic cone) keeps the one-env kernel
-    D.cons2_ok = cons && halves_ok && !rk4 && D.rs <= FMJ_MAXD && m->solver == FMJ_SOLVER_PGS && !dual_instead && m->cone == FMJ_CONE_PYRAMIDAL && m->noslip_iterations == 0 && m->npair == 0 &&
-                 !any_mesh && nplane <= 1 && m->ngeom <= 32;
-    for (int t = 0; t < 3; t++) D.dual_tadd[t] = t < t0 ? (float)(mtot + m->dof_armature[t] + m->timestep * m->dof_damping[t]) : 1.0f;
-    for (int t = 0; t < 3; t++) D.dual_taddm[t] = t < t0 ? (float)(mtot + m->dof_armature[t]) : 1.0f;
-    if (nv <= 64) {   // elimination rounds of the one-env kernel (lane = dof): dofs grouped by depth, deepest first, <= 3 per round
-      std::vector<DualRound> rounds;
-      std::vector<unsigned long long> ancm(nv, 0ull), descm(nv, 0ull);
-      int maxdep = 0;
-      for (int i = 0; i < nv; i++) {
-        if (ddepth[i] > maxdep) maxdep = ddepth[i];
-        for (int a = m->dof_parentid[i]; a >= 0; a = m->dof_parentid[a]) { ancm[i] |= 1ull << a; descm[a] |= 1ull << i; }
-      }
-      for (int dep = maxdep; dep >= 0; dep--) {
-        std::vector<int> lvl;
-        for (int i = 0; i < nv; i++) if (ddepth[i] == dep) lvl.push_back(i);
-        for (size_t q = 0; q < lvl.size(); q += 3) {
-          DualRound R; memset(&R, 0, sizeof R);
-          int* pp[3] = {&R.p0, &R.p1, &R.p2};
-          R.depth = dep;
-          for (int c = 0; c < 3; c++) {
-            if (q + c < lvl.size()) { const int pv = lvl[q + c]; *pp[c] = pv; R.anc[c] = ancm[pv]; }
-            else *pp[c] = c == 1 ? -1 : R.p0;
-          }
-          rounds.push_back(R);
-        }
-      }
-      D.nround1 = (int)rounds.size();
-      UP(rounds, rounds1);
-      std::vector<WideRound> wide;                  // the same levels, up to six dofs per round
-      for (int dep = maxdep; dep >= 0; dep--) {
-        std::vector<int> lvl;
-        for (int i = 0; i < nv; i++) if (ddepth[i] == dep) lvl.push_back(i);
-        for (size_t q = 0; q < lvl.size(); q += 6) {
-          WideRound R; memset(&R, 0, sizeof R);
-          R.depth = dep; R.np = (int)std::min<size_t>(6, lvl.size() - q);
-          for (int c = 0; c < 6; c++) {
-            if (q + c < lvl.size()) { R.p[c] = lvl[q + c]; R.anc[c] = ancm[lvl[q + c]]; }
-            else R.p[c] = lvl[q];                   // under an empty mask
-          }
-          wide.push_back(R);
-        }
-      }
-      D.nround6 = (int)wide.size();
-      UP(wide, rounds6);
-      {   // per dof, per depth: byte = 4 * lane of the ancestor at that depth (own lane where there is none)
-        std::vector<uint32_t> ancl((size_t)64 * (D.rs / 4), 0u);
-        for (int i = 0; i < 64; i++) {
-          uint8_t* row = (uint8_t*)&ancl[(size_t)i * (D.rs / 4)];
-          for (int l = 0; l < D.rs; l++) row[l] = (uint8_t)(4 * i);
-          if (i < nv) for (int a = m->dof_parentid[i]; a >= 0; a = m->dof_parentid[a]) row[ddepth[a]] = (uint8_t)(4 * a);
-        }
-        D.maxdep1 = maxdep;
-        UP(ancl, ancl1);
-      }
-    }
-    if (c->wide) {   // the two-wave kernel: rounds with 128-bit lane masks, ancestor lanes as one byte each
-      std::vector<std::array<unsigned long long, 2>> ancm(nv);
-      for (int i = 0; i < nv; i++) {
-        ancm[i] = {0ull, 0ull};
-        for (int a = m->dof_parentid[i]; a >= 0; a = m->dof_parentid[a]) ancm[i][a >> 6] |= 1ull << (a & 63);
-      }
-      std::vector<WideRoundW> rounds;
-      for (int dep = max_ddepth; dep >= 0; dep--) {
-        std::vector<int> lvl;
-        for (int i = 0; i < nv; i++) if (ddepth[i] == dep) lvl.push_back(i);
-        for (size_t q = 0; q < lvl.size(); q += 6) {
-          WideRoundW R; memset(&R, 0, sizeof R);
-          R.depth = dep; R.np = (int)std::min<size_t>(6, lvl.size() - q);
-          for (int k = 0; k < 6; k++) {
-            if (q + k < lvl.size()) { R.p[k] = lvl[q + k]; R.anc[k][0] = ancm[lvl[q + k]][0]; R.anc[k][1] = ancm[lvl[q + k]][1]; }
-            else R.p[k] = lvl[q];                   // under empty masks
-          }
-          rounds.push_back(R);
-        }
-      }
-      D.nroundw = (int)rounds.size();
-      UP(rounds, roundsw);
-      std::vector<uint32_t> ancl((size_t)FMJ_WIDE_LANES * (D.rs / 4), 0u);
-      for (int i = 0; i < FMJ_WIDE_LANES; i++) {
-        uint8_t* row = (uint8_t*)&ancl[(size_t)i * (D.rs / 4)];
-        for (int l = 0; l < D.rs; l++) row[l] = (uint8_t)i;
-        if (i < nv) for (int a = m->dof_parentid[i]; a >= 0; a = m->dof_parentid[a]) row[ddepth[a]] = (uint8_t)a;
-      }
-      UP(ancl, anclw);
-      D.maxdep1 = max_ddepth;
-    }
-    {   // elimination rounds: lane dofs grouped by depth, deepest first, at most three per round
-      const int nd = nv - t0 > 0 ? nv - t0 : 0;
-      std::vector<DualRound> rounds;
-      if (D.dual_ok || D.cons2_ok) {
-        std::vector<unsigned long long> ancm(nd, 0ull), descm(nd, 0ull);
-        int maxdep = 0;
-        for (int i = 0; i < nd; i++) {
-          if (ddepth[i + t0] > maxdep) maxdep = ddepth[i + t0];
-          for (int a = m->dof_parentid[i + t0]; a >= t0; a = m->dof_parentid[a]) {
-            ancm[i] |= (1ull << (a - t0)) | (1ull << (a - t0 + 32));
-            descm[a - t0] |= (1ull << i) | (1ull << (i + 32));
-          }
-        }
-        for (int dep = maxdep; dep >= 0; dep--) {
-          std::vector<int> lvl;
-          for (int i = 0; i < nd; i++) if (ddepth[i + t0] == dep) lvl.push_back(i);
-          for (size_t q = 0; q < lvl.size(); q += 3) {
-            DualRound R; memset(&R, 0, sizeof R);
-            int* pp[3] = {&R.p0, &R.p1, &R.p2};
-            R.depth = dep;
-            for (int c = 0; c < 3; c++) {
-              if (q + c < lvl.size()) { const int pv = lvl[q + c]; *pp[c] = pv; R.anc[c] = ancm[pv]; }
-              else *pp[c] = c == 1 ? -1 : R.p0;
-            }
-            for (int c = 0; c < 3; c++) R.ro[c] = *pp[c] < 0 ? -1 : *pp[c] * dual_row_stride(D.rs) * 4;
-            rounds.push_back(R);
-          }
-        }
-      }
-      D.dual_nround = (int)rounds.size();
-      { DualRound R; memset(&R, 0, sizeof R); R.p1 = -1; R.ro[1] = -1; R.depth = -1; rounds.push_back(R); }     // terminator: the two-env kernel's loops stop at it and read it as 'the round after the last'
-      UP(rounds, dual_rounds);
-      {   // per lane dof, per absolute depth: byte = 4 * lane of the ancestor at that depth (the solve pulls x from there
-          // with ds_bpermute); own lane where there is none.  The kernel adds the half's offset.
-        std::vector<uint32_t> ancl((size_t)32 * (D.rs / 4), 0u);
-        int md = 0;
-        for (int i = 0; i < 32; i++) {
-          uint8_t* row = (uint8_t*)&ancl[(size_t)i * (D.rs / 4)];
-          for (int l = 0; l < D.rs; l++) row[l] = (uint8_t)(4 * i);
-          if ((D.dual_ok || D.cons2_ok) && i < nd) {
-            if (ddepth[i + t0] > md) md = ddepth[i + t0];
-            for (int a = m->dof_parentid[i + t0]; a >= t0; a = m->dof_parentid[a]) row[ddepth[a]] = (uint8_t)(4 * (a - t0));
-          }
-        }
-        D.dual_maxdep = md;
-        UP(ancl, dual_ancl);
-      }
-    }
-  }
-  c->d_btab = (float4*)D.btab; c->d_dtab = (float4*)D.dtab;
-  { std::vector<float4> empty4(ST_STRIDE, f4(0, 0, 0, 0)); UP(empty4, stab); }
-  c->ngeom = m->ngeom; c->geom_sensor.assign(m->ngeom ? m->ngeom : 1, -1); c->n_contact_rows = 0; c->d_geom_sensor = nullptr; c->d_pairs = nullptr; c->n_pairs = 0;
+  std::vector<float4> empty4(ST_STRIDE, f4(0, 0, 0, 0));
+  UP(empty4, stab);
+  c->ngeom = m->ngeom; c->geom_sensor.assign(m->ngeom ? m->ngeom : 1, -1);
   c->geom_is_plane.assign(m->ngeom ? m->ngeom : 1, 0);
   for (int g = 0; g < m->ngeom; g++) c->geom_is_plane[g] = m->geom_type[g] == FMJ_GEOM_PLANE || m->geom_type[g] == FMJ_GEOM_HFIELD;
-  D.cons_rows = nullptr; D.cons_a = nullptr; D.cons_z = nullptr; D.cons_zf = nullptr;
-  if (D.cons && D.maxefc > 0) {   // HBM scratch of envs whose constraint rows outgrow LDS (fmj_step_kernel<.., CONS = true>, "big" path)
-    void* p1 = nullptr; void* p2 = nullptr;
-    void* p3 = nullptr;
-    if (hipMalloc(&p1, (size_t)n_envs * D.maxefc * 8 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&p2, (size_t)n_envs * D.maxefc * AG_LD * sizeof(float)) != hipSuccess ||
-        hipMalloc(&p3, (size_t)n_envs * D.maxefc * D.rs * sizeof(float)) != hipSuccess) {
-      if (p1) (void)hipFree(p1);
-      if (p2) (void)hipFree(p2);
-      fmj_destroy(c);
-      return set_err(FMJ_ERR_HIP, "fmj_create: out of device memory for the constraint scratch");
-    }
-    c->allocs.push_back(p1); c->allocs.push_back(p2); c->allocs.push_back(p3);
-    D.cons_rows = (float*)p1; D.cons_a = (float*)p2; D.cons_z = (float*)p3;
-    if (D.npair > 0) {
-      void* p4 = nullptr;
-      if (hipMalloc(&p4, (size_t)n_envs * D.maxefc * D.rs * sizeof(float)) != hipSuccess) { fmj_destroy(c); return set_err(FMJ_ERR_HIP, "fmj_create: out of device memory for the constraint scratch"); }
-      c->allocs.push_back(p4);
-      D.cons_zf = (float*)p4;
+  return FMJ_OK;
+}
+
+// ---- stage 5: the elimination rounds and ancestor-lane tables of the LDL' factorisation, per kernel
+typedef std::array<unsigned long long, 2> LaneMask;
+// per dof of [t0, nv): its ancestors among those dofs, bit a - t0
+static std::vector<LaneMask> ancestor_masks(const fmj_model* m, int t0) {
+  std::vector<LaneMask> anc(m->nv, LaneMask{0ull, 0ull});
+  for (int i = t0; i < m->nv; i++)
+    for (int a = m->dof_parentid[i]; a >= t0; a = m->dof_parentid[a]) anc[i][(a - t0) >> 6] |= 1ull << ((a - t0) & 63);
+  return anc;
+}
+
+// the dofs of [t0, nv) grouped by depth, deepest first, at most k per round (dofs of one depth are not each other's ancestors)
+struct DepthRound { int depth, n, p[6]; };
+static std::vector<DepthRound> depth_rounds(const std::vector<int>& ddepth, int t0, int k) {
+  const int nv = (int)ddepth.size();
+  int maxdep = 0;
+  for (int i = t0; i < nv; i++) maxdep = std::max(maxdep, ddepth[i]);
+  std::vector<DepthRound> rounds;
+  for (int dep = maxdep; dep >= 0; dep--) {
+    std::vector<int> lvl;
+    for (int i = t0; i < nv; i++) if (ddepth[i] == dep) lvl.push_back(i);
+    for (size_t q = 0; q < lvl.size(); q += k) {
+      DepthRound R = {dep, (int)std::min<size_t>(k, lvl.size() - q), {}};
+      for (int c = 0; c < R.n; c++) R.p[c] = lvl[q + c];
+      rounds.push_back(R);
     }
   }
+  return rounds;
+}
+
+// A round of up to three members: an absent second member is -1, an absent third repeats the first, under empty masks.  ro_bytes > 0:
+// the two-env kernel's form, with lane dofs counted from t0, the masks in both halves of the wave and the byte offsets of the rows.
+static DualRound round3(const DepthRound& g, const std::vector<LaneMask>& anc, int t0, int ro_bytes) {
+  DualRound R; memset(&R, 0, sizeof R);
+  int* p[3] = {&R.p0, &R.p1, &R.p2};
+  R.depth = g.depth;
+  for (int c = 0; c < 3; c++) {
+    if (c < g.n) { const unsigned long long a = anc[g.p[c]][0]; *p[c] = g.p[c] - t0; R.anc[c] = ro_bytes ? a | a << 32 : a; }
+    else *p[c] = c == 1 ? -1 : R.p0;
+  }
+  if (ro_bytes) for (int c = 0; c < 3; c++) R.ro[c] = *p[c] < 0 ? -1 : *p[c] * ro_bytes;
+  return R;
+}
+
+// A round of up to six members (WideRound: 64-bit masks, WideRoundW: 128-bit); members beyond np repeat the first under empty masks.
+static void set_mask(unsigned long long& dst, const LaneMask& a) { dst = a[0]; }
+static void set_mask(unsigned long long (&dst)[2], const LaneMask& a) { dst[0] = a[0]; dst[1] = a[1]; }
+template <class R>
+static R round6(const DepthRound& g, const std::vector<LaneMask>& anc) {
+  R r; memset(&r, 0, sizeof r);
+  r.depth = g.depth; r.np = g.n;
+  for (int c = 0; c < 6; c++) {
+    r.p[c] = g.p[c < g.n ? c : 0];
+    if (c < g.n) set_mask(r.anc[c], anc[g.p[c]]);
+  }
+  return r;
+}
+
+// per lane, per depth: byte = scale * lane of the ancestor at that depth of the lane's dof (t0 + lane, lanes below n); own lane elsewhere
+static std::vector<uint32_t> ancestor_lanes(const fmj_model* m, const std::vector<int>& ddepth, int rs, int lanes, int scale, int t0, int n) {
+  std::vector<uint32_t> ancl((size_t)lanes * (rs / 4), 0u);
+  for (int i = 0; i < lanes; i++) {
+    uint8_t* row = (uint8_t*)&ancl[(size_t)i * (rs / 4)];
+    for (int l = 0; l < rs; l++) row[l] = (uint8_t)(scale * i);
+    if (i < n) for (int a = m->dof_parentid[i + t0]; a >= t0; a = m->dof_parentid[a]) row[ddepth[a]] = (uint8_t)(scale * (a - t0));
+  }
+  return ancl;
+}
+
+static int upload_rounds(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  DevModel& D = c->dm;
+  const int nv = m->nv;
+  const std::vector<LaneMask> anc = ancestor_masks(m, 0);
+  if (nv <= 64) {      // the one-env kernel (lane = dof): three dofs per round (the solves), six (ldl_factor)
+    std::vector<DualRound> r3; std::vector<WideRound> r6;
+    for (const DepthRound& g : depth_rounds(F.ddepth, 0, 3)) r3.push_back(round3(g, anc, 0, 0));
+    for (const DepthRound& g : depth_rounds(F.ddepth, 0, 6)) r6.push_back(round6<WideRound>(g, anc));
+    D.nround1 = (int)r3.size(); D.nround6 = (int)r6.size();
+    UP(r3, rounds1); UP(r6, rounds6);
+    UP(ancestor_lanes(m, F.ddepth, D.rs, 64, 4, 0, nv), ancl1);
+  }
+  if (F.wide) {        // the two-wave kernel: six dofs per round, ancestor lanes as one byte each
+    std::vector<WideRoundW> rw;
+    for (const DepthRound& g : depth_rounds(F.ddepth, 0, 6)) rw.push_back(round6<WideRoundW>(g, anc));
+    D.nroundw = (int)rw.size();
+    UP(rw, roundsw);
+    UP(ancestor_lanes(m, F.ddepth, D.rs, FMJ_WIDE_LANES, 1, 0, nv), anclw);
+  }
+  // the two-env kernels: lane dofs (past a free root's translational dofs), three per round, then a terminator their loops stop at and
+  // read as 'the round after the last'; the solve pulls x from the ancestor lanes with ds_bpermute (the kernel adds the half's offset)
+  const int t0 = D.dual_t0, two_env = D.dual_ok || D.cons2_ok;
+  const std::vector<LaneMask> lane_anc = ancestor_masks(m, t0);
+  std::vector<DualRound> rd;
+  if (two_env) for (const DepthRound& g : depth_rounds(F.ddepth, t0, 3)) rd.push_back(round3(g, lane_anc, t0, dual_row_stride(D.rs) * 4));
+  D.dual_nround = (int)rd.size();
+  D.dual_maxdep = rd.empty() ? 0 : rd[0].depth;      // deepest first
+  { DualRound R; memset(&R, 0, sizeof R); R.p1 = -1; R.ro[1] = -1; R.depth = -1; rd.push_back(R); }
+  UP(rd, dual_rounds);
+  UP(ancestor_lanes(m, F.ddepth, D.rs, 32, 4, t0, two_env ? std::max(nv - t0, 0) : 0), dual_ancl);
+  return FMJ_OK;
+}
+
+// ---- stage 6: device scratch: the HBM constraint rows of envs whose rows outgrow LDS, the RK4 stage buffers
+static int alloc_scratch(fmj_ctx* c) {
+  DevModel& D = c->dm;
+  const size_t n = (size_t)c->n_envs;
+  if (D.cons && D.maxefc > 0) {   // fmj_step_kernel<.., CONS = true>, "big" path
+    void *p1, *p2, *p3, *p4 = nullptr;
+    if (dev_alloc(c, n * D.maxefc * 8 * sizeof(float), &p1) || dev_alloc(c, n * D.maxefc * AG_LD * sizeof(float), &p2) ||
+        dev_alloc(c, n * D.maxefc * D.rs * sizeof(float), &p3) || (D.npair > 0 && dev_alloc(c, n * D.maxefc * D.rs * sizeof(float), &p4)))
+      return set_err(FMJ_ERR_HIP, "fmj_create: out of device memory for the constraint scratch");
+    D.cons_rows = (float*)p1; D.cons_a = (float*)p2; D.cons_z = (float*)p3; D.cons_zf = (float*)p4;
+  }
+  if (c->rk4) {
+    const size_t per_env = (size_t)D.nq + 3 * (size_t)D.nv + (size_t)(D.nsensordata > 0 ? D.nsensordata : 1);
+    void* pk;
+    if (dev_alloc(c, per_env * n * sizeof(float), &pk)) return set_err(FMJ_ERR_HIP, "fmj_create: RK4 stage buffers");
+    c->rk_q0 = (float*)pk; c->rk_v0 = c->rk_q0 + n * D.nq; c->rk_sv = c->rk_v0 + n * D.nv; c->rk_sa = c->rk_sv + n * D.nv;
+    c->rk_sd = c->rk_sa + n * D.nv;
+  }
+  return FMJ_OK;
+}
+
+// ---- stage 7: the kernels the step launches run (launch_step), their LDS, and the register tier of the two-env kernel
+static StepVariant one_env_variant(const DevModel& D) {
+  if (!D.cons) return SV_PLAIN;
+  const bool ell = D.cone == FMJ_CONE_ELLIPTIC, pairs = D.npair > 0, mesh = D.any_mesh;
+  if (D.solver != FMJ_SOLVER_PGS) return ell ? SV_NEWTON_ELL : pairs ? SV_NEWTON_PAIRS : mesh ? SV_NEWTON_MESH : SV_NEWTON;
+  return ell ? (pairs ? SV_PGS_ELL_PAIRS : SV_PGS_ELL) : pairs ? SV_PGS_PAIRS : mesh ? SV_PGS_MESH : SV_PGS;
+}
+
+static int choose_path(fmj_ctx* c, const ModelFacts& F) {
+  DevModel& D = c->dm;
+  const int nb = D.nbody, nv = D.nv, nq = D.nq;
   LdsLayout L = lds_layout(nb, nv, nq, D.rs, D.anc_stride, D.cons, D.maxefc, D.max_contacts, D.nvs, D.npair);
   D.nfl = L.nfl;
   c->lds_bytes = (size_t)L.total * sizeof(float);
-  c->lds_bytes_dual2 = D.dual_ok ? (size_t)(2 * lds2_layout(nb, nv, nq, D.rs, D.dual_t0).total + r4(nb * D.anc_stride) / 4) * sizeof(float) : 0;
-  c->lds_bytes_cons2 = 0; c->d_resume = nullptr;
-  c->lds_bytes_wide = c->wide ? (size_t)ldsw_layout(nb, nv, nq, D.rs, D.anc_stride).total * sizeof(float) : 0;
-  if (c->lds_bytes_wide > 64 * 1024) { fmj_destroy(c); return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: two-wave kernel LDS above 64 KB"); }     // (cannot happen within the size limits above)
+  if (D.dual_ok) c->lds_bytes_dual2 = (size_t)(2 * lds2_layout(nb, nv, nq, D.rs, D.dual_t0).total + r4(nb * D.anc_stride) / 4) * sizeof(float);
+  if (F.wide) c->lds_bytes_wide = (size_t)ldsw_layout(nb, nv, nq, D.rs, D.anc_stride).total * sizeof(float);
   if (D.cons2_ok) {
     c->lds_bytes_cons2 = (size_t)lds3_layout(nb, nv, nq, D.rs, D.dual_t0, D.max_contacts, D.anc_stride).total * sizeof(float);
     void* pr = nullptr;
-    if (c->lds_bytes_cons2 > 64 * 1024 || hipMalloc(&pr, (size_t)n_envs * sizeof(int)) != hipSuccess) D.cons2_ok = 0;      // (cannot happen within the size limits above)
-    else { c->allocs.push_back(pr); c->d_resume = (int*)pr; (void)hipMemset(pr, 0, (size_t)n_envs * sizeof(int)); }
-  }
-  c->rk4 = m->integrator == FMJ_INT_RK4; c->rk_q0 = c->rk_v0 = c->rk_sv = c->rk_sa = c->rk_sd = nullptr;
-  if (c->rk4) {
-    const size_t per_env = (size_t)nq + 3 * (size_t)nv + (size_t)(D.nsensordata > 0 ? D.nsensordata : 1);
-    void* pk = nullptr;
-    if (hipMalloc(&pk, per_env * (size_t)n_envs * sizeof(float)) != hipSuccess) { fmj_destroy(c); return set_err(FMJ_ERR_HIP, "fmj_create: RK4 stage buffers"); }
-    c->allocs.push_back(pk);
-    c->rk_q0 = (float*)pk; c->rk_v0 = c->rk_q0 + (size_t)n_envs * nq; c->rk_sv = c->rk_v0 + (size_t)n_envs * nv; c->rk_sa = c->rk_sv + (size_t)n_envs * nv;
-    c->rk_sd = c->rk_sa + (size_t)n_envs * nv;
+    if (c->lds_bytes_cons2 > 64 * 1024 || dev_alloc(c, (size_t)c->n_envs * sizeof(int), &pr) != hipSuccess) D.cons2_ok = 0;      // (cannot happen within the size limits above)
+    else { c->d_resume = (int*)pr; (void)hipMemset(pr, 0, (size_t)c->n_envs * sizeof(int)); }
   }
   {
     hipDeviceProp_t prop;
     int n_cu = 256;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-    const int waves = (n_envs + 1) / 2;
+    if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+    const int waves = (c->n_envs + 1) / 2;
     // the build registered for the waves per SIMD the batch can fill: 2 (256 registers: model constants resident), 3 (168) or 4 (128)
     c->dual_wps = waves <= 2 * 4 * n_cu ? 2 : (waves <= 3 * 4 * n_cu ? 3 : 4);
     const char* w = getenv("FMJ_WPS");
     if (w && (w[0] == '2' || w[0] == '3' || w[0] == '4')) c->dual_wps = w[0] - '0';
   }
-  if (!c->wide && c->lds_bytes > 64 * 1024) {
-    hipError_t e1 = hipFuncSetAttribute((const void*)pick_kernel(c, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    hipError_t e2 = hipFuncSetAttribute((const void*)pick_kernel(c, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
-    if (e1 != hipSuccess || e2 != hipSuccess) { fmj_destroy(c); return set_err(FMJ_ERR_HIP, "fmj_create: LDS request too large"); }
+  c->path = F.wide ? PATH_TWO_WAVE : D.dual_ok ? PATH_TWO_ENV : D.cons2_ok ? PATH_CONS2_ONE_ENV : PATH_ONE_ENV;
+  c->variant = one_env_variant(D);
+  if (c->path != PATH_TWO_WAVE && c->lds_bytes > 64 * 1024) {
+    hipError_t e1 = hipFuncSetAttribute((const void*)step_kernel(D.rs, true, c->variant), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
+    hipError_t e2 = hipFuncSetAttribute((const void*)step_kernel(D.rs, false, c->variant), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
+    if (e1 != hipSuccess || e2 != hipSuccess) return set_err(FMJ_ERR_HIP, "fmj_create: LDS request too large");
   }
-  *out = c;
+  return FMJ_OK;
+}
+
+extern "C" {
+
+const char* fmj_last_error(void) { return g_err.c_str(); }
+int fmj_abi_version(void) { return FMJ_ABI_VERSION; }
+
+void fmj_destroy(fmj_ctx* c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  for (void* p : c->allocs) (void)hipFree(p);
+  delete c;
+}
+
+int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out) {
+  if (!m || !out || n_envs <= 0) return set_err(FMJ_ERR_ARG, "fmj_create: NULL model/out or n_envs <= 0");
+  *out = nullptr;
+  ModelFacts F;
+  if (int rc = check_model(m, &F)) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_err(FMJ_ERR_NODEVICE, "fmj_create: no HIP device visible");
+  if (device < 0 || device >= ndev) return set_err(FMJ_ERR_ARG, "fmj_create: bad device ordinal");
+  HIP_TRY(hipSetDevice(device));
+  std::unique_ptr<fmj_ctx, void (*)(fmj_ctx*)> c(new fmj_ctx(), fmj_destroy);     // a failing stage leaves through here: fmj_destroy frees its allocations
+  c->device = device; c->n_envs = n_envs;
+  describe_model(c.get(), m, F);
+  int rc;
+  if ((rc = pack_body_dof_tables(c.get(), m, F)) || (rc = pack_geom_tables(c.get(), m, F)) || (rc = upload_rounds(c.get(), m, F)) ||
+      (rc = alloc_scratch(c.get())) || (rc = choose_path(c.get(), F)))
+    return rc;
+  *out = c.release();
   return FMJ_OK;
 }
 
@@ -2957,13 +2958,11 @@ int fmj_get_sensor_layout(const fmj_ctx* c, fmj_sensor_layout_t* out) {
 
 int fmj_kernel_info(const fmj_ctx* c, int32_t* lds_bytes_per_env, int32_t* threads_per_env) {
   if (!c) return set_err(FMJ_ERR_ARG, "fmj_kernel_info: NULL ctx");
-  if (c->wide) {           // one workgroup of two waves per env (fmj_wide.inc)
-    if (lds_bytes_per_env) *lds_bytes_per_env = (int32_t)c->lds_bytes_wide;
-    if (threads_per_env) *threads_per_env = 128;
-    return FMJ_OK;
-  }
-  if (lds_bytes_per_env) *lds_bytes_per_env = (int32_t)(c->dm.dual_ok ? c->lds_bytes_dual2 / 2 : (c->dm.cons2_ok ? c->lds_bytes_cons2 / 2 : c->lds_bytes));
-  if (threads_per_env) *threads_per_env = (c->dm.dual_ok || c->dm.cons2_ok) ? 32 : 64;   // the integrating step packs two envs per wave when it can
+  // by StepPath: the integrating step packs two envs per wave when it can
+  const size_t lds[4] = {c->lds_bytes, c->lds_bytes_dual2 / 2, c->lds_bytes_cons2 / 2, c->lds_bytes_wide};
+  const int threads[4] = {64, 32, 32, 128};
+  if (lds_bytes_per_env) *lds_bytes_per_env = (int32_t)lds[c->path];
+  if (threads_per_env) *threads_per_env = threads[c->path];
   return FMJ_OK;
 }
 
@@ -3163,10 +3162,10 @@ int fmj_step_fused(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, void*
   A.w_amp = a->wave.amplitude; A.w_lag = a->wave.phase_lag; A.w_env = a->wave.env_phase; A.w_freq = a->wave.frequency;
   A.ctrl_out = a->controller == 1 ? a->ctrl_out : nullptr;
   if (a->rows_ahead) {
-    if (!c->dm.dual_ok || A.substeps != 1) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: rows_ahead needs the two-env unconstrained step kernel and substeps = 1 (write the rows with fmj_before_step instead)");
+    if (c->path != PATH_TWO_ENV || A.substeps != 1) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: rows_ahead needs the two-env unconstrained step kernel and substeps = 1 (write the rows with fmj_before_step instead)");
     A.rows_ahead = 1; A.xfrc_applied_out = (float*)d->xfrc_applied;
   }
-  A.env_order = c->dm.dual_ok ? nullptr : a->env_order;      // the two-env constraint kernel pairs neighbours of the order: similar row counts
+  A.env_order = c->path == PATH_TWO_ENV ? nullptr : a->env_order;      // the two-env constraint kernel pairs neighbours of the order: similar row counts
   HIP_TRY(hipSetDevice(c->device));
   return launch_step(c, true, A, stream);
 }

@@ -174,3 +174,55 @@ def test_model_size_limits_are_refused_with_a_message_that_names_them():
     m.noslip_iterations = -1
     rc, msg = create(m)
     assert rc != 0 and (rc == 4 or 'noslip' in msg), (rc, msg)
+
+
+def _box_walker():
+    """A free box trunk with two limited hinged box limbs above a plane: dof chains of 7 (row length 8), 2 + 4 * max_contacts rows."""
+    from farms_mujoco_amd.model import ModelBuilder, GEOM_BOX, GEOM_PLANE
+    b = ModelBuilder('boxbot', timestep=1e-3)
+    b.options['max_contacts'] = 16
+    b.add_body('trunk', pos=(0, 0, 0.06), mass=0.5, inertia=(2e-4, 6e-4, 7e-4), joint='free')
+    b.add_geom('trunk', GEOM_BOX, (0.06, 0.03, 0.015), friction=(0.8, 0, 0))
+    for side, y in (('L', 0.04), ('R', -0.04)):
+        b.add_body(f'limb_{side}', parent='trunk', pos=(0.03, y, 0.0), mass=0.05, inertia=(2e-6, 8e-6, 8e-6),
+                   joint='hinge', axis=(0, 1, 0), damping=1e-3, limited=True, range=(-0.6, 0.6))
+        b.add_geom(f'limb_{side}', GEOM_BOX, (0.03, 0.008, 0.008), pos=(0.03, 0, -0.02), quat=(0.9659258, 0, 0.258819, 0),
+                   friction=(1.0, 0, 0))
+        b.add_position_actuator(f'joint_limb_{side}', kp=0.05)
+    b.add_geom('world', GEOM_PLANE, (0, 0, 0), friction=(0, 0, 0))
+    return b.compile()
+
+
+def test_model_refusals_come_before_the_device_lookup():
+    """fmj_create checks the whole model before it looks for a device: these refusals carry their own code and message on a machine
+    with or without a GPU (the constraint-row limit, the layout of M, the staging room of the block solvers)."""
+    from farms_mujoco_amd import _lib
+    from farms_mujoco_amd.model import CONES
+    if not os.path.exists(_lib.SO_PATH):
+        pytest.skip('libfmj_hip.so not built')
+    lib = _lib.load()
+
+    def create(m):
+        c = m.as_c(); ctx = ctypes.c_void_p()
+        rc = lib.fmj_create(ctypes.byref(c), 4, 0, ctypes.byref(ctx))
+        if rc == 0:
+            lib.fmj_destroy(ctx)
+        return rc, lib.fmj_last_error().decode()
+    m = _box_walker()
+    rc, msg = create(m)                                      # 2 + 4 * 16 rows: the model passes (4 = FMJ_ERR_NODEVICE without a GPU)
+    assert rc in (0, 4), (rc, msg)
+    m = _box_walker(); m.max_contacts = 48                   # 2 + 4 * 48 = 194 rows
+    rc, msg = create(m)
+    assert rc == 2 and 'more than 192 constraint rows possible' in msg, (rc, msg)
+    m = _box_walker(); m.dof_Madr = np.array(m.dof_Madr); m.dof_Madr[3] += 1
+    rc, msg = create(m)
+    assert rc == 1 and msg == 'fmj_create: dof_Madr inconsistent', (rc, msg)
+    m = _box_walker(); m.nM += 1
+    rc, msg = create(m)
+    assert rc == 1 and msg == 'fmj_create: nM inconsistent', (rc, msg)
+    m = _box_walker(); m.cone = CONES['elliptic']; m.max_contacts = 40     # 162 rows, 64 * 8 floats of staging < 4 * 162
+    rc, msg = create(m)
+    assert rc == 2 and 'PGS with the elliptic cone / noslip: too many constraint rows' in msg, (rc, msg)
+    m = _box_walker(); m.cone = CONES['elliptic']; m.max_contacts = 31     # 126 rows: 512 >= 504 floats
+    rc, msg = create(m)
+    assert rc in (0, 4), (rc, msg)
