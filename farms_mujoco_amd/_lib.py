@@ -66,6 +66,13 @@ BEFORE_ROWS, BEFORE_LINKS_ONLY, BEFORE_CONTACTS, BEFORE_DRAG = 1, 2, 4, 8      #
 
 
 # every symbol include/fmj.h declares: name -> (restype, argtypes)
+class CCreateOptions(ctypes.Structure):
+    _fields_ = [('size', ctypes.c_int32), ('precision', ctypes.c_int32)]
+
+
+PRECISIONS = {'fp32': 0, 'fp64': 1}      # FMJ_PRECISION_* of include/fmj.h
+
+
 class CCpgDesc(ctypes.Structure):
     _fields_ = [('n_osc', ctypes.c_int32), ('n_conn', ctypes.c_int32), ('nu', ctypes.c_int32),
                 ('frequency', _D), ('rate', _D), ('amplitude', _D),
@@ -75,6 +82,8 @@ class CCpgDesc(ctypes.Structure):
 
 SYMBOLS = {
     'fmj_create': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_VP)]),
+    'fmj_create_ex': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(CCreateOptions), ctypes.POINTER(_VP)]),
+    'fmj_precision': (ctypes.c_int, [_VP]),
     'fmj_destroy': (None, [_VP]),
     'fmj_last_error': (ctypes.c_char_p, []),
     'fmj_abi_version': (ctypes.c_int, []),
@@ -141,9 +150,12 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
         jobs = [(os.path.join(objdir, 'host.o'), [])] + [(os.path.join(objdir, f'k{n}.o'), [f'-DFMJ_TU_MAXD={n}'])
                                                          for n in range(4, 65, 4)]      # 36 .. 64: the unconstrained one-env kernel only
         jobs += [(os.path.join(objdir, f'kw{n}.o'), [f'-DFMJ_TU_WIDE={n}']) for n in (32, 64)]      # the two-wave kernel (csrc/fmj_wide.inc)
+        f64_job = (os.path.join(objdir, 'kf64.o'), ['-DFMJ_TU_F64'])      # the fp64 step kernel (csrc/fmj_f64.inc)
         if dev:
-            todo = [j for j in jobs if not j[1] or int(j[1][0].split('=')[1]) in dev or not os.path.exists(j[0])]
+            todo = [j for j in jobs if not j[1] or int(j[1][0].split('=')[1]) in dev or not os.path.exists(j[0])] + [f64_job]
+            jobs.append(f64_job)
         else:
+            jobs.append(f64_job)
             todo = jobs
 
         def cc(job):
@@ -186,7 +198,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
     return target
 
 
-OPTIONAL_IN_AB_BASE = ('fmj_solver_info',)      # queries only (physics.py tolerates their absence under FMJ_SO)
+OPTIONAL_IN_AB_BASE = ('fmj_solver_info', 'fmj_create_ex', 'fmj_precision')      # queries only (physics.py tolerates their absence under FMJ_SO)
 
 
 def load():

@@ -1,0 +1,451 @@
+// fmj_f64.inc — the fp64 step kernel: an unconstrained step in double precision throughout, selected per context with
+// fmj_create_ex(FMJ_PRECISION_F64) (included from fmj_hip.hip; the kernel itself is compiled in its own translation unit, -DFMJ_TU_F64).
+//
+// One workgroup of 128 threads (two wavefronts) per environment, whatever the model's size: lane t is body t and dof t, as in
+// fmj_wide.inc.  The per-env buffers of fmj_data stay fp32: they are widened on load and rounded once on store (a launch of n steps
+// keeps the state in LDS as doubles between its steps).  The model constants come from a second, fp64 set of tables (F64Model) that
+// only fp64 contexts upload.  Every stage follows oracle/fmj_oracle.c's formulas (the 10-vector spatial inertias about the tree's centre
+// of mass, mj_integratePos, true divisions and square roots); what differs is the order of some sums:
+//   K / V   pointer jumping along the body chains through LDS, as in fmj_wide.inc (the oracle walks parent -> child)
+//   C / S   the tree's centre of mass and the subtree sums (composite inertias, body forces): every lane adds the rows of its own
+//           contiguous depth-first range [lane, lane + subtree size) from LDS, last body first: no prefix differences, no cancellation
+//   M       lane = dof i writes row i of H = M + diag(armature + h (damping + implicitfast gains)) to LDS: H[i][j] at column depth(j)
+//   L       L'DL on the rows in LDS by rounds of unrelated dofs of one depth (the WideRoundW rounds), one barrier per round: an
+//           ancestor lane subtracts (H[p][i] / D_p) x row p for every pivot p of the round below it, and the same multiple of p's
+//           right-hand side; a pivot's row and right-hand side are final before the first round of its depth
+//   X       x_i /= D_i, then the root-first sweep a tree level at a time (one barrier per level)
+//   freeze  decided for the workgroup (wg_or) before any lane commits a store; every barrier is reached by all 128 threads
+// No private array is indexed at run time (nothing lives in scratch), no fast reciprocal / rsqrt, no fp32 intermediate.
+
+#define FMJ_F64_LANES 128
+#define F64_BD 28      // doubles per body: pos(3) mass, quat(4), ipos(3) subtree mass, iquat(4), inertia(3) -, axis(3) qpos0, jnt_pos(3) stiffness
+#define F64_BI 8       // ints per body: parent, joint type (-1 none), qpos address, dof address, subtree size
+#define F64_DI 8       // ints per dof: body, depth, qpos address (-1: a free joint's dof), first actuator, actuator count, joint-sensor slot
+#define F64_AD 8       // doubles per actuator (sorted by dof): gain, bias(3), ctrlrange(2), forcerange(2) (infinite where not limited)
+
+struct F64Model {
+  int nbody, nv, nq, nu, rs, jump_rounds, anc_stride, root_free, any_stiffness, implicitfast, nsensordata, njs, maxdep, nround;
+  double h, gx, gy, gz, mtot;
+  const double* bd;             // [nbody][F64_BD]
+  const int* bi;                // [nbody][F64_BI]
+  const double* dd;             // [nv][2] armature, damping
+  const int* di;                // [nv][F64_DI]
+  const double* ad;             // [nact][F64_AD]
+  const int* asrc;              // [nact] the model's actuator index (ctrl / actuatorfrc slot)
+  const uint8_t* b_anc;         // [nbody][anc_stride] ancestor body at distance 2^r (DevModel's table)
+  const uint8_t* danc;          // [nv][rs] ancestor dof at each depth below the dof's own
+  const struct WideRoundW* rounds;   // [nround] elimination rounds, deepest level first
+};
+
+// LDS map, in doubles (ints at the end)
+struct LdsLayoutD { int QP, QV, XA, XCH, CD, CI, CR, CF, CS, MX, HR, XW, FLG, total_bytes; };
+__host__ __device__ inline LdsLayoutD ldsd_layout(int nb, int nv, int nq, int rs) {
+  LdsLayoutD L; int o = 0;
+  L.QP = o; o += (nq + 1) & ~1;
+  L.QV = o; o += (nv + 1) & ~1;
+  L.XA = o; o += (nv + 1) & ~1;
+  L.XCH = o; o += 2 * FMJ_F64_LANES * 8;      // two exchange buffers of 8 doubles per lane (K / V)
+  L.CD = o; o += nv * 6;                      // cdof
+  L.CI = o; o += nb * 10;                     // cinert
+  L.CR = o; o += nb * 10;                     // composite inertia
+  L.CF = o; o += nb * 6;                      // body force
+  L.CS = o; o += nb * 6;                      // subtree force
+  L.MX = o; o += nb * 4;                      // mass * xipos, mass
+  L.HR = o; o += nv * rs;                     // rows of H, then of L'DL
+  L.XW = o; o += FMJ_F64_LANES;               // right-hand side / solution, published per lane
+  L.FLG = o; o += 4;                          // wg_or slots (8 ints)
+  L.total_bytes = o * 8;
+  return L;
+}
+
+#ifdef FMJ_TU_F64
+struct d3 { double x, y, z; };
+struct dq { double w, x, y, z; };
+struct d6 { d3 r, l; };
+__device__ __forceinline__ d3 dmk(double x, double y, double z) { d3 r = {x, y, z}; return r; }
+__device__ __forceinline__ d3 dadd(d3 a, d3 b) { return dmk(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ d3 dsub(d3 a, d3 b) { return dmk(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ __forceinline__ d3 dscl(d3 a, double s) { return dmk(a.x * s, a.y * s, a.z * s); }
+__device__ __forceinline__ double ddot(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ d3 dcross(d3 a, d3 b) { return dmk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+__device__ __forceinline__ dq dqmul(dq a, dq b) {
+  dq r;
+  r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
+  r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
+  r.y = a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x;
+  r.z = a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w;
+  return r;
+}
+__device__ __forceinline__ dq dqnormalize(dq q) {      // mju_normalize4
+  const double n = sqrt(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+  if (n < 1e-15) { dq r = {1.0, 0.0, 0.0, 0.0}; return r; }
+  dq r = {q.w / n, q.x / n, q.y / n, q.z / n};
+  return r;
+}
+struct dm33 { double a0, a1, a2, a3, a4, a5, a6, a7, a8; };
+__device__ __forceinline__ dm33 dq2m(dq q) {           // mju_quat2Mat
+  dm33 m;
+  const double q00 = q.w * q.w, q11 = q.x * q.x, q22 = q.y * q.y, q33 = q.z * q.z;
+  m.a0 = q00 + q11 - q22 - q33; m.a4 = q00 - q11 + q22 - q33; m.a8 = q00 - q11 - q22 + q33;
+  m.a1 = 2.0 * (q.x * q.y - q.w * q.z); m.a2 = 2.0 * (q.x * q.z + q.w * q.y);
+  m.a3 = 2.0 * (q.x * q.y + q.w * q.z); m.a5 = 2.0 * (q.y * q.z - q.w * q.x);
+  m.a6 = 2.0 * (q.x * q.z - q.w * q.y); m.a7 = 2.0 * (q.y * q.z + q.w * q.x);
+  return m;
+}
+__device__ __forceinline__ d3 dmrot(const dm33& m, d3 v) {
+  return dmk(m.a0 * v.x + m.a1 * v.y + m.a2 * v.z, m.a3 * v.x + m.a4 * v.y + m.a5 * v.z, m.a6 * v.x + m.a7 * v.y + m.a8 * v.z);
+}
+__device__ __forceinline__ d3 dqrot(dq q, d3 v) { return dmrot(dq2m(q), v); }      // mju_rotVecQuat
+__device__ __forceinline__ dq daxisangle(d3 ax, double ang) {                     // mju_axisAngle2Quat
+  if (ang == 0.0) { dq r = {1.0, 0.0, 0.0, 0.0}; return r; }
+  double s, c;
+  sincos(0.5 * ang, &s, &c);
+  dq r = {c, ax.x * s, ax.y * s, ax.z * s};
+  return r;
+}
+__device__ __forceinline__ d6 d6add(d6 a, d6 b) { d6 o = {dadd(a.r, b.r), dadd(a.l, b.l)}; return o; }
+__device__ __forceinline__ d6 d6scl(d6 a, double s) { d6 o = {dscl(a.r, s), dscl(a.l, s)}; return o; }
+__device__ __forceinline__ double d6dot(d6 a, d6 b) { return a.r.x * b.r.x + a.r.y * b.r.y + a.r.z * b.r.z + a.l.x * b.l.x + a.l.y * b.l.y + a.l.z * b.l.z; }
+__device__ __forceinline__ d6 dcross_motion(d6 vel, d6 v) { d6 o = {dcross(vel.r, v.r), dadd(dcross(vel.r, v.l), dcross(vel.l, v.r))}; return o; }
+__device__ __forceinline__ d6 dcross_force(d6 vel, d6 f) { d6 o = {dadd(dcross(vel.r, f.r), dcross(vel.l, f.l)), dcross(vel.r, f.l)}; return o; }
+struct di10 { double i0, i1, i2, i3, i4, i5, i6, i7, i8, i9; };      // Ixx Iyy Izz Ixy Ixz Iyz m dx, m dy, m dz, m
+__device__ __forceinline__ d6 dinert_mul(const di10& i, d6 v) {       // mju_mulInertVec
+  d6 o;
+  o.r.x = i.i0 * v.r.x + i.i3 * v.r.y + i.i4 * v.r.z - i.i8 * v.l.y + i.i7 * v.l.z;
+  o.r.y = i.i3 * v.r.x + i.i1 * v.r.y + i.i5 * v.r.z + i.i8 * v.l.x - i.i6 * v.l.z;
+  o.r.z = i.i4 * v.r.x + i.i5 * v.r.y + i.i2 * v.r.z - i.i7 * v.l.x + i.i6 * v.l.y;
+  o.l.x = i.i8 * v.r.y - i.i7 * v.r.z + i.i9 * v.l.x;
+  o.l.y = i.i6 * v.r.z - i.i8 * v.r.x + i.i9 * v.l.y;
+  o.l.z = i.i7 * v.r.x - i.i6 * v.r.y + i.i9 * v.l.z;
+  return o;
+}
+__device__ __forceinline__ void dput6(double* p, d6 v) { p[0] = v.r.x; p[1] = v.r.y; p[2] = v.r.z; p[3] = v.l.x; p[4] = v.l.y; p[5] = v.l.z; }
+__device__ __forceinline__ d6 dget6(const double* p) { d6 v = {dmk(p[0], p[1], p[2]), dmk(p[3], p[4], p[5])}; return v; }
+__device__ __forceinline__ void dput10(double* p, const di10& i) { p[0] = i.i0; p[1] = i.i1; p[2] = i.i2; p[3] = i.i3; p[4] = i.i4; p[5] = i.i5; p[6] = i.i6; p[7] = i.i7; p[8] = i.i8; p[9] = i.i9; }
+__device__ __forceinline__ di10 dget10(const double* p) { di10 i = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9]}; return i; }
+
+__global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Model FM, const StepArgs A) {
+  extern __shared__ __align__(16) double ldsd[];
+  const int env = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int wv = lane >> 6;
+  const int nb = FM.nbody, nv = FM.nv, nq = FM.nq, nu = FM.nu, rs = FM.rs;
+  const LdsLayoutD L = ldsd_layout(nb, nv, nq, rs);
+  double* QP = ldsd + L.QP; double* QV = ldsd + L.QV; double* XA = ldsd + L.XA; double* XCH = ldsd + L.XCH;
+  double* CD = ldsd + L.CD; double* CI = ldsd + L.CI; double* CR = ldsd + L.CR; double* CF = ldsd + L.CF; double* CS = ldsd + L.CS;
+  double* MX = ldsd + L.MX; double* HR = ldsd + L.HR; double* XW = ldsd + L.XW;
+  int* FLG = (int*)(ldsd + L.FLG);
+
+  const bool isb = lane > 0 && lane < nb;
+  const int bl = isb ? lane : 0;
+  const bool isd = lane < nv;
+  const int dl = isd ? lane : 0;
+  // ---- the lane's model constants: body (joint) and dof
+  const double* bdp = FM.bd + (size_t)bl * F64_BD;
+  const int* bip = FM.bi + (size_t)bl * F64_BI;
+  const int parent = bip[0], jtype = isb ? bip[1] : -1, qadr = bip[2], dadr = bip[3];
+  const int lastb = isb ? lane + bip[4] - 1 : lane;
+  const int* dip = FM.di + (size_t)dl * F64_DI;
+  const int d_body = dip[0], ddepth = isd ? dip[1] : 0, d_qadr = dip[2], act0 = dip[3], nact = isd ? dip[4] : 0, d_slot = dip[5];
+  const bool d_scalar = isd && d_qadr >= 0;
+  const double d_arm = FM.dd[2 * dl], d_damp = FM.dd[2 * dl + 1];
+  const double h = FM.h;
+
+  // ---- load the state: widened once
+  int warn = 0;
+  {
+    const float* gq = A.qpos + (size_t)env * nq;
+    const float* gv = A.qvel + (size_t)env * nv;
+    for (int i = lane; i < nq; i += FMJ_F64_LANES) { const float v = gq[i]; QP[i] = (double)v; if (!(fabsf(v) <= 1e10f)) warn |= FMJ_WARN_BADQPOS; }   // mj_checkPos
+    for (int i = lane; i < nv; i += FMJ_F64_LANES) { const float v = gv[i]; QV[i] = (double)v; XA[i] = 0.0; if (!(fabsf(v) <= 1e10f)) warn |= FMJ_WARN_BADQVEL; }   // mj_checkVel
+  }
+  double xf0 = 0.0, xf1 = 0.0, xf2 = 0.0, xf3 = 0.0, xf4 = 0.0, xf5 = 0.0;     // world-frame external force / torque on this body
+  if (A.xfrc_applied && isb) {
+    const float* x = A.xfrc_applied + (size_t)env * nb * 6 + bl * 6;
+    xf0 = x[0]; xf1 = x[1]; xf2 = x[2]; xf3 = x[3]; xf4 = x[4]; xf5 = x[5];
+  }
+  // frozen (include/fmj.h): decided for the whole workgroup
+  bool frozen = (A.status[env] & FMJ_WARN_FREEZE) != 0;
+  frozen = wg_or(warn & FMJ_WARN_FREEZE, FLG + 0) != 0 || frozen;
+  int steps_done = 0;
+  __syncthreads();
+
+#pragma unroll 1
+  for (int step = 0; step < A.n_steps; step++) {
+    if (frozen) break;                          // uniform: every freeze decision is a workgroup OR
+    const bool last = step == A.n_steps - 1;
+    // ---- K: local transforms, composed along the chains by pointer jumping through LDS (buffer r & 1)
+    const d3 axis = dmk(bdp[20], bdp[21], bdp[22]);
+    const d3 jpos = dmk(bdp[24], bdp[25], bdp[26]);
+    d3 xp = dmk(bdp[0], bdp[1], bdp[2]);
+    dq xq = {bdp[4], bdp[5], bdp[6], bdp[7]};
+    if (jtype == FMJ_JNT_FREE) {
+      xp = dmk(QP[qadr], QP[qadr + 1], QP[qadr + 2]);
+      dq rq = {QP[qadr + 3], QP[qadr + 4], QP[qadr + 5], QP[qadr + 6]};
+      xq = dqnormalize(rq);
+    } else if (jtype == FMJ_JNT_HINGE) {
+      const dq ql = daxisangle(axis, QP[qadr] - bdp[23]);
+      xp = dadd(xp, dqrot(xq, dsub(jpos, dqrot(ql, jpos))));      // anchor - R(new) jnt_pos, in the parent's frame
+      xq = dqmul(xq, ql);
+    } else if (jtype == FMJ_JNT_SLIDE) {
+      xp = dadd(xp, dqrot(xq, dscl(axis, QP[qadr] - bdp[23])));
+    }
+    if (!isb) { xp = dmk(0.0, 0.0, 0.0); xq.w = 1.0; xq.x = xq.y = xq.z = 0.0; }
+    for (int r = 0; r < FM.jump_rounds; r++) {
+      double* X = XCH + (r & 1) * (FMJ_F64_LANES * 8);
+      X[lane * 8 + 0] = xp.x; X[lane * 8 + 1] = xp.y; X[lane * 8 + 2] = xp.z;
+      X[lane * 8 + 4] = xq.w; X[lane * 8 + 5] = xq.x; X[lane * 8 + 6] = xq.y; X[lane * 8 + 7] = xq.z;
+      __syncthreads();
+      const int a = isb ? (int)FM.b_anc[lane * FM.anc_stride + r] : 0;
+      const dq aq = {X[a * 8 + 4], X[a * 8 + 5], X[a * 8 + 6], X[a * 8 + 7]};
+      xp = dadd(dmk(X[a * 8], X[a * 8 + 1], X[a * 8 + 2]), dqrot(aq, xp));
+      xq = dqmul(aq, xq);
+    }
+    xq = dqnormalize(xq);
+    const dm33 xmat = dq2m(xq);
+    const d3 xi = dadd(xp, dmrot(xmat, dmk(bdp[8], bdp[9], bdp[10])));
+    const double mass = isb ? bdp[3] : 0.0;
+    // ---- C: the tree's centre of mass
+    if (lane < nb) { MX[lane * 4] = mass * xi.x; MX[lane * 4 + 1] = mass * xi.y; MX[lane * 4 + 2] = mass * xi.z; }
+    __syncthreads();                                                   // (also closes K's last reads of XCH)
+    d3 com = dmk(0.0, 0.0, 0.0);
+    for (int b = nb - 1; b >= 1; b--) com = dadd(com, dmk(MX[b * 4], MX[b * 4 + 1], MX[b * 4 + 2]));
+    com = dmk(com.x / FM.mtot, com.y / FM.mtot, com.z / FM.mtot);
+    // ---- cinert about the centre of mass (mj_comPos)
+    di10 ci;
+    {
+      const dq iq = {bdp[12], bdp[13], bdp[14], bdp[15]};
+      const dm33 R = dq2m(dqmul(xq, iq));
+      const double n0 = bdp[16], n1 = bdp[17], n2 = bdp[18];
+      const d3 dif = dsub(xi, com);
+      ci.i0 = R.a0 * R.a0 * n0 + R.a1 * R.a1 * n1 + R.a2 * R.a2 * n2;
+      ci.i1 = R.a3 * R.a3 * n0 + R.a4 * R.a4 * n1 + R.a5 * R.a5 * n2;
+      ci.i2 = R.a6 * R.a6 * n0 + R.a7 * R.a7 * n1 + R.a8 * R.a8 * n2;
+      ci.i3 = R.a0 * R.a3 * n0 + R.a1 * R.a4 * n1 + R.a2 * R.a5 * n2;
+      ci.i4 = R.a0 * R.a6 * n0 + R.a1 * R.a7 * n1 + R.a2 * R.a8 * n2;
+      ci.i5 = R.a3 * R.a6 * n0 + R.a4 * R.a7 * n1 + R.a5 * R.a8 * n2;
+      ci.i0 += mass * (dif.y * dif.y + dif.z * dif.z);
+      ci.i1 += mass * (dif.x * dif.x + dif.z * dif.z);
+      ci.i2 += mass * (dif.x * dif.x + dif.y * dif.y);
+      ci.i3 -= mass * dif.x * dif.y; ci.i4 -= mass * dif.x * dif.z; ci.i5 -= mass * dif.y * dif.z;
+      ci.i6 = mass * dif.x; ci.i7 = mass * dif.y; ci.i8 = mass * dif.z; ci.i9 = mass;
+      if (!isb) { di10 z = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; ci = z; }
+      if (lane < nb) dput10(CI + lane * 10, ci);
+    }
+    // ---- V: cdof, vJ, cvel = chain sum of vJ, cacc = -g + chain sum of cdof_dot qvel (exchanges alternate between the two buffers)
+    d6 cv, ca;
+    {
+      const d3 z3 = dmk(0.0, 0.0, 0.0);
+      d6 vJ = {z3, z3}, vt = {z3, z3};
+      if (jtype == FMJ_JNT_HINGE || jtype == FMJ_JNT_SLIDE) {
+        const d3 axw = dmrot(xmat, axis);
+        d6 cd;
+        if (jtype == FMJ_JNT_HINGE) { const d3 anchor = dadd(xp, dmrot(xmat, jpos)); cd.r = axw; cd.l = dcross(axw, dsub(com, anchor)); }
+        else { cd.r = z3; cd.l = axw; }
+        dput6(CD + dadr * 6, cd);
+        vJ = d6scl(cd, QV[dadr]);
+      } else if (jtype == FMJ_JNT_FREE) {
+        const d3 off = dsub(com, xp);
+        vt.l = dmk(QV[dadr], QV[dadr + 1], QV[dadr + 2]);
+        const d6 t0 = {z3, dmk(1.0, 0.0, 0.0)}, t1 = {z3, dmk(0.0, 1.0, 0.0)}, t2 = {z3, dmk(0.0, 0.0, 1.0)};
+        dput6(CD + dadr * 6, t0); dput6(CD + (dadr + 1) * 6, t1); dput6(CD + (dadr + 2) * 6, t2);
+        const d3 c0 = dmk(xmat.a0, xmat.a3, xmat.a6), c1 = dmk(xmat.a1, xmat.a4, xmat.a7), c2 = dmk(xmat.a2, xmat.a5, xmat.a8);
+        const d6 r0 = {c0, dcross(c0, off)}, r1 = {c1, dcross(c1, off)}, r2 = {c2, dcross(c2, off)};
+        dput6(CD + (dadr + 3) * 6, r0); dput6(CD + (dadr + 4) * 6, r1); dput6(CD + (dadr + 5) * 6, r2);
+        vJ = d6add(d6add(d6scl(r0, QV[dadr + 3]), d6scl(r1, QV[dadr + 4])), d6scl(r2, QV[dadr + 5]));
+      }
+      int xb = 0;
+#define XPULL6D(dst_, src_, v_) do { \
+        double* X_ = XCH + xb * (FMJ_F64_LANES * 8); \
+        dput6(X_ + lane * 8, v_); \
+        __syncthreads(); \
+        dst_ = dget6(X_ + (src_) * 8); \
+        xb ^= 1; } while (0)
+      cv = d6add(vt, vJ);
+      for (int r = 0; r < FM.jump_rounds; r++) {
+        d6 o; XPULL6D(o, isb ? (int)FM.b_anc[lane * FM.anc_stride + r] : 0, cv);
+        cv = d6add(cv, o);
+      }
+      d6 cpar; XPULL6D(cpar, isb ? parent : 0, cv);
+      cpar = d6add(cpar, vt);
+      ca = dcross_motion(cpar, vJ);
+      if (!isb) { ca.r = ca.l = z3; }
+      for (int r = 0; r < FM.jump_rounds; r++) {
+        d6 o; XPULL6D(o, isb ? (int)FM.b_anc[lane * FM.anc_stride + r] : 0, ca);
+        ca = d6add(ca, o);
+      }
+#undef XPULL6D
+      ca.l = dsub(ca.l, dmk(FM.gx, FM.gy, FM.gz));
+      if (!isb) { cv.r = cv.l = z3; }
+    }
+    // ---- F: body force cinert cacc + cvel x* (cinert cvel) (mj_rne), minus the external wrench about the centre of mass
+    {
+      d6 f = d6add(dinert_mul(ci, ca), dcross_force(cv, dinert_mul(ci, cv)));
+      const d3 fw = dmk(xf0, xf1, xf2), tw = dmk(xf3, xf4, xf5);
+      f.r = dsub(f.r, dadd(tw, dcross(dsub(xi, com), fw)));
+      f.l = dsub(f.l, fw);
+      if (lane < nb) { if (!isb) { f.r = f.l = dmk(0.0, 0.0, 0.0); } dput6(CF + lane * 6, f); }
+    }
+    // ---- sensors and poses of this (pre-integration) state
+    if (last && lane < nb) {
+      float* p = A.xpos + (size_t)env * nb * 3 + lane * 3; p[0] = (float)xp.x; p[1] = (float)xp.y; p[2] = (float)xp.z;
+      float* q = A.xquat + (size_t)env * nb * 4 + lane * 4; q[0] = (float)xq.w; q[1] = (float)xq.x; q[2] = (float)xq.y; q[3] = (float)xq.z;
+      float* ip = A.xipos + (size_t)env * nb * 3 + lane * 3; ip[0] = (float)xi.x; ip[1] = (float)xi.y; ip[2] = (float)xi.z;
+      if (isb) {
+        const d3 linvel = dsub(cv.l, dcross(dsub(xi, com), cv.r));
+        float* sp = A.sensordata + (size_t)env * FM.nsensordata + 6 * (lane - 1);
+        sp[0] = (float)linvel.x; sp[1] = (float)linvel.y; sp[2] = (float)linvel.z;
+        sp[3] = (float)cv.r.x; sp[4] = (float)cv.r.y; sp[5] = (float)cv.r.z;
+      }
+    }
+    __syncthreads();
+    // ---- S: composite inertia and subtree force: the rows of the lane's own depth-first range, last body first
+    if (isb) {
+      di10 s = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      d6 fs = {dmk(0.0, 0.0, 0.0), dmk(0.0, 0.0, 0.0)};
+      for (int b = lastb; b >= lane; b--) {
+        const di10 c = dget10(CI + b * 10);
+        s.i0 += c.i0; s.i1 += c.i1; s.i2 += c.i2; s.i3 += c.i3; s.i4 += c.i4; s.i5 += c.i5; s.i6 += c.i6; s.i7 += c.i7; s.i8 += c.i8; s.i9 += c.i9;
+        fs = d6add(fs, dget6(CF + b * 6));
+      }
+      dput10(CR + lane * 10, s);
+      dput6(CS + lane * 6, fs);
+    }
+    __syncthreads();
+    // ---- Q: qfrc_smooth = passive - bias + actuation (+ J' xfrc, inside the subtree force) (lane = dof)
+    double qfrc = 0.0, bdamp = d_damp;
+    d6 cd = {dmk(0.0, 0.0, 0.0), dmk(0.0, 0.0, 0.0)};
+    if (isd) {
+      cd = dget6(CD + lane * 6);
+      const double qd = QV[lane];
+      double passive = -d_damp * qd;
+      double asum = 0.0;
+      if (d_scalar) {
+        const double qj = QP[d_qadr];
+        if (FM.any_stiffness) {
+          const double kst = FM.bd[(size_t)d_body * F64_BD + 27];
+          if (kst != 0.0) passive += -kst * (qj - (double)A.qpos_spring[(size_t)env * nq + d_qadr]);
+        }
+        for (int a = 0; a < nact; a++) {              // mj_fwdActuation, joint transmission
+          const double* ap = FM.ad + (size_t)(act0 + a) * F64_AD;
+          const int src = FM.asrc[act0 + a];
+          double c = A.ctrl ? (double)A.ctrl[(size_t)step * A.ctrl_step_stride + (size_t)env * nu + src] : 0.0;
+          c = fmin(fmax(c, ap[4]), ap[5]);
+          double f = ap[0] * c + ap[1] + ap[2] * qj + ap[3] * qd;
+          f = fmin(fmax(f, ap[6]), ap[7]);
+          if (FM.implicitfast && !A.disable_actuation && f > ap[6] && f < ap[7]) bdamp += -ap[3];
+          if (A.disable_actuation) f = 0.0;
+          if (last) A.sensordata[(size_t)env * FM.nsensordata + 6 * (nb - 1) + 3 * FM.njs + src] = (float)f;   // actuatorfrc
+          asum += f;
+        }
+      }
+      qfrc = passive - d6dot(cd, dget6(CS + d_body * 6)) + asum;
+    }
+    // ---- M: row i of H (mj_crb, then mj_Euler's M + h B), H[i][j] at column depth(j)
+    {
+      const d6 buf = dinert_mul(dget10(CR + d_body * 10), cd);
+      if (isd) {
+        double* row = HR + lane * rs;
+        const uint8_t* an = FM.danc + (size_t)lane * rs;
+        for (int d = 0; d < ddepth; d++) row[d] = d6dot(dget6(CD + (int)an[d] * 6), buf);
+        row[ddepth] = (d_arm + d6dot(cd, buf)) + h * bdamp;
+        if (A.dbg_H) {
+          for (int d = 0; d < rs; d++) A.dbg_H[((size_t)env * nv + lane) * rs + d] = d <= ddepth ? (float)row[d] : 0.f;
+          A.dbg_qfrc[(size_t)env * nv + lane] = (float)qfrc;
+        }
+      }
+    }
+    // ---- L: L'DL by rounds; the right-hand side is swept leaves-first in the same rounds
+    double x = isd ? qfrc : 0.0;
+    {
+      typedef const WideRoundW __attribute__((address_space(4)))* wround_p;
+      const wround_p RND = (wround_p)FM.rounds;
+      int prev_depth = -1;
+#pragma unroll 1
+      for (int rd = 0; rd < FM.nround; rd++) {
+        const int dep = RND[rd].depth, np = RND[rd].np;
+        if (isd && ddepth == dep && dep != prev_depth) XW[lane] = x;      // final: every round below this depth is done
+        prev_depth = dep;
+        __syncthreads();
+#pragma unroll 1
+        for (int c = 0; c < np; c++) {
+          const int p = RND[rd].p[c];
+          const unsigned long long am = RND[rd].anc[c][0], am1 = RND[rd].anc[c][1];
+          if ((((wv ? am1 : am) >> (lane & 63)) & 1ull) != 0) {
+            const double* rp = HR + p * rs;
+            const double t = rp[ddepth] / rp[dep];
+            double* row = HR + lane * rs;
+            for (int d = 0; d <= ddepth; d++) row[d] -= t * rp[d];
+            x -= t * XW[p];
+          }
+        }
+      }
+      __syncthreads();
+    }
+    // ---- X: divide by D, then the root-first sweep, one tree level at a time
+    const double Dm = isd ? HR[lane * rs + ddepth] : 1.0;
+    x *= 1.0 / Dm;
+#pragma unroll 1
+    for (int lvl = 0; lvl < FM.maxdep; lvl++) {
+      if (isd && ddepth == lvl) XW[lane] = x;
+      __syncthreads();
+      if (isd && ddepth > lvl) x -= (HR[lane * rs + lvl] / Dm) * XW[FM.danc[(size_t)lane * rs + lvl]];
+    }
+    const double my_qacc = x;
+    // ---- semi-implicit Euler; the freeze is decided for the workgroup before any lane commits
+    const double hstep = A.integrate ? h : 0.0;
+    const double pre_qd = isd ? QV[lane] : 0.0;
+    const double nvel = pre_qd + hstep * my_qacc;
+    if (isd) {
+      if (!(fabs(my_qacc) <= 1e10)) warn |= FMJ_WARN_BADQACC;
+      if (!(fabs(nvel) <= 1e10)) warn |= FMJ_WARN_BADQVEL;
+      if (FM.root_free && lane < 3 && A.integrate && !(fabs(QP[lane] + h * nvel) <= 1e10)) warn |= FMJ_WARN_BADQPOS;
+    }
+    if (wg_or(warn & FMJ_WARN_FREEZE, FLG + 2) != 0) frozen = true;
+    if (isd && !frozen) {
+      XA[lane] = my_qacc;
+      QV[lane] = nvel;
+      if (d_scalar) {
+        const double pre_q = QP[d_qadr];
+        QP[d_qadr] = pre_q + hstep * nvel;
+        if (last) {
+          float* s = A.sensordata + (size_t)env * FM.nsensordata + 6 * (nb - 1) + 3 * d_slot;   // jointpos, jointvel, jointlimitfrc
+          s[0] = (float)pre_q; s[1] = (float)pre_qd; s[2] = 0.f;
+        }
+      }
+    }
+    if (!frozen) steps_done++;
+    __syncthreads();
+    if (jtype == FMJ_JNT_FREE && A.integrate && !frozen) {     // mj_integratePos of the free joint (lane = root body)
+      const double nx = QP[qadr] + h * QV[dadr], ny = QP[qadr + 1] + h * QV[dadr + 1], nz = QP[qadr + 2] + h * QV[dadr + 2];
+      if (!(fabs(nx) <= 1e10) || !(fabs(ny) <= 1e10) || !(fabs(nz) <= 1e10)) warn |= FMJ_WARN_BADQPOS;
+      else {
+        QP[qadr] = nx; QP[qadr + 1] = ny; QP[qadr + 2] = nz;
+        d3 w = dmk(QV[dadr + 3], QV[dadr + 4], QV[dadr + 5]);
+        double nrm = sqrt(ddot(w, w));
+        if (nrm < 1e-15) { w = dmk(1.0, 0.0, 0.0); nrm = 0.0; } else w = dmk(w.x / nrm, w.y / nrm, w.z / nrm);
+        dq qo = {QP[qadr + 3], QP[qadr + 4], QP[qadr + 5], QP[qadr + 6]};
+        qo = dqmul(dqnormalize(qo), daxisangle(w, h * nrm));
+        QP[qadr + 3] = qo.w; QP[qadr + 4] = qo.x; QP[qadr + 5] = qo.y; QP[qadr + 6] = qo.z;
+      }
+    }
+    if (wg_or(warn & FMJ_WARN_BADQPOS, FLG + 4) != 0) frozen = true;   // (its barrier also orders the root update before the next step)
+  }
+
+  // ---- store the state: rounded once.  An env that completed no step keeps its buffers as they are.
+  if (steps_done > 0) {
+    float* oq = A.qpos + (size_t)env * nq;
+    float* ov = A.qvel + (size_t)env * nv;
+    if (A.integrate) {
+      for (int i = lane; i < nq; i += FMJ_F64_LANES) oq[i] = (float)QP[i];
+      for (int i = lane; i < nv; i += FMJ_F64_LANES) ov[i] = (float)QV[i];
+    }
+    if (A.qacc) for (int i = lane; i < nv; i += FMJ_F64_LANES) A.qacc[(size_t)env * nv + i] = (float)XA[i];
+    if (A.time && lane == 0 && A.integrate) A.time[env] = (float)((double)A.time[env] + h * steps_done);
+  }
+  const int w = wg_or(warn, FLG + 6);
+  if (w != 0 && lane == 0) A.status[env] |= w;
+}
+
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64(void) { return (void*)fmj_step_f64_kernel; }
+#endif  // FMJ_TU_F64

@@ -215,6 +215,7 @@ enum StepPath {
   PATH_TWO_ENV,         // integrating steps: two envs per wave (fmj_dual2.inc); fmj_forward: the one-env kernel
   PATH_CONS2_ONE_ENV,   // integrating steps: the two-env constraint kernel (fmj_cons2.inc), then the one-env kernel for the envs it hands over
   PATH_TWO_WAVE,        // one workgroup of two waves per env (fmj_wide.inc), fmj_forward included: nbody or nv above 64, or FMJ_WIDE=1
+  PATH_F64,             // the fp64 step kernel (fmj_f64.inc), fmj_forward included: fmj_create_ex with FMJ_PRECISION_F64
 };
 
 struct fmj_ctx {
@@ -240,6 +241,8 @@ struct fmj_ctx {
   int ngeom = 0, n_contact_rows = 0, n_pairs = 0; std::vector<int> geom_sensor, geom_is_plane; int* d_geom_sensor = nullptr; int* d_pairs = nullptr;
   int* d_links_body = nullptr; int* d_joints_dof = nullptr;      // row -> body / dof maps of the standalone readout operator
   std::vector<float4> h_atab; std::vector<int> a_src;   // actuator table mirror (fmj_set_actuator_forcerange)
+  int precision = FMJ_PRECISION_F32;
+  struct F64Host* f64 = nullptr;         // fp64 contexts only: the fp64 model tables and the kernel's arguments (fmj_f64.inc)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1999,16 +2002,19 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 #include "fmj_dual2.inc"
 #include "fmj_cons2.inc"
 #include "fmj_wide.inc"
+#include "fmj_f64.inc"
 
 // ---------------------------------------------------------------------------------------------
 // Build layout: this file is compiled once per register row length with -DFMJ_TU_MAXD=<4..64> (only the step-kernel
 // instantiations of that MAXD and a getter for their host stubs), once per row length of the two-wave kernel with
-// -DFMJ_TU_WIDE=<32|64>, and once without either (standalone operators and all host code), in parallel, and the objects are
+// -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64 (kernel and getter: fmj_f64.inc), and once without any of
+// them (standalone operators and all host code), in parallel, and the objects are
 // linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
 
 #define FMJ_CAT2(a, b) a##b
 #define FMJ_CAT(a, b) FMJ_CAT2(a, b)
-#if defined(FMJ_TU_WIDE)
+#if defined(FMJ_TU_F64)
+#elif defined(FMJ_TU_WIDE)
 extern "C" __attribute__((visibility("hidden"))) void* FMJ_CAT(fmj_tu_wide_, FMJ_TU_WIDE)(int fused) {
   return fused ? (void*)fmj_step_wide_kernel<true, FMJ_TU_WIDE> : (void*)fmj_step_wide_kernel<false, FMJ_TU_WIDE>;
 }
@@ -2296,6 +2302,7 @@ void* fmj_tu_kernel_20(int, int); void* fmj_tu_kernel_24(int, int); void* fmj_tu
 void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu_kernel_44(int, int); void* fmj_tu_kernel_48(int, int);
 void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
+void* fmj_tu_f64(void);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -2309,9 +2316,24 @@ static int launch(const char* what, step_kernel_t k, int blocks, int threads, si
   return FMJ_OK;
 }
 
+// the fp64 model of an fp64 context: the kernel's argument and host mirrors of the tables that change after fmj_create
+struct F64Host {
+  F64Model fm = {};
+  size_t lds_bytes = 0;
+  std::vector<double> h_ad;      // actuator table mirror (fmj_set_actuator_forcerange)
+  std::vector<int> h_asrc;
+};
+
 static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream) {
   const DevModel& D = c->dm;
   const int pairs = (c->n_envs + 1) / 2;
+  if (c->path == PATH_F64) {
+    if (fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: an fp64 context steps through fmj_step; write the rows with fmj_before_step");
+    typedef void (*f64_kernel_t)(const F64Model, const StepArgs);
+    hipLaunchKernelGGL((f64_kernel_t)fmj_tu_f64(), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream, c->f64->fm, A);
+    if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string("fp64 step kernel launch: ") + hipGetErrorString(e));
+    return FMJ_OK;
+  }
   if (c->path == PATH_TWO_WAVE) return launch("two-wave step kernel", wide_kernel(D.rs, fused), c->n_envs, 128, c->lds_bytes_wide, stream, D, A);
   if (c->path == PATH_TWO_ENV && A.integrate) {      // the build registered for the batch's waves per SIMD, or the one with the rare options
     static const StepVariant dual[2][3] = {{SV_DUAL_W2, SV_DUAL_W3, SV_DUAL_W4}, {SV_DUAL_W2_RARE, SV_DUAL_W3_RARE, SV_DUAL_W4_RARE}};
@@ -2363,7 +2385,7 @@ struct ModelFacts {
   int max_contacts = 0, maxefc = 0;
 };
 
-static int check_model(const fmj_model* m, ModelFacts* F) {
+static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   if (m->abi_version != FMJ_ABI_VERSION) return set_err(FMJ_ERR_ARG, "fmj_create: abi_version mismatch");
   const int nb = m->nbody, nv = m->nv, nq = m->nq, nu = m->nu, nj = m->njnt;
   if (nb < 2 || nb > 128 || nv < 1 || nv > 128) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: need 2 <= nbody <= 128 and 1 <= nv <= 128 (two wavefronts per environment at most)");
@@ -2409,6 +2431,11 @@ static int check_model(const fmj_model* m, ModelFacts* F) {
     if (m->geom_bodyid[g1] == m->geom_bodyid[g2]) return set_err(FMJ_ERR_ARG, "fmj_create: a contact pair joins geoms of two bodies");
   }
   const int cons = any_limit || (nplane > 0 && m->ngeom > nplane) || m->npair > 0;
+  if (precision == FMJ_PRECISION_F64) {      // the fp64 step kernel (fmj_f64.inc) is the unconstrained Euler / implicitfast step
+    if (cons) return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex: the fp64 step has no constraint solver: the model has ") +
+                             (any_limit ? "joint limits" : m->npair > 0 ? "explicit contact pairs" : "contact geoms"));
+    if (m->integrator == FMJ_INT_RK4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
+  }
   if (big && cons) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: nbody or nv above 64 with limits, contacts or pairs (one wavefront per environment on the constraint path)");
   if (cons && m->solver != FMJ_SOLVER_PGS && m->solver != FMJ_SOLVER_NEWTON && m->solver != FMJ_SOLVER_CG) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: solver must be FMJ_SOLVER_PGS, FMJ_SOLVER_CG or FMJ_SOLVER_NEWTON");
   if (cons && m->cone != FMJ_CONE_PYRAMIDAL && m->cone != FMJ_CONE_ELLIPTIC) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: cone must be FMJ_CONE_PYRAMIDAL or FMJ_CONE_ELLIPTIC");
@@ -2493,7 +2520,7 @@ static int check_model(const fmj_model* m, ModelFacts* F) {
   F->rs = r4(max_ddepth + 1);
   // FMJ_WIDE=1: the two-wave kernel on any unconstrained model (tests hold it against the one-wave kernel; scripts measure the second wave)
   const char* wenv = getenv("FMJ_WIDE");
-  F->wide = big || (!cons && m->integrator != FMJ_INT_RK4 && wenv && wenv[0] == '1');
+  F->wide = precision == FMJ_PRECISION_F32 && (big || (!cons && m->integrator != FMJ_INT_RK4 && wenv && wenv[0] == '1'));
   if (F->wide) F->rs = F->rs <= 32 ? 32 : 64;     // the row lengths the two-wave kernel is instantiated at
   F->max_contacts = cons ? (m->max_contacts > 0 ? m->max_contacts : 1) : 0;
   int nlimj = 0; for (int j = 0; j < nj; j++) nlimj += (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE);
@@ -2911,11 +2938,87 @@ static int choose_path(fmj_ctx* c, const ModelFacts& F) {
   }
   c->path = F.wide ? PATH_TWO_WAVE : D.dual_ok ? PATH_TWO_ENV : D.cons2_ok ? PATH_CONS2_ONE_ENV : PATH_ONE_ENV;
   c->variant = one_env_variant(D);
-  if (c->path != PATH_TWO_WAVE && c->lds_bytes > 64 * 1024) {
+  if (c->path != PATH_TWO_WAVE && c->precision == FMJ_PRECISION_F32 && c->lds_bytes > 64 * 1024) {      // (an fp64 context launches none of these)
     hipError_t e1 = hipFuncSetAttribute((const void*)step_kernel(D.rs, true, c->variant), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     hipError_t e2 = hipFuncSetAttribute((const void*)step_kernel(D.rs, false, c->variant), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds_bytes);
     if (e1 != hipSuccess || e2 != hipSuccess) return set_err(FMJ_ERR_HIP, "fmj_create: LDS request too large");
   }
+  return FMJ_OK;
+}
+
+// ---- stage 8, fp64 contexts only: the fp64 model tables of the fp64 step kernel (fmj_f64.inc), its rounds and its LDS
+template <class T>
+static int upload_f64(fmj_ctx* c, const std::vector<T>& h, const T** dptr) { return upload(c, h, dptr); }
+static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  const int nb = m->nbody, nv = m->nv, nu = m->nu, nj = m->njnt;
+  c->f64 = new F64Host();
+  F64Host& H = *c->f64;
+  F64Model& M = H.fm;
+  const DevModel& D = c->dm;
+  M.nbody = nb; M.nv = nv; M.nq = m->nq; M.nu = nu; M.rs = r4(F.max_ddepth + 1); M.jump_rounds = F.jump_rounds; M.anc_stride = F.anc_stride;
+  M.root_free = D.root_free; M.any_stiffness = D.any_stiffness; M.implicitfast = D.implicitfast; M.nsensordata = D.nsensordata; M.njs = D.njs;
+  M.maxdep = F.max_ddepth;
+  M.h = m->timestep; M.gx = m->gravity[0]; M.gy = m->gravity[1]; M.gz = m->gravity[2];
+  std::vector<double> smass(nb, 0.0);      // subtree masses, summed children-first as mj_comPos does
+  for (int i = 1; i < nb; i++) smass[i] = m->body_mass[i];
+  for (int i = nb - 1; i >= 2; i--) smass[m->body_parentid[i]] += smass[i];
+  M.mtot = smass[1];
+  std::vector<double> bd((size_t)nb * F64_BD, 0.0), dd((size_t)nv * 2, 0.0), ad;
+  std::vector<int> bi((size_t)nb * F64_BI, 0), di((size_t)nv * F64_DI, 0), asrc;
+  for (int i = 0; i < nb; i++) { double* t = &bd[(size_t)i * F64_BD]; t[4] = 1.0; t[12] = 1.0; t[22] = 1.0; bi[(size_t)i * F64_BI + 1] = -1; bi[(size_t)i * F64_BI + 4] = 1; }
+  for (int i = 1; i < nb; i++) {
+    double* t = &bd[(size_t)i * F64_BD]; int* ti = &bi[(size_t)i * F64_BI];
+    for (int k = 0; k < 3; k++) { t[k] = m->body_pos[3 * i + k]; t[8 + k] = m->body_ipos[3 * i + k]; t[16 + k] = m->body_inertia[3 * i + k]; }
+    for (int k = 0; k < 4; k++) { t[4 + k] = m->body_quat[4 * i + k]; t[12 + k] = m->body_iquat[4 * i + k]; }
+    t[3] = m->body_mass[i]; t[11] = smass[i];
+    ti[0] = m->body_parentid[i]; ti[4] = F.subsize[i];
+    const int j = m->body_jntadr[i];
+    if (j >= 0) {
+      const bool fr = m->jnt_type[j] == FMJ_JNT_FREE;
+      for (int k = 0; k < 3; k++) { t[20 + k] = m->jnt_axis[3 * j + k]; t[24 + k] = m->jnt_pos[3 * j + k]; }
+      t[23] = fr ? 0.0 : m->qpos0[m->jnt_qposadr[j]]; t[27] = fr ? 0.0 : m->jnt_stiffness[j];
+      ti[1] = m->jnt_type[j]; ti[2] = m->jnt_qposadr[j]; ti[3] = m->jnt_dofadr[j];
+    }
+  }
+  int sj = 0;
+  for (int j = 0; j < nj; j++) {
+    const int d0 = m->jnt_dofadr[j], nd = m->jnt_type[j] == FMJ_JNT_FREE ? 6 : 1;
+    for (int k = 0; k < nd; k++) {
+      int* t = &di[(size_t)(d0 + k) * F64_DI];
+      t[0] = m->jnt_bodyid[j]; t[1] = F.ddepth[d0 + k]; t[2] = -1;
+      dd[2 * (d0 + k)] = m->dof_armature[d0 + k]; dd[2 * (d0 + k) + 1] = m->dof_damping[d0 + k];
+    }
+    if (nd == 6) continue;
+    int* t = &di[(size_t)d0 * F64_DI];
+    t[2] = m->jnt_qposadr[j]; t[3] = (int)asrc.size(); t[5] = sj++;
+    for (int a = 0; a < nu; a++) if (m->actuator_jntid[a] == j) {
+      const double inf = INFINITY;
+      const double row[F64_AD] = {m->actuator_gain[a], m->actuator_bias[3 * a], m->actuator_bias[3 * a + 1], m->actuator_bias[3 * a + 2],
+                                  m->actuator_ctrllimited[a] ? m->actuator_ctrlrange[2 * a] : -inf, m->actuator_ctrllimited[a] ? m->actuator_ctrlrange[2 * a + 1] : inf,
+                                  m->actuator_forcelimited[a] ? m->actuator_forcerange[2 * a] : -inf, m->actuator_forcelimited[a] ? m->actuator_forcerange[2 * a + 1] : inf};
+      ad.insert(ad.end(), row, row + F64_AD); asrc.push_back(a); t[4]++;
+    }
+  }
+  std::vector<uint8_t> danc((size_t)nv * M.rs, 0);
+  for (int i = 0; i < nv; i++) {
+    for (int l = 0; l < M.rs; l++) danc[(size_t)i * M.rs + l] = (uint8_t)i;
+    for (int a = m->dof_parentid[i]; a >= 0; a = m->dof_parentid[a]) danc[(size_t)i * M.rs + F.ddepth[a]] = (uint8_t)a;
+  }
+  std::vector<WideRoundW> rw;
+  const std::vector<LaneMask> anc = ancestor_masks(m, 0);
+  for (const DepthRound& g : depth_rounds(F.ddepth, 0, 6)) if (g.depth > 0) rw.push_back(round6<WideRoundW>(g, anc));      // a root dof has no ancestor to update
+  M.nround = (int)rw.size();
+  H.h_ad = ad; H.h_asrc = asrc;
+  int rc;
+  if ((rc = upload_f64(c, bd, &M.bd)) || (rc = upload_f64(c, bi, &M.bi)) || (rc = upload_f64(c, dd, &M.dd)) || (rc = upload_f64(c, di, &M.di)) ||
+      (rc = upload_f64(c, ad, &M.ad)) || (rc = upload_f64(c, asrc, &M.asrc)) || (rc = upload_f64(c, danc, &M.danc)) || (rc = upload_f64(c, rw, &M.rounds)))
+    return rc;
+  M.b_anc = D.b_anc;
+  H.lds_bytes = (size_t)ldsd_layout(nb, nv, m->nq, M.rs).total_bytes;
+  if (H.lds_bytes > 160 * 1024) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: fp64 step kernel LDS above 160 KB");     // (cannot happen within the size limits)
+  if (hipFuncSetAttribute((const void*)fmj_tu_f64(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
+    return set_err(FMJ_ERR_HIP, "fmj_create_ex: LDS request of the fp64 step kernel too large");
+  c->path = PATH_F64;
   return FMJ_OK;
 }
 
@@ -2928,24 +3031,32 @@ void fmj_destroy(fmj_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   for (void* p : c->allocs) (void)hipFree(p);
+  delete c->f64;
   delete c;
 }
 
-int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out) {
+int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out) { return fmj_create_ex(m, n_envs, device, nullptr, out); }
+
+int fmj_precision(const fmj_ctx* c) { return c ? c->precision : FMJ_PRECISION_F32; }
+
+int fmj_create_ex(const fmj_model* m, int32_t n_envs, int32_t device, const fmj_create_options* opts, fmj_ctx** out) {
   if (!m || !out || n_envs <= 0) return set_err(FMJ_ERR_ARG, "fmj_create: NULL model/out or n_envs <= 0");
   *out = nullptr;
+  if (opts && opts->size != (int32_t)sizeof(fmj_create_options)) return set_err(FMJ_ERR_ARG, "fmj_create_ex: fmj_create_options.size is not sizeof(fmj_create_options)");
+  const int precision = opts ? opts->precision : FMJ_PRECISION_F32;
+  if (precision != FMJ_PRECISION_F32 && precision != FMJ_PRECISION_F64) return set_err(FMJ_ERR_ARG, "fmj_create_ex: precision must be FMJ_PRECISION_F32 or FMJ_PRECISION_F64");
   ModelFacts F;
-  if (int rc = check_model(m, &F)) return rc;
+  if (int rc = check_model(m, &F, precision)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_err(FMJ_ERR_NODEVICE, "fmj_create: no HIP device visible");
   if (device < 0 || device >= ndev) return set_err(FMJ_ERR_ARG, "fmj_create: bad device ordinal");
   HIP_TRY(hipSetDevice(device));
   std::unique_ptr<fmj_ctx, void (*)(fmj_ctx*)> c(new fmj_ctx(), fmj_destroy);     // a failing stage leaves through here: fmj_destroy frees its allocations
-  c->device = device; c->n_envs = n_envs;
+  c->device = device; c->n_envs = n_envs; c->precision = precision;
   describe_model(c.get(), m, F);
   int rc;
   if ((rc = pack_body_dof_tables(c.get(), m, F)) || (rc = pack_geom_tables(c.get(), m, F)) || (rc = upload_rounds(c.get(), m, F)) ||
-      (rc = alloc_scratch(c.get())) || (rc = choose_path(c.get(), F)))
+      (rc = alloc_scratch(c.get())) || (rc = choose_path(c.get(), F)) || (precision == FMJ_PRECISION_F64 && (rc = build_f64(c.get(), m, F))))
     return rc;
   *out = c.release();
   return FMJ_OK;
@@ -2959,8 +3070,8 @@ int fmj_get_sensor_layout(const fmj_ctx* c, fmj_sensor_layout_t* out) {
 int fmj_kernel_info(const fmj_ctx* c, int32_t* lds_bytes_per_env, int32_t* threads_per_env) {
   if (!c) return set_err(FMJ_ERR_ARG, "fmj_kernel_info: NULL ctx");
   // by StepPath: the integrating step packs two envs per wave when it can
-  const size_t lds[4] = {c->lds_bytes, c->lds_bytes_dual2 / 2, c->lds_bytes_cons2 / 2, c->lds_bytes_wide};
-  const int threads[4] = {64, 32, 32, 128};
+  const size_t lds[5] = {c->lds_bytes, c->lds_bytes_dual2 / 2, c->lds_bytes_cons2 / 2, c->lds_bytes_wide, c->f64 ? c->f64->lds_bytes : 0};
+  const int threads[5] = {64, 32, 32, 128, FMJ_F64_LANES};
   if (lds_bytes_per_env) *lds_bytes_per_env = (int32_t)lds[c->path];
   if (threads_per_env) *threads_per_env = threads[c->path];
   return FMJ_OK;
@@ -3012,6 +3123,15 @@ int fmj_set_actuator_forcerange(fmj_ctx* c, int32_t nu, const int32_t* forcelimi
   // copy below would not wait for.  Drain the device first (this is a set-up call, task.py:253-286 runs it once).
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy((void*)c->dm.atab, c->h_atab.data(), c->h_atab.size() * sizeof(float4), hipMemcpyHostToDevice));
+  if (c->f64 && !c->f64->h_asrc.empty()) {      // the fp64 table of an fp64 context, from the unrounded values
+    F64Host& H = *c->f64;
+    for (size_t a = 0; a < H.h_asrc.size(); a++) {
+      const int src = H.h_asrc[a];
+      H.h_ad[a * F64_AD + 6] = forcelimited[src] ? forcerange[2 * src] : -INFINITY;
+      H.h_ad[a * F64_AD + 7] = forcelimited[src] ? forcerange[2 * src + 1] : INFINITY;
+    }
+    HIP_TRY(hipMemcpy((void*)H.fm.ad, H.h_ad.data(), H.h_ad.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
   return FMJ_OK;
 }
 
@@ -3105,7 +3225,7 @@ int fmj_forward_debug(fmj_ctx* c, const fmj_data* d, int32_t disable_actuation, 
   StepArgs A; int rc = fill_data(c, d, &A, true); if (rc) return rc;
   if (c->dm.any_stiffness && !d->qpos_spring) return set_err(FMJ_ERR_ARG, "fmj_forward_debug: qpos_spring required (model has joint stiffness)");
   A.n_steps = 1; A.integrate = 0; A.disable_actuation = disable_actuation; A.dbg_H = H_rows; A.dbg_qfrc = qfrc_smooth;
-  if (row_stride) *row_stride = c->dm.rs;
+  if (row_stride) *row_stride = c->f64 ? c->f64->fm.rs : c->dm.rs;
   HIP_TRY(hipSetDevice(c->device));
   return launch_step(c, false, A, stream);
 }
@@ -3141,6 +3261,7 @@ int fmj_step_fused(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, void*
   StepArgs A; int rc = fill_data(c, d, &A, true); if (rc) return rc;
   if (a->n_steps < 0 || a->buffer_size < 1) return set_err(FMJ_ERR_ARG, "fmj_step_fused: bad n_steps/buffer_size");
   if (c->rk4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: the RK4 integrator steps through fmj_step (four forward launches per step); write the rows with fmj_before_step");
+  if (c->precision == FMJ_PRECISION_F64) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: an fp64 context steps through fmj_step (the fp64 step kernel has no fused loop); write the rows with fmj_before_step");
   if (c->dm.any_stiffness && !d->qpos_spring) return set_err(FMJ_ERR_ARG, "fmj_step_fused: qpos_spring required");
   if (a->do_readout && (!a->rows_base.links || !a->rows_base.joints)) return set_err(FMJ_ERR_ARG, "fmj_step_fused: readout needs links and joints rows");
   if (a->do_drag && (!a->rows_base.xfrc || c->dm.ns == 0)) return set_err(FMJ_ERR_ARG, "fmj_step_fused: drag needs xfrc rows and fmj_set_swimming");

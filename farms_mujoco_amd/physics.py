@@ -42,7 +42,11 @@ class _MjData(SimpleNamespace):
 class BatchedPhysics:
     """Device-resident mjData for ``n_envs`` copies of one model + the HIP step context."""
 
-    def __init__(self, model: Model, n_envs: int, device='cuda:0'):
+    def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32'):
+        # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
+        # tensors of physics.data stay fp32
+        if precision not in _lib.PRECISIONS:
+            raise ValueError(f'precision must be one of {sorted(_lib.PRECISIONS)}, not {precision!r}')
         if not torch.cuda.is_available():
             raise _lib.FmjError('BatchedPhysics needs a GPU (torch.cuda.is_available() is False); '
                                 'there is no CPU fallback for the product path.')
@@ -52,9 +56,18 @@ class BatchedPhysics:
         self._lib = _lib.load()
         self._cmodel = model.as_c()
         ctx = ctypes.c_void_p()
-        _lib.check(self._lib.fmj_create(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
-                                        ctypes.byref(ctx)))
+        if precision == 'fp32':
+            _lib.check(self._lib.fmj_create(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
+                                            ctypes.byref(ctx)))
+        else:
+            if not (hasattr(self._lib, 'fmj_create_ex') and self._lib.fmj_create_ex.argtypes):      # an A/B base build (FMJ_SO)
+                raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex: precision=%r needs a current build' % precision)
+            opts = _lib.CCreateOptions(ctypes.sizeof(_lib.CCreateOptions), _lib.PRECISIONS[precision])
+            _lib.check(self._lib.fmj_create_ex(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
+                                               ctypes.byref(opts), ctypes.byref(ctx)))
         self._ctx = ctx
+        code = self._lib.fmj_precision(self._ctx) if hasattr(self._lib, 'fmj_precision') and self._lib.fmj_precision.argtypes else 0
+        self.precision = {v: k for k, v in _lib.PRECISIONS.items()}[code]      # what the context reports
         lay = _lib.CSensorLayout()
         _lib.check(self._lib.fmj_get_sensor_layout(self._ctx, ctypes.byref(lay)))
         self.sensor_layout = lay

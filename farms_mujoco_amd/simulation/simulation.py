@@ -26,7 +26,8 @@ class Simulation:
     """Batched simulation with the reference's API shape (reference simulation.py:33-213).
 
     ``mjcf_model`` is a compiled :class:`~farms_mujoco_amd.model.Model` (the dm_control MJCF element tree is
-    replaced).  Extra kwargs: ``n_envs``, ``device``.  ``legacy_step`` is accepted for signature
+    replaced).  Extra kwargs: ``n_envs``, ``device``, ``precision`` ('fp32' | 'fp64': the step kernel's arithmetic,
+    :class:`~farms_mujoco_amd.physics.BatchedPhysics`).  ``legacy_step`` is accepted for signature
     compatibility; the step is always the full mj_step (legacy_step=False semantics, simulation.py:36-37).
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here
     advances exactly ``n_iterations * substeps`` physics steps after an explicit :meth:`reset`.
@@ -41,7 +42,7 @@ class Simulation:
         self.pause = not self.options.play
         n_envs = kwargs.pop('n_envs', 1)
         device = kwargs.pop('device', 'cuda:0')
-        self.physics = BatchedPhysics(mjcf_model, n_envs, device)
+        self.physics = BatchedPhysics(mjcf_model, n_envs, device, precision=kwargs.pop('precision', 'fp32'))
         self.handle_exceptions = kwargs.pop('handle_exceptions', False)
         # dm_control raises PhysicsError inside the offending step; here the device freezes the offending env at that
         # step (include/fmj.h) and the host looks at the status words every `check_every` steps (one sync each)
@@ -51,8 +52,9 @@ class Simulation:
         self.task = ExperimentTask(base_link=base_link, n_iterations=self.options.n_iterations,
                                    timestep=self.options.timestep, units=self.options.units,
                                    substeps=self.options.num_sub_steps, **kwargs)
-        # RK4 (four forward launches per step, fmj_step): no fused launch, the controller is evaluated on the host path (task.step_control)
-        self.task.host_step_only = self.physics.rk4
+        # RK4 (four forward launches per step, fmj_step) and the fp64 step kernel: no fused launch, the controller is evaluated on the
+        # host path (task.step_control)
+        self.task.host_step_only = self.physics.rk4 or self.physics.precision == 'fp64'
         self._needs_reset = True
 
     @property
@@ -154,7 +156,7 @@ class Simulation:
         """Run ``n_steps`` full iterations (``substeps`` physics steps each) inside ONE launch (fmj_step_fused): ring-buffer
         readout, drag, xfrc glue, controller and mj_step, with state resident in LDS/registers between steps."""
         task, phys = self.task, self.physics
-        assert task.fusable()
+        assert task.fusable() or phys.precision == 'fp64'      # (an fp64 context: fmj_step_fused refuses, FmjError)
         assert task.sim_iteration % task.substeps == 0, 'a fused launch starts on a full step'
         n_steps = min(n_steps, task.n_iterations - task.sim_iteration//task.substeps)
         if n_steps <= 0:

@@ -294,12 +294,31 @@ typedef struct fmj_ctx fmj_ctx;   /* opaque */
  * are FMJ_ERR_UNSUPPORTED with the limit named in fmj_last_error().  FMJ_WIDE=1 in the environment at fmj_create runs the
  * two-wave kernel on any unconstrained, non-RK4 model (to compare it with the one-wave kernels). */
 int fmj_create(const fmj_model* model, int32_t n_envs, int32_t device, fmj_ctx** out);
+/* fmj_create with options (additive: FMJ_ABI_VERSION stays 6).  opts == NULL is fmj_create: the same path, the same bits.
+ * precision = FMJ_PRECISION_F64 selects the fp64 step kernel: every stage of the unconstrained step in double precision, from a second,
+ * fp64 copy of the model constants that only such a context uploads (one workgroup of 128 threads per environment, nbody and nv up to
+ * 128, dof chain up to 64).  fmj_model and fmj_data do not change: the per-env buffers stay fp32, the kernel widens them on load and
+ * rounds once on store; a launch of n_steps keeps the state in double between its steps.  What this buys is the accuracy of long
+ * chains of light links, whose joint-space inertia is too ill-conditioned for fp32 ("Accuracy of long chains").
+ * An fp64 context covers fmj_step (any n_steps, ctrl tape), fmj_forward (disable_actuation included) and fmj_forward_debug (H_rows /
+ * qfrc_smooth rounded to fp32 on store), with the Euler and implicitfast integrators.  Refused with FMJ_ERR_UNSUPPORTED and a message
+ * containing "fp64": a model with limits, contacts or pairs, the RK4 integrator (both at fmj_create_ex, before the device lookup) and
+ * fmj_step_fused (write the rows with fmj_before_step, as with RK4).  The standalone operators (fmj_before_step, fmj_physics2data,
+ * fmj_drag, fmj_contacts2data) work unchanged, in fp32, from the fmj_data fields.  An unknown precision or a size other than
+ * sizeof(fmj_create_options) is FMJ_ERR_ARG. */
+enum { FMJ_PRECISION_F32 = 0, FMJ_PRECISION_F64 = 1 };
+typedef struct fmj_create_options {
+  int32_t size;        /* = sizeof(fmj_create_options), for later growth */
+  int32_t precision;   /* FMJ_PRECISION_* */
+} fmj_create_options;
+int fmj_create_ex(const fmj_model* model, int32_t n_envs, int32_t device, const fmj_create_options* opts, fmj_ctx** out);
+int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
 void fmj_destroy(fmj_ctx* ctx);
 const char* fmj_last_error(void);
 int fmj_abi_version(void);
 int fmj_get_sensor_layout(const fmj_ctx* ctx, fmj_sensor_layout_t* out);
 /* LDS bytes / VGPR-independent facts the host needs for reporting; threads_per_env is 32 (two envs per wave), 64 (one wave) or
- * 128 (two waves: models past 64 bodies / dofs, or FMJ_WIDE=1) */
+ * 128 (two waves: models past 64 bodies / dofs, or FMJ_WIDE=1; always for an fp64 context, whose LDS holds the rows of H as doubles) */
 int fmj_kernel_info(const fmj_ctx* ctx, int32_t* lds_bytes_per_env, int32_t* threads_per_env);
 
 /* ---- swimming links (SwimmingHandler.__init__, reference drag.pyx:333-387) ------------------
