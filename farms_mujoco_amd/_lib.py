@@ -89,6 +89,7 @@ SYMBOLS = {
     'fmj_abi_version': (ctypes.c_int, []),
     'fmj_get_sensor_layout': (ctypes.c_int, [_VP, ctypes.POINTER(CSensorLayout)]),
     'fmj_kernel_info': (ctypes.c_int, [_VP, _I, _I]),
+    'fmj_dual_build_info': (ctypes.c_int, [_VP, _I, _I, _I]),
     'fmj_set_swimming': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, _I, _I, _I, _D, _D, _D, _D]),
     'fmj_set_actuator_forcerange': (ctypes.c_int, [_VP, ctypes.c_int32, _I, _D]),
     'fmj_drag_link': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _VP, ctypes.c_int64, _VP, ctypes.c_int64, _D,
@@ -198,7 +199,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
     return target
 
 
-OPTIONAL_IN_AB_BASE = ('fmj_solver_info', 'fmj_create_ex', 'fmj_precision')      # queries only (physics.py tolerates their absence under FMJ_SO)
+OPTIONAL_IN_AB_BASE = ('fmj_solver_info', 'fmj_create_ex', 'fmj_precision', 'fmj_dual_build_info')      # queries only (physics.py tolerates their absence under FMJ_SO)
 
 
 def load():

@@ -135,8 +135,15 @@ __device__ __forceinline__ bool drag_same_frames2(v3 com_pos, q4 q_wxyz, v3 lin_
 // sub-steps) 1.7 % when it was decided at run time (same-box A/B, round 4).  The same instantiation carries the other rarely used
 // option, the implicitfast integrator (one compare pair per actuator and one more live register: 1.4 % of the headline when every
 // build had it), so a launch with substeps = 1 of an implicitfast model also runs it.
-template <bool FUSED, int MAXD, int WPS, bool SUBS = false>
+// LEAN: the launch has the shape of a fused Simulation.run() with the device wave controller - rows written by the launch itself
+// (no rows_ahead), readout and drag on, controller 1, actuation enabled, integrating, no joint stiffness, none of the SUBS options -
+// which launch_step checks on the host before it picks this instantiation.  Every OPT_* below is then a constant instead of a scalar
+// load through the laundered argument pointer plus a compare and a branch inside each step (the rows_ahead tests alone were 0.8 % of
+// the headline, round 5), and the tail pass and the xfrc_applied hand-over of rows_ahead are not compiled.  The arithmetic is the
+// generic build's: the two are bitwise equal on the same launch (tests/test_gpu_dual2_lean.py).
+template <bool FUSED, int MAXD, int WPS, bool SUBS = false, bool LEAN = false>
 __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel M_by_value, const StepArgs A_by_value) {
+  static_assert(!LEAN || (FUSED && !SUBS), "the lean build is a fused launch without the rare options");
   extern __shared__ __align__(16) float lds[];
   // the two arguments, addressed in the kernarg segment instead of being held in SGPRs
   const char AS4* const karg = (const char AS4*)__builtin_amdgcn_kernarg_segment_ptr();
@@ -148,6 +155,15 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
 #define DT2(d, k) ldg4(M.dtab, (unsigned)(d) * DT_STRIDE + (k))
 #define AT2(a, k) ldg4(M.atab, (unsigned)(a) * AT_STRIDE + (k))
 #define ST2(i, k) ldg4(M.stab, (unsigned)(i) * ST_STRIDE + (k))
+  // launch options that never change during a launch: read where they are used, constants in the LEAN build
+#define OPT_ROWS_AHEAD (!LEAN && A.rows_ahead)
+#define OPT_READOUT (LEAN || A.do_readout)
+#define OPT_DRAG (LEAN || A.do_drag)
+#define OPT_CONTROLLER (LEAN ? 1 : (FUSED ? A.controller : 0))
+#define OPT_TAPE (LEAN ? (const float*)nullptr : A.ctrl)
+#define OPT_NO_ACT (!LEAN && A.disable_actuation != 0)
+#define OPT_STIFFNESS (!LEAN && M.any_stiffness)
+#define OPT_INTEGRATE (LEAN || A.integrate)
   const int lane = threadIdx.x;
   const bool upper = lane >= 32;
   const int sl = lane & 31;
@@ -212,8 +228,8 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
   float4 a0_p = make_float4(0.f, 0.f, 0.f, 0.f), a0_lim = make_float4(0.f, 0.f, 0.f, 0.f); int a0_src = 0; float a0_amp = 0.f, a0_lag = 0.f;
   unsigned live_mask = 0;                                   // bit a: slot a of this lane is live
   {
-    const int controller = FUSED ? A.controller : 0;
-    const bool have_tape = A.ctrl != nullptr;
+    const int controller = OPT_CONTROLLER;
+    const bool have_tape = OPT_TAPE != nullptr;
 #pragma unroll
     for (int a = 3; a >= 0; a--) {
       if (a < act_n) {
@@ -246,7 +262,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
   // element offsets of the lane's link / xfrc / joint rows inside one ring row (the ring index adds a uniform multiple of the stride)
   const long long r_offl_ = (long long)env * M.n_links * FMJ_LINK_SIZE, r_offx_ = (long long)env * M.n_xfrc * FMJ_XFRC_SIZE,
                   r_offj_ = (long long)env * M.n_joints * FMJ_JOINT_SIZE;
-  const float r_wenv_ = (FUSED && A.controller == 1) ? gptr(A.w_env)[env] : 0.f;
+  const float r_wenv_ = (FUSED && OPT_CONTROLLER == 1) ? gptr(A.w_env)[env] : 0.f;
   // the env phase in revolutions, rounded once per launch in EVERY build (pinf keeps the product from being contracted into the
   // add of a step in the builds that would otherwise reload the phase there: the register builds must agree bitwise)
   const float r_wturn_ = pinf(0.15915494309189535f * r_wenv_);
@@ -258,7 +274,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
     const float im = A.inv_meters;
     const v3 r_com = scl3(xi, im), r_urdf = scl3(xp, im);
     const v3 r_lin = scl3(linvel, A.inv_velocity), r_ang = scl3(angvel, A.inv_angvel);
-    if (A.do_readout && isb && live && ci2.z >= 0) {      // quaternions: w,x,y,z -> x,y,z,w (physics.py:458)
+    if (OPT_READOUT && isb && live && ci2.z >= 0) {      // quaternions: w,x,y,z -> x,y,z,w (physics.py:458)
       float AS1* row = gptr(A.links) + ((size_t)index * A.row_stride_links + (RES2_ ? (size_t)r_offl_ : (size_t)env * M.n_links * FMJ_LINK_SIZE)) + ci2.z * FMJ_LINK_SIZE;
       stg4(row + 0, r_com.x, r_com.y, r_com.z, xq.x);
       stg4(row + 4, xq.y, xq.z, xq.w, r_urdf.x);
@@ -266,7 +282,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
       stg4(row + 12, xq.z, xq.w, r_lin.x, r_lin.y);
       stg4(row + 16, r_lin.z, r_ang.x, r_ang.y, r_ang.z);
     }
-    if (A.do_drag) {
+    if (OPT_DRAG) {
 #pragma unroll
       for (int k = 0; k < 6; k++) xf[k] = 0.f;
       if (isb && ci2.w >= 0) {
@@ -291,7 +307,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
   // were written by the launch before (its tail, below) or by fmj_before_step - and host callbacks may have edited xfrc_applied since -,
   // so nothing of them is written here and the drag force comes from xfrc_applied; in exchange the launch writes everything
   // before_step would write for the iteration AFTER its last step
-  const bool rows_ahead = FUSED && A.rows_ahead != 0;
+  const bool rows_ahead = FUSED && OPT_ROWS_AHEAD != 0;
   if (FUSED && !rows_ahead) {
     // the launch's first iteration logs the fields the previous launch (or the reset's mj_forward) left in mjData
     const float AS1* p = gptr(A.xpos) + (size_t)env * nb * 3 + bl * 3;
@@ -308,7 +324,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
       for (int a = 0; a < 4; a++) if (a < act_n) cy_actsum += sa[__float_as_int(AT2(d_act.x + a, 2).x)] * itq;
     }
   }
-  if ((!(FUSED && A.do_drag) || rows_ahead) && A.xfrc_applied && isb) {
+  if ((!(FUSED && OPT_DRAG) || rows_ahead) && A.xfrc_applied && isb) {
     const float AS1* x = gptr(A.xfrc_applied) + (size_t)env * nb * 6 + bl * 6;
 #pragma unroll
     for (int k = 0; k < 6; k++) xf[k] = x[k];
@@ -389,7 +405,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
     const float4 d_prm = RES ? r_dprm : DT2(mydof, 1);          // armature, damping, qposadr bits, hinge/slide flag
     const int d_qadr = __float_as_int(d_prm.z);
     const bool d_scalar = isd && d_prm.w != 0.f;
-    if (FUSED && A.do_readout && full && !(A.rows_ahead && step == 0)) {
+    if (FUSED && OPT_READOUT && full && !(OPT_ROWS_AHEAD && step == 0)) {
       if (d_scalar && live && jrow >= 0) {
         const int index = ring;
         float AS1* row = gptr(A.joints) + ((size_t)index * A.row_stride_joints + (RES2_ ? (size_t)r_offj_ : (size_t)env * M.n_joints * FMJ_JOINT_SIZE)) + jrow * FMJ_JOINT_SIZE;
@@ -401,7 +417,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
         stg4(row + 8, cy_actsum, 0.f, 0.f, 0.f);                            // motor torque, limit force
       }
     }
-    if (FUSED && A.rows_ahead && step == n_steps) break;        // the tail pass: the next iteration's rows are complete, nothing is stepped
+    if (FUSED && OPT_ROWS_AHEAD && step == n_steps) break;        // the tail pass: the next iteration's rows are complete, nothing is stepped
     // ============ mj_step ============
     const int4 c_info = as_int4(RES ? r_info : BT2(bl, 7));     // parent, jtype, qadr, dadr
     const int jtype = isb ? c_info.y : -1;
@@ -555,8 +571,8 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
     //      and its drag are emitted here, where the values are, instead of being carried to the next step through LDS
     {
       const v3 linvel = add3(cv.l, cross(cv.r, dcom));
-      if (FUSED && (!last || A.rows_ahead) && (nfull || (SUBS && A.sub_links && !(A.n_it_total > 0 && it + (nrow1 ? 1 : 0) >= A.n_it_total)))) emit_links_and_drag2(nrow1 ? ring_n1 : ring, xp, xq, xi, linvel, cv.r);   // a sub-step without a row keeps its drag force
-      if (FUSED && last && A.rows_ahead && A.do_drag && A.xfrc_applied_out && isb && live) {      // ... and the world-frame drag goes where the next launch (and the host callbacks before it) find it
+      if (FUSED && (!last || OPT_ROWS_AHEAD) && (nfull || (SUBS && A.sub_links && !(A.n_it_total > 0 && it + (nrow1 ? 1 : 0) >= A.n_it_total)))) emit_links_and_drag2(nrow1 ? ring_n1 : ring, xp, xq, xi, linvel, cv.r);   // a sub-step without a row keeps its drag force
+      if (FUSED && last && OPT_ROWS_AHEAD && OPT_DRAG && A.xfrc_applied_out && isb && live) {      // ... and the world-frame drag goes where the next launch (and the host callbacks before it) find it
         const int4 ci2x = as_int4(BT2(bl, 8));
         if (ci2x.w >= 0) {
           float AS1* xa = gptr(A.xfrc_applied_out) + (size_t)env * nb * 6 + bl * 6;
@@ -644,12 +660,12 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
       if (isd) qfrc = -d_prm.y * qd - s6dot(cd, lds_get6(F + dbody * D2S));
       if (d_scalar) {
         const float qj = QP[d_qadr];
-        if (M.any_stiffness) {
+        if (OPT_STIFFNESS) {
           const float kst = BT2(dbody, 6).w;
           if (kst != 0.f) qfrc -= kst * (qj - gptr(A.qpos_spring)[(size_t)env * nq + d_qadr]);
         }
         float asum = 0.f, cbase = 0.f, cturn = 0.f;
-        const int controller = FUSED ? A.controller : 0;
+        const int controller = OPT_CONTROLLER;
         if (controller == 1) {
           double cyc = (double)A.w_freq * ((double)it * ((double)M.h * (double)S_sub));   // task.py:290: time = iteration * timestep (of an iteration)
           cyc -= floor(cyc);
@@ -657,8 +673,8 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
           cbase = fmaf(6.283185307179586f, (float)cyc, wenv);
           cturn = (float)cyc + r_wturn_;                         // the same phase in revolutions
         }
-        const float AS1* ctrl_row = A.ctrl ? gptr(A.ctrl) + (size_t)itm * A.ctrl_step_stride + (size_t)env * nu : nullptr;      // one ctrl row per iteration
-        const bool no_act = A.disable_actuation != 0;
+        const float AS1* ctrl_row = OPT_TAPE ? gptr(A.ctrl) + (size_t)itm * A.ctrl_step_stride + (size_t)env * nu : nullptr;      // one ctrl row per iteration
+        const bool no_act = OPT_NO_ACT;
         if (first_live < 4) {                        // the resident slot
           float c;
           if (controller == 1) c = a0_amp != 0.f ? a0_amp * sin_turns(fmaf(-0.15915494309189535f, a0_lag, cturn)) : 0.f;
@@ -857,7 +873,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
     }
     STAMP(10);
     // ---- Euler
-    const float hstep = A.integrate ? M.h : 0.f;
+    const float hstep = OPT_INTEGRATE ? M.h : 0.f;
     const float pre_qd = QV[mydof];
     const float nvel = pre_qd + hstep * my_qacc;
     if (isd) {
@@ -887,7 +903,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
       // left them (include/fmj.h: freeze contract) - at no cost to the steps that pass
       const float nv0 = QV[0] + hstep * xt0, nv1 = QV[1] + hstep * xt1, nv2 = QV[2] + hstep * xt2;
       const float nx = QP[0] + hstep * nv0, ny = QP[1] + hstep * nv1, nz = QP[2] + hstep * nv2;
-      posbad = A.integrate && (!(fabsf(nx) <= 1e10f) || !(fabsf(ny) <= 1e10f) || !(fabsf(nz) <= 1e10f));
+      posbad = OPT_INTEGRATE && (!(fabsf(nx) <= 1e10f) || !(fabsf(ny) <= 1e10f) || !(fabsf(nz) <= 1e10f));
       if (posbad) warn |= FMJ_WARN_BADQPOS;
       else {
         XV[0] = xt0; XV[1] = xt1; XV[2] = xt2;
@@ -897,7 +913,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
     }
     if (!frozen) steps_done++;
     WSYNC();
-    if (T0 && sl == 1 && A.integrate && !frozen && !posbad) {      // orientation of the free root: needs the angular velocity the dof lanes just stored
+    if (T0 && sl == 1 && OPT_INTEGRATE && !frozen && !posbad) {      // orientation of the free root: needs the angular velocity the dof lanes just stored
       const float h = M.h;
       const v3 w = mk3(QV[3], QV[4], QV[5]);
       const float n2 = dot3(w, w), rn = rsqrt_nr(n2), n = n2 * rn;
@@ -944,4 +960,12 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
 #undef DT2
 #undef AT2
 #undef ST2
+#undef OPT_ROWS_AHEAD
+#undef OPT_READOUT
+#undef OPT_DRAG
+#undef OPT_CONTROLLER
+#undef OPT_TAPE
+#undef OPT_NO_ACT
+#undef OPT_STIFFNESS
+#undef OPT_INTEGRATE
 }

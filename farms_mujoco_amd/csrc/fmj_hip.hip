@@ -202,11 +202,13 @@ static_assert(alignof(DevModel) == 8 && alignof(StepArgs) == 8, "kernarg layout 
 
 // The step-kernel instantiations of one row length (fmj_tu_kernel_<rs>): the one-env kernel by what its constraint code covers
 // (fmj_step_kernel<.., CONS, PAIRS, NEWTON, MESH, ELL>), the two-env kernel (fmj_dual2.inc) by the waves per SIMD its registers are
-// budgeted for, without and with the rare options (sub-steps, implicitfast), and the two-env constraint kernel (fmj_cons2.inc).
+// budgeted for, without and with the rare options (sub-steps, implicitfast) and with the launch options of a fused run folded in
+// (LEAN, fmj_dual2.inc), and the two-env constraint kernel (fmj_cons2.inc).
 // ELL: the elliptic cone (+ meshes); PAIRS: explicit pairs (+ meshes); MESH: meshes without pairs.
 enum StepVariant {
   SV_PLAIN, SV_PGS, SV_PGS_PAIRS, SV_NEWTON, SV_PGS_MESH, SV_NEWTON_MESH, SV_NEWTON_ELL, SV_NEWTON_PAIRS, SV_PGS_ELL, SV_PGS_ELL_PAIRS,
   SV_DUAL_W2, SV_DUAL_W3, SV_DUAL_W4, SV_DUAL_W2_RARE, SV_DUAL_W3_RARE, SV_DUAL_W4_RARE, SV_CONS2,
+  SV_DUAL_W2_LEAN, SV_DUAL_W3_LEAN, SV_DUAL_W4_LEAN,      // fused launches only
 };
 
 // The kernels the step launches of a context run (fmj_create chooses, launch_step launches)
@@ -225,6 +227,8 @@ struct fmj_ctx {
   StepPath path = PATH_ONE_ENV;
   StepVariant variant = SV_PLAIN;        // of the one-env kernel
   int dual_wps = 4;           // waves per SIMD the dual2 build is registered for: 2, 3 or 4, the most the batch fills (FMJ_WPS overrides)
+  int dual_lean = 1;          // fused launches of the flagship shape run the LEAN dual2 build (FMJ_DUAL_LEAN=0: always the generic one)
+  int dual_last = FMJ_DUAL_BUILD_NONE;      // FMJ_DUAL_BUILD_* of the last dual2 launch (fmj_dual_build_info)
   size_t lds_bytes = 0, lds_bytes_dual2 = 0, lds_bytes_cons2 = 0, lds_bytes_wide = 0;
   int* d_resume = nullptr;    // [n_envs] hand-over of the two-env constraint kernel to the one-env kernel
   int rk4 = 0;                // integrator = RK4: fmj_step runs four forward launches per step (fmj_rk4_stage_kernel between them)
@@ -2025,7 +2029,7 @@ constexpr bool tu_builds([[maybe_unused]] StepVariant v, [[maybe_unused]] bool f
 #if FMJ_TU_MAXD > 32
   return v == SV_PLAIN;
 #elif defined(FMJ_DEV_DUAL2_ONLY)          // the fused two-env kernels
-  return fused && (v == SV_DUAL_W4 || v == SV_DUAL_W2 || v == SV_DUAL_W3);
+  return fused && (v == SV_DUAL_W4 || v == SV_DUAL_W2 || v == SV_DUAL_W3 || v == SV_DUAL_W4_LEAN || v == SV_DUAL_W2_LEAN || v == SV_DUAL_W3_LEAN);
 #elif defined(FMJ_DEV_CONS2_FUSED_ONLY)    // the fused two-env constraint kernel alone
   return fused && v == SV_CONS2;
 #elif defined(FMJ_DEV_PGSOPT_ONLY)         // the one-env constraint kernels of the PGS options (elliptic cone, noslip)
@@ -2042,6 +2046,8 @@ constexpr bool tu_builds([[maybe_unused]] StepVariant v, [[maybe_unused]] bool f
 #define FMJ_PICK(V, KT, KF) do { if (fused) { FMJ_OR_NULL(V, true, KT); } FMJ_OR_NULL(V, false, KF); } while (0)
 // the rare options (fused sub-steps, implicitfast): single steps run one register tier, they are launch-bound
 #define FMJ_PICK_RARE(V, KT) do { if (!fused) { FMJ_OR_NULL(V, false, (fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 4, true>)); } FMJ_OR_NULL(V, true, KT); } while (0)
+// the lean builds exist for fused launches alone
+#define FMJ_PICK_LEAN(V, KT) do { if (fused) { FMJ_OR_NULL(V, true, KT); } return nullptr; } while (0)
 #define FMJ_PICK_ONE(V, ...) FMJ_PICK(V, (fmj_step_kernel<true, FMJ_TU_MAXD, __VA_ARGS__>), (fmj_step_kernel<false, FMJ_TU_MAXD, __VA_ARGS__>))
 extern "C" __attribute__((visibility("hidden"))) void* FMJ_CAT(fmj_tu_kernel_, FMJ_TU_MAXD)(int fused, int variant) {
   switch ((StepVariant)variant) {
@@ -2052,6 +2058,9 @@ extern "C" __attribute__((visibility("hidden"))) void* FMJ_CAT(fmj_tu_kernel_, F
     case SV_DUAL_W4:       FMJ_PICK(SV_DUAL_W4, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 4>), (fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 4>));
     case SV_DUAL_W2:       FMJ_PICK(SV_DUAL_W2, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 2>), (fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 2>));
     case SV_DUAL_W3:       FMJ_PICK(SV_DUAL_W3, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 3>), (fmj_step_dual2_kernel<false, FMJ_TU_MAXD, 3>));
+    case SV_DUAL_W4_LEAN:  FMJ_PICK_LEAN(SV_DUAL_W4_LEAN, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 4, false, true>));
+    case SV_DUAL_W2_LEAN:  FMJ_PICK_LEAN(SV_DUAL_W2_LEAN, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 2, false, true>));
+    case SV_DUAL_W3_LEAN:  FMJ_PICK_LEAN(SV_DUAL_W3_LEAN, (fmj_step_dual2_kernel<true, FMJ_TU_MAXD, 3, false, true>));
     //                                                CONS  PAIRS  NEWTON MESH  ELL
     case SV_PGS_ELL_PAIRS: FMJ_PICK_ONE(SV_PGS_ELL_PAIRS, true, true,  false, true, true);
     case SV_PGS_ELL:       FMJ_PICK_ONE(SV_PGS_ELL,       true, false, false, true, true);
@@ -2336,9 +2345,14 @@ static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream) 
   }
   if (c->path == PATH_TWO_WAVE) return launch("two-wave step kernel", wide_kernel(D.rs, fused), c->n_envs, 128, c->lds_bytes_wide, stream, D, A);
   if (c->path == PATH_TWO_ENV && A.integrate) {      // the build registered for the batch's waves per SIMD, or the one with the rare options
-    static const StepVariant dual[2][3] = {{SV_DUAL_W2, SV_DUAL_W3, SV_DUAL_W4}, {SV_DUAL_W2_RARE, SV_DUAL_W3_RARE, SV_DUAL_W4_RARE}};
+    static const StepVariant dual[3][3] = {{SV_DUAL_W2, SV_DUAL_W3, SV_DUAL_W4}, {SV_DUAL_W2_RARE, SV_DUAL_W3_RARE, SV_DUAL_W4_RARE},
+                                           {SV_DUAL_W2_LEAN, SV_DUAL_W3_LEAN, SV_DUAL_W4_LEAN}};
     const bool rare = (fused && A.substeps > 1) || D.implicitfast;
-    return launch("dual step kernel", step_kernel(D.rs, fused, dual[rare][c->dual_wps - 2]), pairs, 64, c->lds_bytes_dual2, stream, D, A);
+    // the launch shape the lean build has folded in (fmj_dual2.inc, LEAN); anything else runs the generic build
+    const bool lean = c->dual_lean && fused && !rare && !A.rows_ahead && A.controller == 1 && A.do_readout && A.do_drag && !A.disable_actuation &&
+                      !D.any_stiffness && !A.xfrc_applied_out;
+    c->dual_last = lean ? FMJ_DUAL_BUILD_LEAN : (rare ? FMJ_DUAL_BUILD_RARE : FMJ_DUAL_BUILD_GENERIC);
+    return launch("dual step kernel", step_kernel(D.rs, fused, dual[lean ? 2 : rare][c->dual_wps - 2]), pairs, 64, c->lds_bytes_dual2, stream, D, A);
   }
   if (D.cons && (!A.qacc_warmstart || !A.contact || !A.ncon))
     return set_err(FMJ_ERR_ARG, "fmj_data: qacc_warmstart, contact and ncon are required for models with limits / contacts");
@@ -2935,6 +2949,8 @@ static int choose_path(fmj_ctx* c, const ModelFacts& F) {
     c->dual_wps = waves <= 2 * 4 * n_cu ? 2 : (waves <= 3 * 4 * n_cu ? 3 : 4);
     const char* w = getenv("FMJ_WPS");
     if (w && (w[0] == '2' || w[0] == '3' || w[0] == '4')) c->dual_wps = w[0] - '0';
+    const char* l = getenv("FMJ_DUAL_LEAN");      // 0: every launch runs the generic build (tests and A/B runs compare the two)
+    if (l && l[0] == '0') c->dual_lean = 0;
   }
   c->path = F.wide ? PATH_TWO_WAVE : D.dual_ok ? PATH_TWO_ENV : D.cons2_ok ? PATH_CONS2_ONE_ENV : PATH_ONE_ENV;
   c->variant = one_env_variant(D);
@@ -3074,6 +3090,15 @@ int fmj_kernel_info(const fmj_ctx* c, int32_t* lds_bytes_per_env, int32_t* threa
   const int threads[5] = {64, 32, 32, 128, FMJ_F64_LANES};
   if (lds_bytes_per_env) *lds_bytes_per_env = (int32_t)lds[c->path];
   if (threads_per_env) *threads_per_env = threads[c->path];
+  return FMJ_OK;
+}
+
+int fmj_dual_build_info(const fmj_ctx* c, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch) {
+  if (!c) return set_err(FMJ_ERR_ARG, "fmj_dual_build_info: NULL ctx");
+  const bool dual = c->path == PATH_TWO_ENV;
+  if (waves_per_simd) *waves_per_simd = dual ? c->dual_wps : 0;
+  if (lean_enabled) *lean_enabled = dual ? c->dual_lean : 0;
+  if (last_launch) *last_launch = c->dual_last;
   return FMJ_OK;
 }
 

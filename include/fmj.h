@@ -320,6 +320,13 @@ int fmj_get_sensor_layout(const fmj_ctx* ctx, fmj_sensor_layout_t* out);
 /* LDS bytes / VGPR-independent facts the host needs for reporting; threads_per_env is 32 (two envs per wave), 64 (one wave) or
  * 128 (two waves: models past 64 bodies / dofs, or FMJ_WIDE=1; always for an fp64 context, whose LDS holds the rows of H as doubles) */
 int fmj_kernel_info(const fmj_ctx* ctx, int32_t* lds_bytes_per_env, int32_t* threads_per_env);
+/* The build of the two-env step kernel a context runs (all zero / NONE for a context on another kernel).  *waves_per_simd: the register
+ * tier, 2, 3 or 4 (chosen from the batch size at fmj_create; FMJ_WPS=2|3|4 overrides).  *lean_enabled: 1 when fmj_step_fused launches of
+ * the shape of a fused run - wave controller, readout and drag on, substeps = 1, no rows_ahead, no joint stiffness, Euler - run the
+ * build with those options folded in at compile time (bitwise the same results; FMJ_DUAL_LEAN=0 in the environment at fmj_create turns
+ * it off, for comparisons).  *last_launch: the FMJ_DUAL_BUILD_* the last step launch of the context ran.  Any pointer may be NULL. */
+enum { FMJ_DUAL_BUILD_NONE = 0, FMJ_DUAL_BUILD_GENERIC = 1, FMJ_DUAL_BUILD_RARE = 2, FMJ_DUAL_BUILD_LEAN = 3 };
+int fmj_dual_build_info(const fmj_ctx* ctx, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch);
 
 /* ---- swimming links (SwimmingHandler.__init__, reference drag.pyx:333-387) ------------------
  * n_xfrc_rows: rows per env of the xfrc array (len(data.sensors.xfrc.names); the env stride of every xfrc row
