@@ -89,6 +89,7 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
 #define BT2(b, k) ldg4(M.btab, (unsigned)(b) * BT_STRIDE + (k))
 #define DT2(d, k) ldg4(M.dtab, (unsigned)(d) * DT_STRIDE + (k))
 #define AT2(a, k) ldg4(M.atab, (unsigned)(a) * AT_STRIDE + (k))
+#define STAGE2_REC 8      // stride of the CD / F records, for the shared stages (fmj_stage2_*.inc)
   const int lane = threadIdx.x;
   const bool upper = lane >= 32;
   const int sl = lane & 31;
@@ -295,37 +296,7 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
     {
       const float4 c_pos_mass = BT2(bl, 0);
       const float4 c_quat = BT2(bl, 1);
-      xp = mk3(c_pos_mass.x, c_pos_mass.y, c_pos_mass.z);
-      xq.w = c_quat.x; xq.x = c_quat.y; xq.y = c_quat.z; xq.z = c_quat.w;
-      if (jtype == FMJ_JNT_FREE) {
-        xp = mk3(QP[qadr], QP[qadr + 1], QP[qadr + 2]);
-        q4 rq = {QP[qadr + 3], QP[qadr + 4], QP[qadr + 5], QP[qadr + 6]};
-        xq = qnormalize(rq);
-      } else if (jtype == FMJ_JNT_HINGE) {
-        const float q = QP[qadr] - c_axis_q0.w;
-        const v3 ax = mk3(c_axis_q0.x, c_axis_q0.y, c_axis_q0.z);
-        const q4 ql = axisangle_mid(ax, q);
-        if (any_jpos) {
-          const v3 jp = mk3(c_jpos_k.x, c_jpos_k.y, c_jpos_k.z);
-          xp = add3(xp, qrot(xq, sub3(jp, qrot(ql, jp))));
-        }
-        xq = any_bquat ? qmul(xq, ql) : ql;
-      } else if (jtype == FMJ_JNT_SLIDE) {
-        const float q = QP[qadr] - c_axis_q0.w;
-        xp = add3(xp, qrot(xq, scl3(mk3(c_axis_q0.x, c_axis_q0.y, c_axis_q0.z), q)));
-      }
-      if (!isb) { xp = mk3(0.f, 0.f, 0.f); xq.w = 1.f; xq.x = xq.y = xq.z = 0.f; }
-      for (int r = 0; r < max_bdepth; r++) {
-        const int a = r < 4 ? (int)((jm >> (8 * r)) & 0xff) : (sl < nb ? (int)JMP[sl * M.anc_stride + r] : 0);
-        const int src = (hb + a) << 2;
-#define PULL(v_) __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v_)))
-        const v3 ap = mk3(PULL(xp.x), PULL(xp.y), PULL(xp.z));
-        const q4 aqq = {PULL(xq.w), PULL(xq.x), PULL(xq.y), PULL(xq.z)};
-#undef PULL
-        xp = add3(ap, qrot(aqq, xp));
-        xq = qmul(aqq, xq);
-      }
-      xq = qnormalize(xq);
+#include "fmj_stage2_k.inc"
       if (sl < nb) {
         *(float4*)(PO + sl * 8) = make_float4(xp.x, xp.y, xp.z, 0.f);
         *(float4*)(PO + sl * 8 + 4) = make_float4(xq.w, xq.x, xq.y, xq.z);
@@ -348,84 +319,17 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
     {
       const float4 c_iquat = BT2(bl, 3);
       const float4 c_inertia = BT2(bl, 4);
-      q4 iq = {c_iquat.x, c_iquat.y, c_iquat.z, c_iquat.w};
-      const m33 Ri = q2m(any_iquat ? qmul(xq, iq) : xq);
-      const float i0 = c_inertia.x, i1 = c_inertia.y, i2 = c_inertia.z;
-      iw[0] = Ri.a[0] * Ri.a[0] * i0 + Ri.a[1] * Ri.a[1] * i1 + Ri.a[2] * Ri.a[2] * i2;
-      iw[1] = Ri.a[3] * Ri.a[3] * i0 + Ri.a[4] * Ri.a[4] * i1 + Ri.a[5] * Ri.a[5] * i2;
-      iw[2] = Ri.a[6] * Ri.a[6] * i0 + Ri.a[7] * Ri.a[7] * i1 + Ri.a[8] * Ri.a[8] * i2;
-      iw[3] = Ri.a[0] * Ri.a[3] * i0 + Ri.a[1] * Ri.a[4] * i1 + Ri.a[2] * Ri.a[5] * i2;
-      iw[4] = Ri.a[0] * Ri.a[6] * i0 + Ri.a[1] * Ri.a[7] * i1 + Ri.a[2] * Ri.a[8] * i2;
-      iw[5] = Ri.a[3] * Ri.a[6] * i0 + Ri.a[4] * Ri.a[7] * i1 + Ri.a[5] * Ri.a[8] * i2;
-      if (!isb) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) iw[k] = 0.f;
-      }
+#include "fmj_stage2_c.inc"
     }
     STAMP(3);   // C
     // ---- V: joint velocity, cvel = chain sum of joint velocities, cacc = chain sum of cvel_parent x vJ - g
-    s6 cv, ca;
-    {
-      s6 vJ = {mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 0.f)};
-      s6 vt = {mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 0.f)};
-      if (jtype == FMJ_JNT_HINGE || jtype == FMJ_JNT_SLIDE) {
-        const v3 axw = qrot(xq, mk3(c_axis_q0.x, c_axis_q0.y, c_axis_q0.z));
-        s6 cd;
-        if (jtype == FMJ_JNT_HINGE) {
-          const v3 anchor = any_jpos ? add3(xp, qrot(xq, mk3(c_jpos_k.x, c_jpos_k.y, c_jpos_k.z))) : xp;
-          cd.r = axw; cd.l = cross(axw, sub3(com, anchor));
-        } else { cd.r = mk3(0.f, 0.f, 0.f); cd.l = axw; }
-        lds_put6(CD + dadr * 8, cd);
-        vJ = s6scl(cd, QV[dadr]);
-      } else if (jtype == FMJ_JNT_FREE) {
-        const v3 off = sub3(com, xp);
-        const m33 R = q2m(xq);
-        vt.l = mk3(QV[dadr], QV[dadr + 1], QV[dadr + 2]);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {              // the translational cdof are unit vectors: never read back
-          const v3 col = mk3(R.a[k], R.a[k + 3], R.a[k + 6]);
-          s6 cr = {col, cross(col, off)};
-          lds_put6(CD + (dadr + 3 + k) * 8, cr);
-          vJ = s6add(vJ, s6scl(cr, QV[dadr + 3 + k]));
-        }
-      }
-      cv = s6add(vJ, vt);
-#define PULL6(dst_, src_, v_) do { \
-        dst_.r = mk3(__int_as_float(__builtin_amdgcn_ds_bpermute(src_, __float_as_int(v_.r.x))), __int_as_float(__builtin_amdgcn_ds_bpermute(src_, __float_as_int(v_.r.y))), \
-                     __int_as_float(__builtin_amdgcn_ds_bpermute(src_, __float_as_int(v_.r.z)))); \
-        dst_.l = mk3(__int_as_float(__builtin_amdgcn_ds_bpermute(src_, __float_as_int(v_.l.x))), __int_as_float(__builtin_amdgcn_ds_bpermute(src_, __float_as_int(v_.l.y))), \
-                     __int_as_float(__builtin_amdgcn_ds_bpermute(src_, __float_as_int(v_.l.z)))); } while (0)
-      for (int r = 0; r < max_bdepth; r++) {
-        const int a = r < 4 ? (int)((jm >> (8 * r)) & 0xff) : (sl < nb ? (int)JMP[sl * M.anc_stride + r] : 0);
-        s6 o; PULL6(o, (hb + a) << 2, cv);
-        cv = s6add(cv, o);
-      }
-      s6 cpar; PULL6(cpar, (hb + (isb ? c_info.x : 0)) << 2, cv);
-      cpar = s6add(cpar, vt);
-      ca = cross_motion(cpar, vJ);
-      if (!isb) { ca.r = ca.l = mk3(0.f, 0.f, 0.f); }
-      for (int r = 0; r < max_bdepth; r++) {
-        const int a = r < 4 ? (int)((jm >> (8 * r)) & 0xff) : (sl < nb ? (int)JMP[sl * M.anc_stride + r] : 0);
-        s6 o; PULL6(o, (hb + a) << 2, ca);
-        ca = s6add(ca, o);
-      }
-#undef PULL6
-      ca.l = sub3(ca.l, mk3(M.gx, M.gy, M.gz));
-      if (!isb) { cv.r = cv.l = mk3(0.f, 0.f, 0.f); }
-    }
+#include "fmj_stage2_v.inc"
     STAMP(4);   // V
     // ---- F: body force (inertial minus external) about the tree CoM
     const v3 dcom = sub3(xi, com);
     s6 fbody;
     {
-      s6 ia, iv;
-      ia.l = scl3(add3(ca.l, cross(ca.r, dcom)), mass);
-      ia.r = add3(mk3(iw[0] * ca.r.x + iw[3] * ca.r.y + iw[4] * ca.r.z, iw[3] * ca.r.x + iw[1] * ca.r.y + iw[5] * ca.r.z,
-                      iw[4] * ca.r.x + iw[5] * ca.r.y + iw[2] * ca.r.z), cross(dcom, ia.l));
-      iv.l = scl3(add3(cv.l, cross(cv.r, dcom)), mass);
-      iv.r = add3(mk3(iw[0] * cv.r.x + iw[3] * cv.r.y + iw[4] * cv.r.z, iw[3] * cv.r.x + iw[1] * cv.r.y + iw[5] * cv.r.z,
-                      iw[4] * cv.r.x + iw[5] * cv.r.y + iw[2] * cv.r.z), cross(dcom, iv.l));
-      s6 f = s6add(ia, cross_force(cv, iv));
+#include "fmj_stage2_f.inc"
       float xf[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // world-frame external force / torque on this body (the caller's xfrc_applied: this kernel
       if (A.xfrc_applied && isb) {                      // is not launched with the fused drag), re-read instead of carried across the steps
         const float AS1* x = gptr(A.xfrc_applied) + (size_t)env * nb * 6 + bl * 6;
@@ -460,37 +364,7 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
     {
       const float4 c_ipos = BT2(bl, 2);            // .w = subtree mass (model constant)
       const int lastl = hb | (isb ? sl + as_int4(BT2(bl, 8)).y - 1 : sl);
-      const double dm = (double)mass;
-      const double dx = (double)dcom.x, dy = (double)dcom.y, dz = (double)dcom.z;
-      const double ms = (double)c_ipos.w;
-      const double px = half_subtree_sum_f64(dm * dx, lastl), py = half_subtree_sum_f64(dm * dy, lastl), pz = half_subtree_sum_f64(dm * dz, lastl);
-      const double minv = ms > 0.0 ? rcp_f64_nr(ms) : 0.0;
-      const double ex = px * minv, ey = py * minv, ez = pz * minv;
-#define SCAN2(ra_, rb_, ea_, eb_, post_a_, post_b_) do { \
-        double pa_ = (ea_), pb_ = (eb_); \
-        const double xa_ = pa_, xb_ = pb_; \
-        pa_ += dpp_f64<0x111, 0xF>(pa_); pb_ += dpp_f64<0x111, 0xF>(pb_); \
-        pa_ += dpp_f64<0x112, 0xF>(pa_); pb_ += dpp_f64<0x112, 0xF>(pb_); \
-        pa_ += dpp_f64<0x114, 0xF>(pa_); pb_ += dpp_f64<0x114, 0xF>(pb_); \
-        pa_ += dpp_f64<0x118, 0xF>(pa_); pb_ += dpp_f64<0x118, 0xF>(pb_); \
-        pa_ += dpp_f64<0x142, 0xA>(pa_); pb_ += dpp_f64<0x142, 0xA>(pb_); \
-        const double sa_ = lane_gather_f64(pa_, lastl) - pa_ + xa_, sb_ = lane_gather_f64(pb_, lastl) - pb_ + xb_; \
-        ra_ = pinf((float)(sa_ + (post_a_))); rb_ = pinf((float)(sb_ + (post_b_))); } while (0)
-      float i0, i1, i2, i3, i4, i5;
-      SCAN2(i0, i1, (double)pinf(iw[0]) + dm * (dy * dy + dz * dz), (double)pinf(iw[1]) + dm * (dx * dx + dz * dz), -ms * (ey * ey + ez * ez), -ms * (ex * ex + ez * ez));
-      SCAN2(i2, i3, (double)pinf(iw[2]) + dm * (dx * dx + dy * dy), (double)pinf(iw[3]) - dm * dx * dy, -ms * (ex * ex + ey * ey), ms * ex * ey);
-      SCAN2(i4, i5, (double)pinf(iw[4]) - dm * dx * dz, (double)pinf(iw[5]) - dm * dy * dz, ms * ex * ez, ms * ey * ez);
-      s6 fs;
-      SCAN2(fs.r.x, fs.r.y, (double)pinf(fbody.r.x), (double)pinf(fbody.r.y), 0.0, 0.0);
-      SCAN2(fs.r.z, fs.l.x, (double)pinf(fbody.r.z), (double)pinf(fbody.l.x), 0.0, 0.0);
-      SCAN2(fs.l.y, fs.l.z, (double)pinf(fbody.l.y), (double)pinf(fbody.l.z), 0.0, 0.0);
-#undef SCAN2
-      if (sl < nb) {
-        *(float4*)(CI + sl * 12) = make_float4(i0, i1, i2, i3);
-        *(float4*)(CI + sl * 12 + 4) = make_float4(i4, i5, (float)ex, (float)ey);
-        *(float2*)(CI + sl * 12 + 8) = make_float2((float)ez, (float)ms);
-        lds_put6(F + sl * 8, fs);
-      }
+#include "fmj_stage2_s.inc"
     }
     WSYNC();
     STAMP(6);   // S
@@ -1056,4 +930,5 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
 #undef BT2
 #undef DT2
 #undef AT2
+#undef STAGE2_REC
 }

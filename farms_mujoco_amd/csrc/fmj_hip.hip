@@ -1216,22 +1216,7 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
   }
   float cy_limfrc = 0.f;                            // carried joint-limit force of this dof's joint (physics.py:484-487)
   if (CONS && FUSED && isd) { const int4 da0 = DTABI(dl, 2); if (DTAB(dl, 1).w != 0.f) cy_limfrc = gptr(A.sensordata)[(size_t)env * M.nsensordata + 6 * (nb - 1) + 3 * da0.z + 2] * A.inv_torques; }
-  float xf[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // world-frame external force / torque on this body
-  float cy_actsum = 0.f;                            // carried motor torque (physics.py:510-524)
-  if (FUSED) {
-    const float4 dp = DTAB(dl, 1);
-    if (isd && dp.w != 0.f) {
-      const int4 da = DTABI(dl, 2);
-      const float* sa = glob(A.sensordata) + (size_t)env * M.nsensordata + 6 * (nb - 1) + 3 * M.njs;
-#pragma unroll
-      for (int a = 0; a < 4; a++) if (a < da.y) cy_actsum += sa[__float_as_int(ATAB(da.x + a, 2).x)] * A.inv_torques;
-    }
-  }
-  if (!(FUSED && A.do_drag) && A.xfrc_applied && isb) {
-    const float* x = glob(A.xfrc_applied) + (size_t)env * nb * 6 + bl * 6;
-#pragma unroll
-    for (int k = 0; k < 6; k++) xf[k] = x[k];
-  }
+#include "fmj_stage_carry_in.inc"      // xf, cy_actsum
   // An env with a bad-state bit is frozen (include/fmj.h): it is not integrated and writes no rows, from the step that
   // finds the bad value on and in later launches until the caller clears its status word.
   bool frozen = (gptr(A.status)[env] & FMJ_WARN_FREEZE) != 0 || __any((warn & FMJ_WARN_FREEZE) != 0);
@@ -1266,17 +1251,7 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
 #pragma unroll 1
   for (int step = step0; step < A.n_steps; step++) {
     if (frozen) break;
-    asm volatile("" : "+s"(Mp), "+s"(Ap));       // arguments are re-read from the kernarg segment in every step
-    // per-lane LDS/global addresses are recomputed every step instead of being hoisted and spilled
-    const int lane = opaque(lane_outer);
-    const int it = A.iteration0 + itm;
-    const bool last = step == A.n_steps - 1;
-    const int S_sub = A.substeps;
-    const bool full = sub == 0;
-    const int nsub = sub + 1 >= S_sub ? 0 : sub + 1;           // the next physics step: its sub index, whether it is a full step,
-    const bool nfull = nsub == 0;                               // and task.iteration as its before_step will see it: the reference
-    const int nit = (nfull ? it + 1 : it) + ((nsub >= 1 && nsub >= S_sub - 1) ? 1 : 0);   // advances it after sub-step S - 2 (task.py:352-355)
-    const int blo = opaque(bl), dlo = opaque(dl);
+#include "fmj_stage_step_head.inc"      // lane, it, last, S_sub, full, nsub, nfull, nit, blo, dlo
     // the lane's depth / subtree size are laundered too: every per-lane predicate made from them (lvl < ddepth for 20
     // levels, the ancestor tests of the sweeps) is loop-invariant and was hoisted into SGPR pairs - ~100 of them, all spilled
     const int ddepth = opaque(ddepth_o), dsub = opaque(dsub_o);
@@ -1313,28 +1288,7 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
     const bool any_jpos = M.any_jpos != 0, any_bquat = M.any_bquat != 0, any_iquat = M.any_iquat != 0;   // model-wide (uniform) shortcuts
     v3 xp; q4 xq;
     {
-      const float4 c_pos_mass = BTAB(blo, 0);
-      const float4 c_quat = BTAB(blo, 1);
-      xp = mk3(c_pos_mass.x, c_pos_mass.y, c_pos_mass.z);
-      xq.w = c_quat.x; xq.x = c_quat.y; xq.y = c_quat.z; xq.z = c_quat.w;
-      if (jtype == FMJ_JNT_FREE) {
-        xp = mk3(QP[qadr], QP[qadr + 1], QP[qadr + 2]);
-        q4 rq = {QP[qadr + 3], QP[qadr + 4], QP[qadr + 5], QP[qadr + 6]};
-        xq = qnormalize(rq);
-      } else if (jtype == FMJ_JNT_HINGE) {
-        const float q = QP[qadr] - c_axis_q0.w;
-        const v3 ax = mk3(c_axis_q0.x, c_axis_q0.y, c_axis_q0.z);
-        const q4 ql = axisangle_mid(ax, q);       // half-angle sin / cos by polynomial for |q| <= pi
-        if (any_jpos) {                           // anchor off the body origin: the body turns about the anchor
-          const v3 jp = mk3(c_jpos_k.x, c_jpos_k.y, c_jpos_k.z);
-          xp = add3(xp, qrot(xq, sub3(jp, qrot(ql, jp))));
-        }
-        xq = any_bquat ? qmul(xq, ql) : ql;       // body frames aligned with their parents': the local rotation is the joint's
-      } else if (jtype == FMJ_JNT_SLIDE) {
-        const float q = QP[qadr] - c_axis_q0.w;
-        xp = add3(xp, qrot(xq, scl3(mk3(c_axis_q0.x, c_axis_q0.y, c_axis_q0.z), q)));
-      }
-      if (!isb) { xp = mk3(0.f, 0.f, 0.f); xq.w = 1.f; xq.x = xq.y = xq.z = 0.f; }
+#include "fmj_stage_k.inc"      // the body's local transform (xp, xq)
       const uint32_t jm = lane < nb ? *(const uint32_t*)(JMP + lane * M.anc_stride) : 0u;   // rounds 0..3
       // the partner's pose comes out of its registers with ds_bpermute (lane 0 is the world: identity)
       for (int r = 0; r < M.max_bdepth; r++) {      // max_bdepth = number of jumping rounds
@@ -1365,53 +1319,12 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
     com.x = wave_sum_fast(mass * xi.x) * M.mtot_inv;     // DPP reductions, no LDS traffic
     com.y = wave_sum_fast(mass * xi.y) * M.mtot_inv;
     com.z = wave_sum_fast(mass * xi.z) * M.mtot_inv;
-    float iw[6];     // world-frame inertia about the body's own CoM
-    {
-      const float4 c_iquat = BTAB(blo, 3);
-      const float4 c_inertia = BTAB(blo, 4);
-      q4 iq = {c_iquat.x, c_iquat.y, c_iquat.z, c_iquat.w};
-      const m33 Ri = q2m(any_iquat ? qmul(xq, iq) : xq);
-      const float i0 = c_inertia.x, i1 = c_inertia.y, i2 = c_inertia.z;
-      iw[0] = Ri.a[0] * Ri.a[0] * i0 + Ri.a[1] * Ri.a[1] * i1 + Ri.a[2] * Ri.a[2] * i2;
-      iw[1] = Ri.a[3] * Ri.a[3] * i0 + Ri.a[4] * Ri.a[4] * i1 + Ri.a[5] * Ri.a[5] * i2;
-      iw[2] = Ri.a[6] * Ri.a[6] * i0 + Ri.a[7] * Ri.a[7] * i1 + Ri.a[8] * Ri.a[8] * i2;
-      iw[3] = Ri.a[0] * Ri.a[3] * i0 + Ri.a[1] * Ri.a[4] * i1 + Ri.a[2] * Ri.a[5] * i2;
-      iw[4] = Ri.a[0] * Ri.a[6] * i0 + Ri.a[1] * Ri.a[7] * i1 + Ri.a[2] * Ri.a[8] * i2;
-      iw[5] = Ri.a[3] * Ri.a[6] * i0 + Ri.a[4] * Ri.a[7] * i1 + Ri.a[5] * Ri.a[8] * i2;
-      if (!isb) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) iw[k] = 0.f;
-      }
-    }
+#include "fmj_stage_c.inc"      // iw: world-frame inertia about the body's own CoM
     STAMP(3);   // C
     // ---- V: joint velocity vJ, then cvel = chain sum of vJ, cacc = a0 + chain sum of cvel_parent x vJ
     s6 cv, ca;
     {
-      s6 vJ = {mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 0.f)};
-      s6 vt = {mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 0.f)};       // translational part of a free root
-      if (jtype == FMJ_JNT_HINGE || jtype == FMJ_JNT_SLIDE) {
-        const v3 axw = qrot(xq, mk3(c_axis_q0.x, c_axis_q0.y, c_axis_q0.z));
-        s6 cd;
-        if (jtype == FMJ_JNT_HINGE) {
-          const v3 anchor = any_jpos ? add3(xp, qrot(xq, mk3(c_jpos_k.x, c_jpos_k.y, c_jpos_k.z))) : xp;
-          cd.r = axw; cd.l = cross(axw, sub3(com, anchor));
-        } else { cd.r = mk3(0.f, 0.f, 0.f); cd.l = axw; }
-        lds_put6(CD + dadr * 8, cd);
-        vJ = s6scl(cd, QV[dadr]);
-      } else if (jtype == FMJ_JNT_FREE) {
-        const v3 off = sub3(com, xp);
-        const m33 R = q2m(xq);
-        vt.l = mk3(QV[dadr], QV[dadr + 1], QV[dadr + 2]);
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          s6 ct = {mk3(0.f, 0.f, 0.f), mk3(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f)};
-          lds_put6(CD + (dadr + k) * 8, ct);
-          const v3 col = mk3(R.a[k], R.a[k + 3], R.a[k + 6]);
-          s6 cr = {col, cross(col, off)};
-          lds_put6(CD + (dadr + 3 + k) * 8, cr);
-          vJ = s6add(vJ, s6scl(cr, QV[dadr + 3 + k]));
-        }
-      }
+#include "fmj_stage_v.inc"      // cdof into CD, joint velocity vJ, vt
       const uint32_t jm = lane < nb ? *(const uint32_t*)(JMP + lane * M.anc_stride) : 0u;
       cv = s6add(vJ, vt);
 #define PULL6(dst_, src_, v_) do { \
@@ -1439,45 +1352,7 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
       if (!isb) { cv.r = cv.l = mk3(0.f, 0.f, 0.f); }
     }
     STAMP(4);   // V
-    // ---- F: body force (inertial minus external), about the common point
-    s6 fbody;
-    {
-      // cinert * v with cinert = {Iw, d = xi - com, m} (MuJoCo's cinert about the tree CoM, never materialised):
-      // lin = p = m (u + w x d),  rot = Iw w + d x p
-      const v3 d = sub3(xi, com);
-      s6 ia, iv;
-      ia.l = scl3(add3(ca.l, cross(ca.r, d)), mass);
-      ia.r = add3(mk3(iw[0] * ca.r.x + iw[3] * ca.r.y + iw[4] * ca.r.z, iw[3] * ca.r.x + iw[1] * ca.r.y + iw[5] * ca.r.z,
-                      iw[4] * ca.r.x + iw[5] * ca.r.y + iw[2] * ca.r.z), cross(d, ia.l));
-      iv.l = scl3(add3(cv.l, cross(cv.r, d)), mass);
-      iv.r = add3(mk3(iw[0] * cv.r.x + iw[3] * cv.r.y + iw[4] * cv.r.z, iw[3] * cv.r.x + iw[1] * cv.r.y + iw[5] * cv.r.z,
-                      iw[4] * cv.r.x + iw[5] * cv.r.y + iw[2] * cv.r.z), cross(d, iv.l));
-      s6 f = s6add(ia, cross_force(cv, iv));
-      const v3 fw = mk3(xf[0], xf[1], xf[2]), tw = mk3(xf[3], xf[4], xf[5]);
-      f.r = sub3(f.r, add3(tw, cross(sub3(xi, com), fw)));
-      f.l = sub3(f.l, fw);
-      if (!isb) { f.r = f.l = mk3(0.f, 0.f, 0.f); }
-      fbody = f;
-    }
-    // ---- sensors of this (pre-integration) state; they are next iteration's link data (mj_step lag)
-    {
-      const v3 linvel = add3(cv.l, cross(cv.r, sub3(xi, com)));
-      if (FUSED && !last && (nfull || (A.sub_links && !(A.n_it_total > 0 && nit >= A.n_it_total)))) {      // the next before_step's links row and drag (xf is consumed above, in this step's F);
-        const int4 ci2 = BTABI(blo, 8);                     // a sub-step that writes no row keeps the drag force it has
-        emit_links_and_drag(M, A, env, nit, isb, false, ci2.z, ci2.w, xp, xq, xi, linvel, cv.r, xf);
-      }
-      if (last && lane < nb) {
-        float* p = glob(A.xpos) + (size_t)env * nb * 3 + lane * 3; p[0] = xp.x; p[1] = xp.y; p[2] = xp.z;
-        *(float4*)(glob(A.xquat) + (size_t)env * nb * 4 + lane * 4) = make_float4(xq.w, xq.x, xq.y, xq.z);
-        float* ip = glob(A.xipos) + (size_t)env * nb * 3 + lane * 3; ip[0] = xi.x; ip[1] = xi.y; ip[2] = xi.z;
-        if (isb) {
-          float* sp = glob(A.sensordata) + (size_t)env * M.nsensordata + 6 * (lane - 1);
-          *(float2*)(sp) = make_float2(linvel.x, linvel.y);
-          *(float2*)(sp + 2) = make_float2(linvel.z, cv.r.x);
-          *(float2*)(sp + 4) = make_float2(cv.r.y, cv.r.z);
-        }
-      }
-    }
+#include "fmj_stage_f.inc"      // F: fbody; the next links row and drag; on the last step the pose and velocimeter stores
     WSYNC();
     STAMP(5);   // F + carry
     // ---- S: subtree sums over the contiguous DFS id range [lane, lane + subsize) as prefix-sum differences
@@ -1520,123 +1395,17 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
     }
     WSYNC();
     STAMP(6);   // S
-    // ---- Q: qfrc_smooth, buf = (I_s w, m v(s))  (lane = dof)
-    float qfrc = 0.f;
-    float dvel = 0.f;                               // implicitfast: velocity gains of this dof's unclamped actuators
-    float af0 = 0.f, af1 = 0.f, af2 = 0.f, af3 = 0.f;
-    const float4 d_prm = DTAB(dlo, 1);             // armature, damping, qposadr bits, hinge/slide flag
-    const int4 d_act = DTABI(dlo, 2);               // first actuator, count, joint sensor slot
-    const int d_qadr = __float_as_int(d_prm.z);
-    const bool d_scalar = isd && d_prm.w != 0.f;
-    s6 cd = {mk3(0.f, 0.f, 0.f), mk3(0.f, 0.f, 0.f)}, bf = cd;     // this dof's cdof; (I_s w_i, m v_i(s)), s = CoM of the subtree it moves
-    v3 sc = mk3(0.f, 0.f, 0.f);                                    // s relative to the tree CoM
-    if (isd) {
-      const int body = DTABI(dlo, 0).x;
-      cd = lds_get6(CD + lane * 8);
-      {
-        const float4 a = *(const float4*)(CI + body * 12), b = *(const float4*)(CI + body * 12 + 4);
-        const float2 c = *(const float2*)(CI + body * 12 + 8);
-        sc = sub3(mk3(b.z, b.w, c.x), com);
-        const v3 vs = add3(cd.l, cross(cd.r, sc));                 // velocity of the subtree CoM per unit dof rate
-        bf.r = mk3(a.x * cd.r.x + a.w * cd.r.y + b.x * cd.r.z, a.w * cd.r.x + a.y * cd.r.y + b.y * cd.r.z, b.x * cd.r.x + b.y * cd.r.y + a.z * cd.r.z);
-        bf.l = scl3(vs, c.y);
-      }
-      const float qd = QV[lane];
-      qfrc = -d_prm.y * qd - s6dot(cd, lds_get6(F + body * 8));
-      if (d_scalar) {
-        const float qj = QP[d_qadr];
-        if (M.any_stiffness) {
-          const float kst = BTAB(body, 6).w;
-          if (kst != 0.f) qfrc -= kst * (qj - gptr(A.qpos_spring)[(size_t)env * nq + d_qadr]);
-        }
-        float asum = 0.f;
-        float cbase = 0.f;
-        if (FUSED && A.controller == 1) {
-          // phase in cycles kept in fp64 so long runs keep the argument exact (task.py:290: time = iteration*timestep)
-          double cyc = (double)A.w_freq * ((double)it * ((double)M.h * (double)S_sub));   // task.py:290: time = iteration * timestep (of an iteration)
-          cyc -= floor(cyc);
-          cbase = 6.283185307179586f * (float)cyc + gptr(A.w_env)[env];
-        }
-#pragma unroll
-        for (int a = 0; a < 4; a++) {                 // mj_fwdActuation, joint transmission
-          if (a < d_act.y) {
-            const int ai = d_act.x + a, src = __float_as_int(ATAB(ai, 2).x);
-            const float4 p = ATAB(ai, 0), lim = ATAB(ai, 1);
-            float c;
-            if (FUSED && A.controller == 1) { const float amp = gptr(A.w_amp)[src]; c = amp != 0.f ? amp * sinf(cbase - gptr(A.w_lag)[src]) : 0.f; }
-            else c = A.ctrl ? gptr(A.ctrl)[(size_t)itm * A.ctrl_step_stride + (size_t)env * nu + src] : 0.f;      // one ctrl row per iteration
-            c = fminf(fmaxf(c, lim.x), lim.y);
-            float f = p.x * c + p.y + p.z * qj + p.w * qd;
-            if (M.implicitfast && !A.disable_actuation && f > lim.z && f < lim.w) dvel -= p.w;      // d force / d qvel of an unclamped actuator (mjd_actuator_vel)
-            f = fminf(fmaxf(f, lim.z), lim.w);
-            if (A.disable_actuation) f = 0.f;
-            if (a == 0) af0 = f; else if (a == 1) af1 = f; else if (a == 2) af2 = f; else af3 = f;
-            asum += f;
-          }
-        }
-        qfrc += asum;
-        cy_actsum = asum * A.inv_torques;
-        if (FUSED && A.controller == 1 && last && A.ctrl_out) {     // what task.py:288-346 leaves in physics.data.ctrl
-#pragma unroll
-          for (int a = 0; a < 4; a++) if (a < d_act.y) {
-            const int src = __float_as_int(ATAB(d_act.x + a, 2).x);
-            const float amp = gptr(A.w_amp)[src];
-            gptr(A.ctrl_out)[(size_t)env * nu + src] = amp != 0.f ? amp * sinf(cbase - gptr(A.w_lag)[src]) : 0.f;
-          }
-        }
-        if (last) {
-          float* sa = glob(A.sensordata) + (size_t)env * M.nsensordata + 6 * (nb - 1) + 3 * M.njs;   // actuatorfrc
-          if (0 < d_act.y) sa[__float_as_int(ATAB(d_act.x + 0, 2).x)] = af0;
-          if (1 < d_act.y) sa[__float_as_int(ATAB(d_act.x + 1, 2).x)] = af1;
-          if (2 < d_act.y) sa[__float_as_int(ATAB(d_act.x + 2, 2).x)] = af2;
-          if (3 < d_act.y) sa[__float_as_int(ATAB(d_act.x + 3, 2).x)] = af3;
-        }
-      }
-    }
+#include "fmj_stage_q.inc"      // Q: qfrc_smooth with actuation (lane = dof); defines qfrc, dvel, cd, bf, sc, d_prm, d_act, d_qadr, d_scalar
     WSYNC();
     STAMP(7);   // Q
-    // ---- M: row i of M (lane = dof i), one entry per depth of the chain root -> i, born in registers:
-    //      M[i][j] = w_j . (I_s w_i) + v_j(s) . (m v_i(s)), s = CoM of the subtree dof i moves, j = ancestor of i at that depth;
-    //      v_j(s) = v_j + w_j x sc, so M[i][j] = w_j . (I_s w_i + sc x p_i) + v_j . p_i with p_i = m v_i(s): the bracket gi is
-    //      the lane's own and an entry costs two dot products.  Slots at and past the lane's own depth hold finite values
-    //      that are never read as matrix entries (beyond the chain the table names the lane itself); the diagonals live in
-    //      hdg_m (+ armature) and hdg_h (+ armature + h damping).  Lanes without a dof have cd = 0: their rows are zero.
-    f2_t hrow[MAXD / 2];
-    float hdg_m, hdg_h;
-    {
-      const v3 gi = add3(bf.r, cross(sc, bf.l));
-      const float mii = dot3(cd.r, gi) + dot3(cd.l, bf.l);
-      hdg_m = isd ? mii + d_prm.x : 1.f;
-      hdg_h = isd ? mii + (d_prm.x + M.hdamp * (d_prm.y + dvel)) : 1.f;
-      const int maxdep = M.maxdep1;
-#pragma unroll
-      for (int g = 0; g < MAXD / 4; g++) {
-        const uint32_t ab = gptr(M.ancl1)[(unsigned)dlo * (MAXD / 4) + g];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const int d = 4 * g + k;
-          float mij = 0.f;
-          if (d <= maxdep) {                        // uniform test, static register index
-            const int al = (int)((ab >> (8 * k)) & 0xffu) >> 2;            // lane = dof of the ancestor at depth d
-            const s6 cdj = lds_get6(CD + al * 8);
-            mij = dot3(cdj.r, gi) + dot3(cdj.l, bf.l);
-          }
-          if (k & 1) hrow[d / 2].y = mij; else hrow[d / 2].x = mij;
-        }
-      }
-    }
+#define MROW_ANCL M.ancl1
+#define MROW_LANE(byte_) ((int)(byte_) >> 2)      // byte = 4 * lane (a ds_bpermute address)
+#include "fmj_stage_m.inc"
+#undef MROW_ANCL
+#undef MROW_LANE
     WSYNC();                                        // without constraints the published rows overlay CD / F / CI from here
     STAMP(8);   // M
-    if (!FUSED && A.dbg_H) {      // fmj_forward_debug: the assembled rows of H and the right-hand side, before any factorisation
-      if (isd) {
-#pragma unroll
-        for (int d = 0; d < MAXD; d++) {
-          const float v = (d & 1) ? hrow[d / 2].y : hrow[d / 2].x;
-          gptr(A.dbg_H)[((size_t)env * nv + lane) * RS + d] = d < ddepth ? v : (d == ddepth ? hdg_h : 0.f);
-        }
-        gptr(A.dbg_qfrc)[(size_t)env * nv + lane] = qfrc;
-      }
-    }
+#include "fmj_stage_dbg_h.inc"      // fmj_forward_debug: the rows of H and the right-hand side
     // ---- constraints (CONS instantiation only): qfrc_constraint from limits + plane contacts via PGS
     float qfrc_c = 0.f;
     float dinv_h = 0.f;               // 1 / D of the factor of H
@@ -1931,46 +1700,11 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
       else my_qacc = ldl_pull_sweep<MAXD>(HR, xr * dinv_h, isd ? lane : 0, isd, ddepth, M.ancl1, M.maxdep1);
     }
     STAMP(10);  // X
-    // ---- semi-implicit Euler (mj_Euler with implicit joint damping)
-    const float hstep = A.integrate ? M.h : 0.f;     // fmj_forward: mj_forward only
-    const float pre_qd = isd ? QV[lane] : 0.f;
-    const float nvel = pre_qd + hstep * my_qacc;
-    if (isd) {
-      if (!(fabsf(my_qacc) <= 1e10f)) warn |= FMJ_WARN_BADQACC;      // mj_checkAcc
-      if (!(fabsf(nvel) <= 1e10f)) warn |= FMJ_WARN_BADQVEL;
-      // the root position this step would commit is tested BEFORE anything is committed (the translational dofs of a free root are
-      // dofs 0..2 at qpos 0..2): a step that raises BADQPOS leaves qpos, qvel and time exactly at the previous step's values
-      if (M.root_free && lane < 3 && A.integrate && !(fabsf(QP[lane] + M.h * nvel) <= 1e10f)) warn |= FMJ_WARN_BADQPOS;
-    }
+#include "fmj_stage_euler_check.inc"      // semi-implicit Euler: nvel and the warn tests ...
     if (__any((warn & FMJ_WARN_FREEZE) != 0)) frozen = true;         // the state stays at its last finite values
-    if (isd && !frozen) {
-      XV[lane] = my_qacc;
-      QV[lane] = nvel;
-      if (d_scalar) {
-        const float pre_q = QP[d_qadr];
-        QP[d_qadr] = pre_q + hstep * nvel;
-        if (last) {
-          float* s = glob(A.sensordata) + (size_t)env * M.nsensordata + 6 * (nb - 1) + 3 * d_act.z;   // jointpos, jointvel, jointlimitfrc
-          s[0] = pre_q; s[1] = pre_qd; if (!CONS) s[2] = 0.f;
-        }
-      }
-    }
-    if (!frozen) steps_done++;
+#include "fmj_stage_euler_commit.inc"      // ... the commit of XV / QV / QP and the joint sensors ...
     WSYNC();
-    if (jtype == FMJ_JNT_FREE && A.integrate && !frozen) {     // free joint position update (lane = root body)
-      // the new root position is tested before it is committed: a frozen env keeps its last finite state (include/fmj.h)
-      const float nx = QP[qadr] + M.h * QV[dadr], ny = QP[qadr + 1] + M.h * QV[dadr + 1], nz = QP[qadr + 2] + M.h * QV[dadr + 2];
-      if (!(fabsf(nx) <= 1e10f) || !(fabsf(ny) <= 1e10f) || !(fabsf(nz) <= 1e10f)) warn |= FMJ_WARN_BADQPOS;
-      else {
-        QP[qadr] = nx; QP[qadr + 1] = ny; QP[qadr + 2] = nz;
-        const v3 w = mk3(QV[dadr + 3], QV[dadr + 4], QV[dadr + 5]);
-        const float n2 = dot3(w, w), rn = rsqrt_nr(n2), n = n2 * rn;
-        q4 qo = {QP[qadr + 3], QP[qadr + 4], QP[qadr + 5], QP[qadr + 6]};
-        qo = qnormalize(qo);
-        if (n2 >= 1e-30f) qo = qmul(qo, axisangle_small(scl3(w, rn), M.h * n));
-        QP[qadr + 3] = qo.w; QP[qadr + 4] = qo.x; QP[qadr + 5] = qo.y; QP[qadr + 6] = qo.z;
-      }
-    }
+#include "fmj_stage_euler_root.inc"      // ... and the free root's position and quaternion
     if (__any((warn & FMJ_WARN_BADQPOS) != 0)) frozen = true;   // no row of the next iteration is emitted from a bad position
     sub = nsub; itm += nfull ? 1 : 0;
     WSYNC();
@@ -2014,6 +1748,12 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 // -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64 (kernel and getter: fmj_f64.inc), and once without any of
 // them (standalone operators and all host code), in parallel, and the objects are
 // linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
+// Every csrc/*.inc is part of this one source (the build and build_id() depend on all of them):
+//   fmj_cons_rows.inc, fmj_newton.inc          constraint rows and solvers of fmj_step_kernel<.., CONS = true>
+//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc      the other step kernels
+//   fmj_stage_{carry_in,step_head,k,c,v,f,q,m,dbg_h,euler_check,euler_commit,euler_root}.inc      stages shared by fmj_step_kernel and fmj_step_wide_kernel
+//   fmj_stage2_{k,c,v,f,s}.inc                 stages shared by fmj_step_dual2_kernel and fmj_step_cons2_kernel
+// scripts/device_listing.sh prints one digest of the device assembly per translation unit: a refactor keeps all of them.
 
 #define FMJ_CAT2(a, b) a##b
 #define FMJ_CAT(a, b) FMJ_CAT2(a, b)
