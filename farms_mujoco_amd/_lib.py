@@ -62,6 +62,11 @@ class CFusedArgs(ctypes.Structure):
                 ('n_iterations', ctypes.c_int32), ('rows_ahead', ctypes.c_int32)]
 
 
+class CFusedExt(ctypes.Structure):      # fmj_fused_ext: per-env parameters of the wave controller (fmj_step_fused_ex)
+    _fields_ = [('size', ctypes.c_int32), ('reserved', ctypes.c_int32), ('wave_frequency_env', _VP),
+                ('wave_amplitude_env_stride', ctypes.c_int64), ('wave_phase_lag_env_stride', ctypes.c_int64)]
+
+
 BEFORE_ROWS, BEFORE_LINKS_ONLY, BEFORE_CONTACTS, BEFORE_DRAG = 1, 2, 4, 8      # FMJ_BEFORE_* of include/fmj.h
 
 
@@ -78,6 +83,13 @@ class CCpgDesc(ctypes.Structure):
                 ('frequency', _D), ('rate', _D), ('amplitude', _D),
                 ('conn_to', _I), ('conn_from', _I), ('conn_weight', _D), ('conn_bias', _D),
                 ('out_a', _I), ('out_b', _I), ('out_gain', _D), ('out_offset', _D)]
+
+
+CPG_ENV_ARRAYS = ('drive', 'omega', 'rate', 'amplitude', 'conn_weight', 'conn_bias', 'out_gain', 'out_offset')
+
+
+class CCpgEnvParams(ctypes.Structure):      # fmj_cpg_env_params: per-env network parameters (fmj_cpg_tape_ex)
+    _fields_ = [('size', ctypes.c_int32), ('reserved', ctypes.c_int32)] + [(n, _VP) for n in CPG_ENV_ARRAYS]
 
 
 SYMBOLS = {
@@ -109,10 +121,13 @@ SYMBOLS = {
                                        ctypes.c_int32, _VP, _VP]),
     'fmj_contacts2data': (ctypes.c_int, [_VP, ctypes.POINTER(CData), ctypes.POINTER(CRows), ctypes.POINTER(CUnits), _VP]),
     'fmj_step_fused': (ctypes.c_int, [_VP, ctypes.POINTER(CData), ctypes.POINTER(CFusedArgs), _VP]),
+    'fmj_step_fused_ex': (ctypes.c_int, [_VP, ctypes.POINTER(CData), ctypes.POINTER(CFusedArgs), ctypes.POINTER(CFusedExt), _VP]),
     'fmj_sc': (ctypes.c_int, [ctypes.c_char_p]),
     'fmj_cpg_create': (ctypes.c_int, [ctypes.POINTER(CCpgDesc), ctypes.c_int32, ctypes.POINTER(_VP)]),
     'fmj_cpg_destroy': (None, [_VP]),
     'fmj_cpg_tape': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
+    'fmj_cpg_tape_ex': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _VP, _VP, _VP, ctypes.POINTER(CCpgEnvParams),
+                                       _VP, _VP]),
 }
 
 def build_id() -> str:
@@ -199,7 +214,8 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
     return target
 
 
-OPTIONAL_IN_AB_BASE = ('fmj_solver_info', 'fmj_create_ex', 'fmj_precision', 'fmj_dual_build_info')      # queries only (physics.py tolerates their absence under FMJ_SO)
+# queries, and entries only per-env controller parameters call (physics.py / simulation.py tolerate their absence under FMJ_SO)
+OPTIONAL_IN_AB_BASE = ('fmj_solver_info', 'fmj_create_ex', 'fmj_precision', 'fmj_dual_build_info', 'fmj_step_fused_ex', 'fmj_cpg_tape_ex')
 
 
 def load():

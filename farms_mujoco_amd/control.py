@@ -40,26 +40,61 @@ class AnimatController:
 class WaveController(AnimatController):
     """Travelling-wave position controller of the benchmark configs:
     ``ctrl_j(t, e) = A_j sin(2 pi f t - phi_j + psi_e)``.  ``fusable``: the fused HIP loop evaluates the
-    same expression on the device (include/fmj.h: fmj_wave_controller), so no per-step host work remains."""
+    same expression on the device (include/fmj.h: fmj_wave_controller), so no per-step host work remains.
+
+    Every env may swim its own gait (a parameter sweep; include/fmj.h: fmj_fused_ext): ``frequency`` is a scalar or ``[n_envs]``,
+    and the keyword-only ``amplitude_env`` / ``phase_lag_env`` = ``[n_envs, nu]`` in actuator order replace the rows that
+    ``amplitude`` / ``n_wave`` describe (entries of non-position actuators must be 0, as ``wave_controller_params`` leaves them).
+    The attributes carry the shapes: ``frequency`` a float or a tensor ``[n_envs]``, ``amplitude`` / ``phase_lag`` ``[nu]`` or
+    ``[n_envs, nu]``."""
     fusable = True
 
-    def __init__(self, model, env_phase, frequency=1.0, amplitude=0.3, n_wave=1.0, device='cuda:0'):
+    def __init__(self, model, env_phase, frequency=1.0, amplitude=0.3, n_wave=1.0, device='cuda:0', *, amplitude_env=None,
+                 phase_lag_env=None):
         from .model import wave_controller_params
         names = [model.joint_names[model.actuator_jntid[a]] for a in range(model.nu)
                  if model.actuator_tags[a] == 'position']
         super().__init__({ControlType.POSITION: names, ControlType.VELOCITY: [], ControlType.TORQUE: []})
         amp, lag = wave_controller_params(model, amplitude, n_wave)
-        self.frequency = float(frequency)
-        self.amplitude = torch.as_tensor(amp, dtype=torch.float32, device=device)      # [nu]
-        self.phase_lag = torch.as_tensor(lag, dtype=torch.float32, device=device)      # [nu]
-        self.env_phase = torch.as_tensor(np.asarray(env_phase), dtype=torch.float32, device=device)  # [n_envs]
+        env_phase = np.asarray(env_phase)
+        if env_phase.ndim != 1:
+            raise ValueError(f'env_phase: expected shape [n_envs], not {env_phase.shape}')
+        n_envs, nu = len(env_phase), model.nu
+        if np.ndim(frequency) == 0:
+            self.frequency = float(frequency)
+        else:
+            if np.shape(frequency) != (n_envs,):
+                raise ValueError(f'frequency: expected a scalar or shape [n_envs] = ({n_envs},), not {np.shape(frequency)}')
+            self.frequency = torch.as_tensor(np.asarray(frequency), dtype=torch.float32, device=device).contiguous()      # [n_envs]
+        other = np.array([t != 'position' for t in model.actuator_tags[:nu]], bool)
+        for name, rows in (('amplitude_env', amplitude_env), ('phase_lag_env', phase_lag_env)):
+            if rows is None:
+                continue
+            rows = np.asarray(rows, np.float64)
+            if rows.shape != (n_envs, nu):
+                raise ValueError(f'{name}: expected shape [n_envs, nu] = ({n_envs}, {nu}), not {rows.shape}')
+            if np.any(rows[:, other] != 0):
+                raise ValueError(f'{name}: entries of non-position actuators must be 0')
+            if name == 'amplitude_env':
+                amp = rows
+            else:
+                lag = rows
+        self.amplitude = torch.as_tensor(amp, dtype=torch.float32, device=device).contiguous()      # [nu] or [n_envs, nu]
+        self.phase_lag = torch.as_tensor(lag, dtype=torch.float32, device=device).contiguous()      # [nu] or [n_envs, nu]
+        self.env_phase = torch.as_tensor(env_phase, dtype=torch.float32, device=device)  # [n_envs]
         self._pos_idx = torch.as_tensor([a for a in range(model.nu) if model.actuator_tags[a] == 'position'],
                                         device=device)
 
     def positions(self, iteration, time, timestep):
-        cyc = (self.frequency*time) % 1.0
-        arg = (2*math.pi*cyc) + self.env_phase[:, None] - self.phase_lag[None, self._pos_idx]
-        return self.amplitude[None, self._pos_idx]*torch.sin(arg)
+        if torch.is_tensor(self.frequency):      # the env's own clock, in fp64 like the device's (fmj_stage_q.inc)
+            cyc = torch.remainder(self.frequency.to(torch.float64)*time, 1.0)
+            turn = (2*math.pi*cyc).to(torch.float32)[:, None]
+        else:
+            cyc = (self.frequency*time) % 1.0
+            turn = (2*math.pi*cyc)
+        rows = lambda t: t[:, self._pos_idx] if t.dim() == 2 else t[None, self._pos_idx]
+        arg = turn + self.env_phase[:, None] - rows(self.phase_lag)
+        return rows(self.amplitude)*torch.sin(arg)
 
 
 class OscillatorNetwork:
@@ -152,11 +187,16 @@ class NetworkController(AnimatController):
     """AnimatController (reference task.py:292-346) whose joint position commands come from an OscillatorNetwork
     integrated on the device by ``fmj_cpg_tape``.  ``fusable``: a chunk of the fused loop asks for its
     ctrl tape up front (``ctrl_tape``), so no host work or host->device copy remains per step.  ``drive`` ([n_envs],
-    optional) scales the intrinsic frequencies per env."""
+    optional) scales the intrinsic frequencies per env.  ``env_params`` gives every env its own numbers on the network's topology
+    (``fmj_cpg_tape_ex``): a dict with any of ``frequency``, ``rate``, ``amplitude`` ([n_envs, n_osc]), ``conn_weight``,
+    ``conn_bias`` ([n_envs, n_conn], in the order of ``network``'s connection list), ``out_gain``, ``out_offset`` ([n_envs, nu]);
+    an entry left out keeps the network's shared values."""
     fusable = True
     tape = True
+    ENV_PARAMS = dict(frequency='n_osc', rate='n_osc', amplitude='n_osc', conn_weight='n_conn', conn_bias='n_conn', out_gain='nu',
+                      out_offset='nu')
 
-    def __init__(self, model, network, n_envs, env_phase=None, drive=None, device='cuda:0', timestep=None):
+    def __init__(self, model, network, n_envs, env_phase=None, drive=None, device='cuda:0', timestep=None, env_params=None):
         from . import _lib
         names = [model.joint_names[model.actuator_jntid[a]] for a in range(model.nu)
                  if model.actuator_tags[a] == 'position']
@@ -186,6 +226,17 @@ class NetworkController(AnimatController):
         self._pos_idx = torch.as_tensor([a for a in range(model.nu) if model.actuator_tags[a] == 'position'],
                                         device=self.device)
         self._tape = None
+        self.env_params = {}      # name of fmj_cpg_env_params -> [n_envs, n] fp32 device tensor
+        for k, v in (env_params or {}).items():
+            if k not in self.ENV_PARAMS:
+                raise ValueError(f'env_params: unknown entry {k!r} (one of {sorted(self.ENV_PARAMS)})')
+            v = np.asarray(v, np.float64)
+            width = getattr(network, self.ENV_PARAMS[k])
+            if v.shape != (n_envs, width):
+                raise ValueError(f'env_params[{k!r}]: expected shape [n_envs, {self.ENV_PARAMS[k]}] = ({n_envs}, {width}), not {v.shape}')
+            if k == 'frequency':      # rad/s, rounded once as fmj_cpg_create rounds the shared value
+                k, v = 'omega', np.float32(2*np.pi*v)
+            self.env_params[k] = torch.as_tensor(v, dtype=torch.float32, device=self.device).contiguous()
 
     def __del__(self):
         try:
@@ -211,10 +262,18 @@ class NetworkController(AnimatController):
         if self._tape is None or self._tape.shape[0] < n_steps:
             self._tape = torch.empty(n_steps, self.n_envs, self.nu, dtype=torch.float32, device=self.device)
         tape = self._tape[:n_steps]
-        _lib.check(self._lib.fmj_cpg_tape(self._ctx, self.n_envs, n_steps, self.timestep, self.phase.data_ptr(),
-                                          self.amp.data_ptr(), self.damp.data_ptr(),
-                                          None if self.drive is None else self.drive.data_ptr(), tape.data_ptr(),
-                                          ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        drive = None if self.drive is None else self.drive.data_ptr()
+        if not self.env_params:
+            _lib.check(self._lib.fmj_cpg_tape(self._ctx, self.n_envs, n_steps, self.timestep, self.phase.data_ptr(),
+                                              self.amp.data_ptr(), self.damp.data_ptr(), drive, tape.data_ptr(), stream))
+            return tape
+        p = _lib.CCpgEnvParams(ctypes.sizeof(_lib.CCpgEnvParams), 0)
+        p.drive = drive
+        for k, t in self.env_params.items():
+            setattr(p, k, t.data_ptr())
+        _lib.check(self._lib.fmj_cpg_tape_ex(self._ctx, self.n_envs, n_steps, self.timestep, self.phase.data_ptr(),
+                                             self.amp.data_ptr(), self.damp.data_ptr(), ctypes.byref(p), tape.data_ptr(), stream))
         return tape
 
     def positions(self, iteration, time, timestep):

@@ -403,13 +403,16 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
         float asum = 0.f, cbase = 0.f;
         const int controller = FUSED ? A.controller : 0;
         if (controller == 1) {
-          double cyc = (double)A.w_freq * ((double)it * ((double)M.h * (double)S_sub));
+          const float wfreq = A.w_freq_env ? gptr(A.w_freq_env)[env] : A.w_freq;      // the env's own frequency (fmj_fused_ext), else the shared one
+          double cyc = (double)wfreq * ((double)it * ((double)M.h * (double)S_sub));
           cyc -= floor(cyc);
           cbase = fmaf(6.283185307179586f, (float)cyc, gptr(A.w_env)[env]);
         }
         const float AS1* ctrl_row = A.ctrl ? gptr(A.ctrl) + (size_t)itm * A.ctrl_step_stride + (size_t)env * nu : nullptr;
         const bool no_act = A.disable_actuation != 0;
         const int4 d_act = as_int4(DT2(mydof, 2));
+        const float AS1* const w_amp = gptr(A.w_amp) + (size_t)env * A.w_amp_stride;      // the env's rows (stride 0: the shared row)
+        const float AS1* const w_lag = gptr(A.w_lag) + (size_t)env * A.w_lag_stride;
 #pragma unroll
         for (int a = 0; a < 4; a++) {                 // mj_fwdActuation, joint transmission
           if (a < d_act.y) {
@@ -417,7 +420,7 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
             const float4 p = AT2(ai, 0), lim = AT2(ai, 1);
             const int src = __float_as_int(AT2(ai, 2).x);
             float c;
-            if (controller == 1) { const float amp = gptr(A.w_amp)[src]; c = amp != 0.f ? amp * sinf(cbase - gptr(A.w_lag)[src]) : 0.f; }
+            if (controller == 1) { const float amp = w_amp[src]; c = amp != 0.f ? amp * sinf(cbase - w_lag[src]) : 0.f; }
             else c = ctrl_row ? ctrl_row[src] : 0.f;
             if (controller == 1 && last && live && A.ctrl_out) gptr(A.ctrl_out)[(size_t)env * nu + src] = c;
             c = fminf(fmaxf(c, lim.x), lim.y);

@@ -165,6 +165,10 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
 #define OPT_NO_ACT (!LEAN && A.disable_actuation != 0)
 #define OPT_STIFFNESS (!LEAN && M.any_stiffness)
 #define OPT_INTEGRATE (LEAN || A.integrate)
+  // per-env wave parameters (fmj_fused_ext): never in a LEAN launch, whose wave controller reads the shared row and A.w_freq
+#define OPT_WFREQ_ENV (LEAN ? (const float*)nullptr : A.w_freq_env)
+#define OPT_WAMP_STRIDE (LEAN ? 0ll : A.w_amp_stride)
+#define OPT_WLAG_STRIDE (LEAN ? 0ll : A.w_lag_stride)
   const int lane = threadIdx.x;
   const bool upper = lane >= 32;
   const int sl = lane & 31;
@@ -222,7 +226,8 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
   int steps_done = 0;
 
   // Actuators of this lane's joint (<= 4, sorted by model order).  A slot is dead in this launch when it cannot produce
-  // a force: no bias and either no gain or nothing driving it (wave controller: zero amplitude; tape: no tape).  The
+  // a force: no bias and either no gain or nothing driving it (wave controller: zero amplitude IN THIS LANE'S ENV - with per-env
+  // amplitudes the halves of a wave may disagree, live_mask is a per-lane fact and a dead slot adds an exact 0; tape: no tape).  The
   // first live slot stays in registers; more live slots (wave-uniform count NL) are re-read from the tables each step.
   const int4 d_act = as_int4(DT2(mydof, 2));              // first actuator, count, joint sensor slot, dof parent
   const int act_n = isd ? d_act.y : 0;
@@ -238,7 +243,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
         const float4 p = AT2(ai, 0), lim = AT2(ai, 1);
         const int src = __float_as_int(AT2(ai, 2).x);
         float amp = 0.f, lag = 0.f;
-        if (controller == 1) { amp = gptr(A.w_amp)[src]; lag = gptr(A.w_lag)[src]; }
+        if (controller == 1) { amp = gptr(A.w_amp)[(size_t)env * OPT_WAMP_STRIDE + src]; lag = gptr(A.w_lag)[(size_t)env * OPT_WLAG_STRIDE + src]; }
         const bool biased = p.y != 0.f || p.z != 0.f || p.w != 0.f;
         const bool driven = controller == 1 ? amp != 0.f : have_tape;
         const bool clamp0 = lim.x > 0.f || lim.y < 0.f || lim.z > 0.f || lim.w < 0.f;   // a range without 0
@@ -264,6 +269,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
   const long long r_offl_ = (long long)env * M.n_links * FMJ_LINK_SIZE, r_offx_ = (long long)env * M.n_xfrc * FMJ_XFRC_SIZE,
                   r_offj_ = (long long)env * M.n_joints * FMJ_JOINT_SIZE;
   const float r_wenv_ = (FUSED && OPT_CONTROLLER == 1) ? gptr(A.w_env)[env] : 0.f;
+  const float r_wfreq_ = (RES2_ && FUSED && OPT_CONTROLLER == 1 && OPT_WFREQ_ENV) ? gptr(A.w_freq_env)[env] : 0.f;      // the env's own frequency: resident in the 256-register build only
   // the env phase in revolutions, rounded once per launch in EVERY build (pinf keeps the product from being contracted into the
   // add of a step in the builds that would otherwise reload the phase there: the register builds must agree bitwise)
   const float r_wturn_ = pinf(0.15915494309189535f * r_wenv_);
@@ -538,7 +544,8 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
         float asum = 0.f, cbase = 0.f, cturn = 0.f;
         const int controller = OPT_CONTROLLER;
         if (controller == 1) {
-          double cyc = (double)A.w_freq * ((double)it * ((double)M.h * (double)S_sub));   // task.py:290: time = iteration * timestep (of an iteration)
+          const float wfreq = OPT_WFREQ_ENV ? (RES2_ ? r_wfreq_ : gptr(A.w_freq_env)[env]) : A.w_freq;      // the env's own frequency (fmj_fused_ext), else the shared one
+          double cyc = (double)wfreq * ((double)it * ((double)M.h * (double)S_sub));   // task.py:290: time = iteration * timestep (of an iteration)
           cyc -= floor(cyc);
           const float wenv = RES2_ ? r_wenv_ : gptr(A.w_env)[env];
           cbase = fmaf(6.283185307179586f, (float)cyc, wenv);
@@ -568,7 +575,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
             const float4 p = AT2(ai, 0), lim = AT2(ai, 1);
             const int src = __float_as_int(AT2(ai, 2).x);
             float c;
-            if (controller == 1) { const float amp = gptr(A.w_amp)[src]; c = amp != 0.f ? amp * sinf(cbase - gptr(A.w_lag)[src]) : 0.f; }
+            if (controller == 1) { const float amp = gptr(A.w_amp)[(size_t)env * OPT_WAMP_STRIDE + src]; c = amp != 0.f ? amp * sinf(cbase - gptr(A.w_lag)[(size_t)env * OPT_WLAG_STRIDE + src]) : 0.f; }
             else c = ctrl_row ? ctrl_row[src] : 0.f;
             if (controller == 1 && last && live && A.ctrl_out) gptr(A.ctrl_out)[(size_t)env * nu + src] = c;   // what task.py:288-346 leaves in physics.data.ctrl
             c = fminf(fmaxf(c, lim.x), lim.y);
@@ -840,4 +847,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
 #undef OPT_NO_ACT
 #undef OPT_STIFFNESS
 #undef OPT_INTEGRATE
+#undef OPT_WFREQ_ENV
+#undef OPT_WAMP_STRIDE
+#undef OPT_WLAG_STRIDE
 }

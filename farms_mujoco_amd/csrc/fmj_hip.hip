@@ -190,7 +190,9 @@ struct StepArgs {
   float inv_meters, inv_velocity, inv_angvel, inv_torques, newtons, torques;
   // wave controller
   const float* w_amp; const float* w_lag; const float* w_env; float w_freq;
-  float* ctrl_out;            // fused + wave controller: ctrl of the launch's last step (physics.data.ctrl)
+  // per-env wave parameters (fmj_fused_ext): the env's own frequency [n_envs] or NULL; element stride between the envs' rows of w_amp / w_lag (0: one shared row)
+  const float* w_freq_env; long long w_amp_stride, w_lag_stride;
+  float* ctrl_out;           // fused + wave controller: ctrl of the launch's last step (physics.data.ctrl)
   const int* env_order;       // one-env kernel: env of workgroup b (NULL: b); heavier envs first shortens a launch's tail
   int* resume;                // [n_envs] or NULL: steps of this launch already completed per env (written by fmj_cons2.inc, read by the one-env kernel)
   float* dbg_H; float* dbg_qfrc;   // fmj_forward_debug: rows of H = M + diag(armature + h damping) [n_envs][nv][rs], qfrc_smooth [n_envs][nv]
@@ -2090,7 +2092,7 @@ static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream) 
     const bool rare = (fused && A.substeps > 1) || D.implicitfast;
     // the launch shape the lean build has folded in (fmj_dual2.inc, LEAN); anything else runs the generic build
     const bool lean = c->dual_lean && fused && !rare && !A.rows_ahead && A.controller == 1 && A.do_readout && A.do_drag && !A.disable_actuation &&
-                      !D.any_stiffness && !A.xfrc_applied_out;
+                      !D.any_stiffness && !A.xfrc_applied_out && !A.w_freq_env && !A.w_amp_stride && !A.w_lag_stride;      // per-env wave fields: the generic builds
     c->dual_last = lean ? FMJ_DUAL_BUILD_LEAN : (rare ? FMJ_DUAL_BUILD_RARE : FMJ_DUAL_BUILD_GENERIC);
     return launch("dual step kernel", step_kernel(D.rs, fused, dual[lean ? 2 : rare][c->dual_wps - 2]), pairs, 64, c->lds_bytes_dual2, stream, D, A);
   }
@@ -3021,7 +3023,9 @@ int fmj_step_debug(fmj_ctx* c, const fmj_data* d, float* efc_rows, float* pgs_im
   return launch_step(c, false, A, stream);
 }
 
-int fmj_step_fused(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, void* stream) {
+int fmj_step_fused(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, void* stream) { return fmj_step_fused_ex(c, d, a, nullptr, stream); }
+
+int fmj_step_fused_ex(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, const fmj_fused_ext* ext, void* stream) {
   if (!c || !a) return set_err(FMJ_ERR_ARG, "fmj_step_fused: NULL argument");
   StepArgs A; int rc = fill_data(c, d, &A, true); if (rc) return rc;
   if (a->n_steps < 0 || a->buffer_size < 1) return set_err(FMJ_ERR_ARG, "fmj_step_fused: bad n_steps/buffer_size");
@@ -3032,6 +3036,13 @@ int fmj_step_fused(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, void*
   if (a->do_drag && (!a->rows_base.xfrc || c->dm.ns == 0)) return set_err(FMJ_ERR_ARG, "fmj_step_fused: drag needs xfrc rows and fmj_set_swimming");
   if (a->controller == 1 && (!a->wave.amplitude || !a->wave.phase_lag || !a->wave.env_phase)) return set_err(FMJ_ERR_ARG, "fmj_step_fused: wave controller arrays missing");
   if (a->controller != 0 && a->controller != 1) return set_err(FMJ_ERR_ARG, "fmj_step_fused: unknown controller");
+  if (ext) {
+    if (ext->size != (int32_t)sizeof(fmj_fused_ext)) return set_err(FMJ_ERR_ARG, "fmj_step_fused_ex: fmj_fused_ext.size is not sizeof(fmj_fused_ext)");
+    const bool per_env = ext->wave_frequency_env || ext->wave_amplitude_env_stride || ext->wave_phase_lag_env_stride;
+    if (per_env && a->controller != 1) return set_err(FMJ_ERR_ARG, "fmj_step_fused_ex: per-env wave parameters need the wave controller (controller = 1)");
+    for (const int64_t s : {ext->wave_amplitude_env_stride, ext->wave_phase_lag_env_stride})
+      if (s != 0 && s < c->nu) return set_err(FMJ_ERR_ARG, "fmj_step_fused_ex: a per-env stride must be 0 (one shared row) or >= nu");
+  }
   A.integrate = 1;
   A.substeps = a->substeps > 1 ? a->substeps : 1; A.sub_links = (A.substeps > 1 && a->substep_links) ? 1 : 0; A.n_it_total = a->n_iterations > 0 ? a->n_iterations : 0;
   if ((long long)a->n_steps * A.substeps > 0x7fffffffLL) return set_err(FMJ_ERR_ARG, "fmj_step_fused: n_steps * substeps overflows");
@@ -3046,6 +3057,7 @@ int fmj_step_fused(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, void*
   }
   fill_units(&A, &a->units); fill_water(&A, &a->water);
   A.w_amp = a->wave.amplitude; A.w_lag = a->wave.phase_lag; A.w_env = a->wave.env_phase; A.w_freq = a->wave.frequency;
+  if (ext) { A.w_freq_env = ext->wave_frequency_env; A.w_amp_stride = ext->wave_amplitude_env_stride; A.w_lag_stride = ext->wave_phase_lag_env_stride; }
   A.ctrl_out = a->controller == 1 ? a->ctrl_out : nullptr;
   if (a->rows_ahead) {
     if (c->path != PATH_TWO_ENV || A.substeps != 1) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: rows_ahead needs the two-env unconstrained step kernel and substeps = 1 (write the rows with fmj_before_step instead)");
@@ -3151,22 +3163,27 @@ struct fmj_cpg {
   int device, n_osc, n_conn, nu, max_deg;
   float4* osc;      // [n_osc] 2 pi f, a, R, -
   int* row;         // [n_osc + 1] CSR by target oscillator
-  float4* conn;     // [n_conn] from (bits), w, phi, -
+  float4* conn;     // [n_conn] from (bits), w, phi, -   in CSR order
+  int* perm;        // [n_conn] CSR slot -> index in the descriptor's connection list (the order of fmj_cpg_env_params::conn_*)
   float4* out;      // [nu] a (bits), b (bits), gain, offset
 };
 
-__global__ void __launch_bounds__(64) fmj_cpg_kernel(const int n_osc, const int nu, const float4* __restrict__ osc,
-                                                     const int* __restrict__ row, const float4* __restrict__ conn,
+// the env's own parameters (fmj_cpg_env_params; DEVICE pointers by value): a NULL array is the shared table, decided per array for the whole wave
+struct CpgEnv { const float *drive, *omega, *rate, *amplitude, *conn_weight, *conn_bias, *out_gain, *out_offset; };
+
+__global__ void __launch_bounds__(64) fmj_cpg_kernel(const int n_osc, const int n_conn, const int nu, const float4* __restrict__ osc,
+                                                     const int* __restrict__ row, const float4* __restrict__ conn, const int* __restrict__ perm,
                                                      const float4* __restrict__ outp, const int n_envs, const int n_steps,
                                                      const float h, float* phase, float* amp, float* damp,
-                                                     const float* drive, float* tape) {
+                                                     const CpgEnv E, float* tape) {
   __shared__ float TH[64], RR[64];
   const int env = blockIdx.x, lane = threadIdx.x;
   const bool iso = lane < n_osc;
   const int ol = iso ? lane : 0;
   const float4 o = osc[ol];
-  const float dr = drive ? drive[env] : 1.f;
-  const float omega = o.x * dr, a = o.y, R = o.z;
+  const size_t eo = (size_t)env * n_osc + ol, ec = (size_t)env * n_conn, eu = (size_t)env * nu;
+  const float dr = E.drive ? E.drive[env] : 1.f;
+  const float omega = (E.omega ? E.omega[eo] : o.x) * dr, a = E.rate ? E.rate[eo] : o.y, R = E.amplitude ? E.amplitude[eo] : o.z;
   const int k0 = row[ol], k1 = iso ? row[ol + 1] : k0;
   float th = iso ? phase[(size_t)env * n_osc + lane] : 0.f;
   float r = iso ? amp[(size_t)env * n_osc + lane] : 0.f;
@@ -3176,7 +3193,9 @@ __global__ void __launch_bounds__(64) fmj_cpg_kernel(const int n_osc, const int 
     __syncthreads();
     float* t = tape + ((size_t)s * n_envs + env) * nu;
     for (int u = lane; u < nu; u += 64) {
-      const float4 q = outp[u];
+      float4 q = outp[u];
+      if (E.out_gain) q.z = E.out_gain[eu + u];
+      if (E.out_offset) q.w = E.out_offset[eu + u];
       const int ia = __float_as_int(q.x), ib = __float_as_int(q.y);
       float v = q.w;
       if (ia >= 0) v += q.z * RR[ia] * (1.f + cosf(TH[ia]));
@@ -3185,7 +3204,9 @@ __global__ void __launch_bounds__(64) fmj_cpg_kernel(const int n_osc, const int 
     }
     float dth = omega;
     for (int k = k0; k < k1; k++) {
-      const float4 c = conn[k];
+      float4 c = conn[k];
+      if (E.conn_weight) c.y = E.conn_weight[ec + perm[k]];
+      if (E.conn_bias) c.z = E.conn_bias[ec + perm[k]];
       const int j = __float_as_int(c.x);
       dth = fmaf(RR[j] * c.y, sinf(TH[j] - th - c.z), dth);
     }
@@ -3209,21 +3230,23 @@ int fmj_cpg_create(const fmj_cpg_desc* d, int32_t device, fmj_cpg** out) {
     if (d->out_a[u] >= d->n_osc || d->out_b[u] >= d->n_osc) return set_err(FMJ_ERR_ARG, "fmj_cpg_create: output oscillator out of range");
   HIP_TRY(hipSetDevice(device));
   std::vector<float4> osc(d->n_osc), conn(d->n_conn ? d->n_conn : 1), outp(d->nu);
-  std::vector<int> row(d->n_osc + 1, 0);
+  std::vector<int> row(d->n_osc + 1, 0), perm(d->n_conn ? d->n_conn : 1, 0);
   for (int i = 0; i < d->n_osc; i++) osc[i] = make_float4((float)(6.283185307179586 * d->frequency[i]), (float)d->rate[i], (float)d->amplitude[i], 0.f);
   for (int k = 0; k < d->n_conn; k++) row[d->conn_to[k] + 1]++;
   for (int i = 0; i < d->n_osc; i++) row[i + 1] += row[i];
   { std::vector<int> fill(row.begin(), row.end() - 1);
-    for (int k = 0; k < d->n_conn; k++) conn[fill[d->conn_to[k]]++] = make_float4(ibits(d->conn_from[k]), (float)d->conn_weight[k], (float)d->conn_bias[k], 0.f); }
+    for (int k = 0; k < d->n_conn; k++) { const int s = fill[d->conn_to[k]]++; perm[s] = k; conn[s] = make_float4(ibits(d->conn_from[k]), (float)d->conn_weight[k], (float)d->conn_bias[k], 0.f); } }
   for (int u = 0; u < d->nu; u++) outp[u] = make_float4(ibits(d->out_a[u]), ibits(d->out_b[u]), (float)d->out_gain[u], (float)d->out_offset[u]);
   fmj_cpg* c = new fmj_cpg();
   c->device = device; c->n_osc = d->n_osc; c->n_conn = d->n_conn; c->nu = d->nu;
-  c->osc = nullptr; c->row = nullptr; c->conn = nullptr; c->out = nullptr;
+  c->osc = nullptr; c->row = nullptr; c->conn = nullptr; c->perm = nullptr; c->out = nullptr;
   bool ok = hipMalloc((void**)&c->osc, osc.size() * sizeof(float4)) == hipSuccess && hipMalloc((void**)&c->row, row.size() * sizeof(int)) == hipSuccess &&
-            hipMalloc((void**)&c->conn, conn.size() * sizeof(float4)) == hipSuccess && hipMalloc((void**)&c->out, outp.size() * sizeof(float4)) == hipSuccess;
+            hipMalloc((void**)&c->conn, conn.size() * sizeof(float4)) == hipSuccess && hipMalloc((void**)&c->out, outp.size() * sizeof(float4)) == hipSuccess &&
+            hipMalloc((void**)&c->perm, perm.size() * sizeof(int)) == hipSuccess;
   ok = ok && hipMemcpy(c->osc, osc.data(), osc.size() * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(c->row, row.data(), row.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(c->conn, conn.data(), conn.size() * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy(c->perm, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(c->out, outp.data(), outp.size() * sizeof(float4), hipMemcpyHostToDevice) == hipSuccess;
   if (!ok) { fmj_cpg_destroy(c); return set_err(FMJ_ERR_HIP, "fmj_cpg_create: device allocation failed"); }
   *out = c;
@@ -3236,17 +3259,28 @@ void fmj_cpg_destroy(fmj_cpg* c) {
   if (c->osc) (void)hipFree(c->osc);
   if (c->row) (void)hipFree(c->row);
   if (c->conn) (void)hipFree(c->conn);
+  if (c->perm) (void)hipFree(c->perm);
   if (c->out) (void)hipFree(c->out);
   delete c;
 }
 
 int fmj_cpg_tape(fmj_cpg* c, int32_t n_envs, int32_t n_steps, double timestep, float* phase, float* amp, float* damp,
                  const float* drive, float* ctrl_tape, void* stream) {
+  fmj_cpg_env_params p = {};
+  p.size = (int32_t)sizeof p; p.drive = drive;
+  return fmj_cpg_tape_ex(c, n_envs, n_steps, timestep, phase, amp, damp, &p, ctrl_tape, stream);
+}
+
+int fmj_cpg_tape_ex(fmj_cpg* c, int32_t n_envs, int32_t n_steps, double timestep, float* phase, float* amp, float* damp,
+                    const fmj_cpg_env_params* p, float* ctrl_tape, void* stream) {
   if (!c || n_envs <= 0 || n_steps < 0 || !phase || !amp || !damp || !ctrl_tape) return set_err(FMJ_ERR_ARG, "fmj_cpg_tape: bad argument");
+  if (p && p->size != (int32_t)sizeof(fmj_cpg_env_params)) return set_err(FMJ_ERR_ARG, "fmj_cpg_tape_ex: fmj_cpg_env_params.size is not sizeof(fmj_cpg_env_params)");
   if (n_steps == 0) return FMJ_OK;
+  CpgEnv E = {};
+  if (p) E = CpgEnv{p->drive, p->omega, p->rate, p->amplitude, p->conn_weight, p->conn_bias, p->out_gain, p->out_offset};
   HIP_TRY(hipSetDevice(c->device));
-  hipLaunchKernelGGL(fmj_cpg_kernel, dim3(n_envs), dim3(64), 0, (hipStream_t)stream, c->n_osc, c->nu, c->osc, c->row, c->conn, c->out,
-                     n_envs, n_steps, (float)timestep, phase, amp, damp, drive, ctrl_tape);
+  hipLaunchKernelGGL(fmj_cpg_kernel, dim3(n_envs), dim3(64), 0, (hipStream_t)stream, c->n_osc, c->n_conn, c->nu, c->osc, c->row, c->conn, c->perm, c->out,
+                     n_envs, n_steps, (float)timestep, phase, amp, damp, E, ctrl_tape);
   HIP_TRY(hipGetLastError());
   return FMJ_OK;
 }

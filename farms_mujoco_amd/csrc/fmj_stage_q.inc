@@ -35,9 +35,12 @@
         }
         float asum = 0.f;
         float cbase = 0.f;
+        const float AS1* const w_amp = gptr(A.w_amp) + (size_t)env * A.w_amp_stride;      // the env's rows (stride 0: the shared row)
+        const float AS1* const w_lag = gptr(A.w_lag) + (size_t)env * A.w_lag_stride;
         if (FUSED && A.controller == 1) {
           // phase in cycles kept in fp64 so long runs keep the argument exact (task.py:290: time = iteration*timestep)
-          double cyc = (double)A.w_freq * ((double)it * ((double)M.h * (double)S_sub));   // task.py:290: time = iteration * timestep (of an iteration)
+          const float wfreq = A.w_freq_env ? gptr(A.w_freq_env)[env] : A.w_freq;      // the env's own frequency (fmj_fused_ext), else the shared one
+          double cyc = (double)wfreq * ((double)it * ((double)M.h * (double)S_sub));   // task.py:290: time = iteration * timestep (of an iteration)
           cyc -= floor(cyc);
           cbase = 6.283185307179586f * (float)cyc + gptr(A.w_env)[env];
         }
@@ -47,7 +50,7 @@
             const int ai = d_act.x + a, src = __float_as_int(ATAB(ai, 2).x);
             const float4 p = ATAB(ai, 0), lim = ATAB(ai, 1);
             float c;
-            if (FUSED && A.controller == 1) { const float amp = gptr(A.w_amp)[src]; c = amp != 0.f ? amp * sinf(cbase - gptr(A.w_lag)[src]) : 0.f; }
+            if (FUSED && A.controller == 1) { const float amp = w_amp[src]; c = amp != 0.f ? amp * sinf(cbase - w_lag[src]) : 0.f; }
             else c = A.ctrl ? gptr(A.ctrl)[(size_t)itm * A.ctrl_step_stride + (size_t)env * nu + src] : 0.f;      // one ctrl row per iteration
             c = fminf(fmaxf(c, lim.x), lim.y);
             float f = p.x * c + p.y + p.z * qj + p.w * qd;
@@ -64,8 +67,8 @@
 #pragma unroll
           for (int a = 0; a < 4; a++) if (a < d_act.y) {
             const int src = __float_as_int(ATAB(d_act.x + a, 2).x);
-            const float amp = gptr(A.w_amp)[src];
-            gptr(A.ctrl_out)[(size_t)env * nu + src] = amp != 0.f ? amp * sinf(cbase - gptr(A.w_lag)[src]) : 0.f;
+            const float amp = w_amp[src];
+            gptr(A.ctrl_out)[(size_t)env * nu + src] = amp != 0.f ? amp * sinf(cbase - w_lag[src]) : 0.f;
           }
         }
         if (last) {

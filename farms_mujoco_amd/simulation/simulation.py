@@ -22,6 +22,45 @@ def extract_sub_dict(dictionary: Dict, keys: List[str]) -> Dict:
     return {key: dictionary.pop(key) for key in keys if key in dictionary}
 
 
+def _wave_args(a, c, n_envs, nu):
+    """Fill ``a.wave`` (fmj_wave_controller) from a WaveController and return the fmj_fused_ext of its per-env fields, or None when
+    every parameter is shared (then the launch is a plain fmj_step_fused).  A field is per-env by its shape: ``frequency`` a tensor
+    [n_envs] instead of a float, ``amplitude`` / ``phase_lag`` [n_envs, nu] instead of [nu]."""
+    per_env = False
+    ext = _lib.CFusedExt(ctypes.sizeof(_lib.CFusedExt), 0)
+    for name, field in (('amplitude', 'wave_amplitude_env_stride'), ('phase_lag', 'wave_phase_lag_env_stride')):
+        t = getattr(c, name)
+        if t.dim() == 2:
+            if tuple(t.shape) != (n_envs, nu) or t.stride(1) != 1:
+                raise ValueError(f'WaveController.{name}: per-env rows must be [n_envs, nu] = [{n_envs}, {nu}] with contiguous rows, not {tuple(t.shape)}')
+            setattr(ext, field, t.stride(0))
+            per_env = True
+        elif tuple(t.shape) != (nu,):
+            raise ValueError(f'WaveController.{name}: expected [nu] = [{nu}] or [n_envs, nu] = [{n_envs}, {nu}], not {tuple(t.shape)}')
+        setattr(a.wave, name, t.data_ptr())
+    a.wave.env_phase = c.env_phase.data_ptr()
+    if torch.is_tensor(c.frequency):
+        if tuple(c.frequency.shape) != (n_envs,) or not c.frequency.is_contiguous():
+            raise ValueError(f'WaveController.frequency: expected a scalar or [n_envs] = [{n_envs}], not {tuple(c.frequency.shape)}')
+        a.wave.frequency = 0.0
+        ext.wave_frequency_env = c.frequency.data_ptr()
+        per_env = True
+    else:
+        a.wave.frequency = c.frequency
+    return ext if per_env else None
+
+
+def _launch_fused(phys, cd, a, ext):
+    """fmj_step_fused, or fmj_step_fused_ex when the controller has a per-env field (include/fmj.h)."""
+    stream = ctypes.c_void_p(torch.cuda.current_stream(phys.device).cuda_stream)
+    if ext is None:
+        _lib.check(phys._lib.fmj_step_fused(phys._ctx, ctypes.byref(cd), ctypes.byref(a), stream))
+    else:
+        if not (hasattr(phys._lib, 'fmj_step_fused_ex') and phys._lib.fmj_step_fused_ex.argtypes):      # an A/B base build (FMJ_SO)
+            raise _lib.FmjError('this libfmj_hip.so has no fmj_step_fused_ex: per-env wave parameters need a current build')
+        _lib.check(phys._lib.fmj_step_fused_ex(phys._ctx, ctypes.byref(cd), ctypes.byref(a), ctypes.byref(ext), stream))
+
+
 class Simulation:
     """Batched simulation with the reference's API shape (reference simulation.py:33-213).
 
@@ -140,17 +179,16 @@ class Simulation:
                 a.water = swim[0].handler.water.as_c(use_buoyancy=swim[0].handler.buoyancy)
         c = task._controller
         cd = phys._cdata()
+        ext = None
         if getattr(c, 'tape', False):
             tape = c.ctrl_tape(1)
             a.controller, a.ctrl_step_stride = 0, tape.stride(0)
             cd.ctrl = tape.data_ptr()
         else:
             a.controller = 1
-            a.wave.amplitude, a.wave.phase_lag, a.wave.env_phase = c.amplitude.data_ptr(), c.phase_lag.data_ptr(), c.env_phase.data_ptr()
-            a.wave.frequency = c.frequency
+            ext = _wave_args(a, c, phys.n_envs, phys.model.nu)
             a.ctrl_out = phys.data.ctrl.data_ptr()
-        _lib.check(phys._lib.fmj_step_fused(phys._ctx, ctypes.byref(cd), ctypes.byref(a),
-                                            ctypes.c_void_p(torch.cuda.current_stream(phys.device).cuda_stream)))
+        _launch_fused(phys, cd, a, ext)
 
     def step_fused(self, n_steps: int):
         """Run ``n_steps`` full iterations (``substeps`` physics steps each) inside ONE launch (fmj_step_fused): ring-buffer
@@ -184,6 +222,7 @@ class Simulation:
         a.units = task.units.as_c()
         c = task._controller
         cd = phys._cdata()
+        ext = None
         if c is not None and getattr(c, 'tape', False):        # device controller that hands over a ctrl tape
             tape = c.ctrl_tape(n_steps)
             a.controller = 0
@@ -191,9 +230,7 @@ class Simulation:
             cd.ctrl = tape.data_ptr()
         elif c is not None:
             a.controller = 1
-            a.wave.amplitude, a.wave.phase_lag, a.wave.env_phase = (c.amplitude.data_ptr(), c.phase_lag.data_ptr(),
-                                                                     c.env_phase.data_ptr())
-            a.wave.frequency = c.frequency
+            ext = _wave_args(a, c, phys.n_envs, phys.model.nu)
             a.ctrl_out = phys.data.ctrl.data_ptr()       # callbacks reading physics.data.ctrl see the last step's command
         if phys.has_constraints and self.order_by_contacts:
             # envs with the most contacts (the slowest to step) are launched first instead of wherever they sit; the two-env constraint
@@ -201,8 +238,7 @@ class Simulation:
             # for both; pairing the heaviest with the lightest instead was measured: no difference in the launch time)
             self._env_order = torch.argsort(phys.data.ncon, descending=True, stable=True).to(torch.int32)
             a.env_order = self._env_order.data_ptr()
-        _lib.check(phys._lib.fmj_step_fused(phys._ctx, ctypes.byref(cd), ctypes.byref(a),
-                                            ctypes.c_void_p(torch.cuda.current_stream(phys.device).cuda_stream)))
+        _launch_fused(phys, cd, a, ext)
         # the counters as n_steps * substeps calls of after_step leave them (task.py:351-355: with sub-steps the iteration is
         # advanced one sub-step early, except that nothing follows the launch's last full step yet)
         task.sim_iteration += n_steps*task.substeps

@@ -499,6 +499,25 @@ typedef struct fmj_fused_args {
 
 int fmj_step_fused(fmj_ctx* ctx, const fmj_data* d, const fmj_fused_args* args, void* hip_stream);
 
+/* fmj_step_fused with per-environment parameters of the wave controller (additive: FMJ_ABI_VERSION stays 6, fmj_fused_args and
+ * fmj_wave_controller keep their layouts).  The reference's AnimatController belongs to ONE animat (task.py:288-346: step / positions per
+ * control step), so a batch of animats has one controller each; here every env may swim its own gait in the same launch - a parameter
+ * sweep or a CPG optimisation without a host-built ctrl tape, and with the wave controller's in-kernel fp64 clock:
+ *   ctrl[e][u] = amplitude[e][u] sin(2 pi frac(frequency[e] t) + env_phase[e] - phase_lag[e][u]).
+ * ext == NULL is fmj_step_fused (which is this call): the same path, the same bits, and so is an ext whose three fields are NULL / 0.
+ * A per-env field needs controller = 1 and a stride must be 0 or >= nu (FMJ_ERR_ARG otherwise, as for a size other than
+ * sizeof(fmj_fused_ext)); RK4 and fp64 contexts are refused as by fmj_step_fused.  Whether an actuator is driven (amplitude != 0) is
+ * then a fact of the env; ctrl_out receives each env's own last command.  Model tables stay shared.  A launch with a per-env field
+ * runs the generic build of the two-env kernel (fmj_dual_build_info: never the LEAN one). */
+typedef struct fmj_fused_ext {
+  int32_t size;                        /* = sizeof(fmj_fused_ext); anything else: FMJ_ERR_ARG */
+  int32_t reserved;                    /* 0 */
+  const float* wave_frequency_env;     /* [n_envs] DEVICE, Hz, or NULL: args->wave.frequency for all */
+  int64_t wave_amplitude_env_stride;   /* 0: args->wave.amplitude is [nu], shared; >= nu: it is [n_envs][stride] */
+  int64_t wave_phase_lag_env_stride;   /* the same for args->wave.phase_lag */
+} fmj_fused_ext;
+int fmj_step_fused_ex(fmj_ctx* ctx, const fmj_data* d, const fmj_fused_args* args, const fmj_fused_ext* ext, void* hip_stream);
+
 /* ---- on-device controller: a network of amplitude-controlled phase oscillators --------------------
  * The reference only defines the AnimatController interface (task.py:292-346: step/positions/torques/springrefs);
  * the oscillator networks themselves live in its callers (farms_amphibious). This is the batched device counterpart:
@@ -529,6 +548,26 @@ void fmj_cpg_destroy(fmj_cpg* cpg);
  * intrinsic frequencies per env; ctrl_tape: [n_steps][n_envs][nu] DEVICE fp32. */
 int fmj_cpg_tape(fmj_cpg* cpg, int32_t n_envs, int32_t n_steps, double timestep, float* phase, float* amp, float* damp,
                  const float* drive, float* ctrl_tape, void* hip_stream);
+/* fmj_cpg_tape with per-environment network parameters: every env integrates the descriptor's network (same oscillators, same
+ * connection topology, same outputs) with its own numbers - one AnimatController per animat, as the reference has it (task.py:288-346),
+ * for a batch.  fmj_cpg_tape(.., drive, ..) is this call with only `drive` set: the same bits.  p == NULL or a NULL array: the
+ * descriptor's shared values; the arithmetic and its order do not depend on where a value comes from, so env e of a per-env launch
+ * equals, bit for bit, a one-env network created from e's values.  conn_weight / conn_bias follow the ORDER OF THE DESCRIPTOR's
+ * connection list (fmj_cpg_create sorts the connections by target and keeps the permutation).  A size other than
+ * sizeof(fmj_cpg_env_params) is FMJ_ERR_ARG. */
+typedef struct fmj_cpg_env_params {     /* every array DEVICE fp32, NULL = the descriptor's shared value */
+  int32_t size, reserved;
+  const float* drive;        /* [n_envs] as fmj_cpg_tape */
+  const float* omega;        /* [n_envs][n_osc] rad/s (2 pi f, already rounded to fp32 by the caller) */
+  const float* rate;         /* [n_envs][n_osc] a_i */
+  const float* amplitude;    /* [n_envs][n_osc] R_i */
+  const float* conn_weight;  /* [n_envs][n_conn], in the ORDER OF THE DESCRIPTOR's connections */
+  const float* conn_bias;    /* [n_envs][n_conn], same order */
+  const float* out_gain;     /* [n_envs][nu] */
+  const float* out_offset;   /* [n_envs][nu] */
+} fmj_cpg_env_params;
+int fmj_cpg_tape_ex(fmj_cpg* cpg, int32_t n_envs, int32_t n_steps, double timestep, float* phase, float* amp, float* damp,
+                    const fmj_cpg_env_params* p, float* ctrl_tape, void* hip_stream);
 
 /* enum query so host code never hard-codes column integers: name is e.g. "LINK_COM_POS" */
 int fmj_sc(const char* name);

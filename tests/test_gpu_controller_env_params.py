@@ -1,0 +1,470 @@
+"""Per-environment parameters of the device controllers on the GPU (include/fmj.h: fmj_step_fused_ex / fmj_fused_ext and
+fmj_cpg_tape_ex / fmj_cpg_env_params): every env of a batch swims its own gait inside the fused launch.
+
+Small shapes: 5 envs (odd: the last wave's upper half is a copy), 12 iterations on a ring of 5 rows (the ring wraps), drag on with
+the surface cutting the animal and a current.  The per-env sets come from a seeded generator: frequency in [0.5, 2] Hz, amplitudes
+in [0, 0.4] with exact zeros placed so that the two envs of wave 0 disagree on which actuators are live, env 2 with every
+amplitude zero, lags in [-2 pi, 2 pi]."""
+import ctypes
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+N, T, RING = 5, 12, 5
+FMJ_ERR_ARG = 1
+
+
+def _relerr(a, b):      # the metric of tests/test_gpu_fused_parity.py
+    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
+    return np.abs(a - b).max()/max(np.abs(b).max(), 1e-12)
+
+
+def _model(kind, substeps=1):
+    import farms_mujoco_amd.model as mm
+    h = 1e-3/substeps
+    if kind == 'salamander':
+        return mm.salamander33(timestep=h)
+    if kind == 'centipede':
+        return mm.centipede(timestep=h)
+    if kind == 'centipede_long':
+        return mm.centipede(20, 25, timestep=h)
+    assert kind == 'walker'
+    return mm.salamander33(contacts=True, limits=True, spawn_z=0.045, timestep=h)
+
+
+def _params(m, n, seed=1):
+    """The per-env sweep as fp32 arrays (what the device reads): freq [n], amp / lag [n, nu], zero on non-position actuators."""
+    rng = np.random.default_rng(seed)
+    pos = np.array([t == 'position' for t in m.actuator_tags[:m.nu]])
+    freq = rng.uniform(0.5, 2.0, n)
+    amp = rng.uniform(0.0, 0.4, (n, m.nu))
+    lag = rng.uniform(-2*np.pi, 2*np.pi, (n, m.nu))
+    amp[rng.random((n, m.nu)) < 0.25] = 0.0
+    p = np.nonzero(pos)[0]
+    amp[0, p[0]], amp[1, p[0]] = 0.3, 0.0        # wave 0: env 0 drives an actuator its partner has dead, and the other way round
+    amp[0, p[1]], amp[1, p[1]] = 0.0, 0.25
+    if n > 2:
+        amp[2] = 0.0                             # an env that is not driven at all (its partner in wave 1 is)
+    amp *= pos; lag *= pos
+    return freq.astype(np.float32), amp.astype(np.float32), lag.astype(np.float32)
+
+
+def _initial(m, n, kind, env_offset=0):
+    import farms_mujoco_amd.model as mm
+    qpos, qvel, psi = mm.synthetic_batch(m, n, seed=4, env_offset=env_offset)
+    if kind == 'walker':                          # the trunk partly below its rest height: the feet and trunk corners touch the plane
+        for e in range(n):
+            qpos[e, 2] = 0.02 + 0.01*np.random.default_rng(100 + env_offset + e).uniform()
+    return qpos, qvel, psi
+
+
+def _make_sim(kind, controller_of, n=N, n_iterations=T, ring=RING, substeps=1, env_offset=0, device='cuda:0'):
+    """A fused swimming (or walking) simulation whose controller is ``controller_of(m, psi)``."""
+    import torch
+    from farms_mujoco_amd.data import AnimatData
+    from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
+    from farms_mujoco_amd.simulation.simulation import Simulation
+    m = _model(kind, substeps)
+    qpos, qvel, psi = _initial(m, n, kind, env_offset)
+    kw = {}
+    if kind == 'walker':
+        arena = ArenaOptions(water=WaterOptions(height=None, drag=False), ground_height=0.0)
+        pairs = [(b, '') for b in m.body_names[1:] if b.endswith('_3')]
+        kw['data'] = AnimatData(m.timestep, ring, n, m.body_names[1:], m.hinge_joint_names(), contacts=pairs, device=device)
+    else:      # the surface cuts the salamander (tests/test_gpu_dual2_lean.py); the flat centipede lies just under it (partial buoyancy)
+        height = -0.11 if kind == 'salamander' else float(m.key_qpos[2]) + 0.003
+        arena = ArenaOptions(water=WaterOptions(height=height, velocity=[0.03, 0.0, -0.01]))
+    sim = Simulation.from_sdf(SimulationOptions(timestep=1e-3, n_iterations=n_iterations, num_sub_steps=substeps),
+                              AnimatOptions.from_model(m), arena, model=m, n_envs=n, controller=controller_of(m, psi),
+                              buffer_size=ring, device=device, **kw)
+    sim.reset()
+    d = sim.physics.data
+    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32)
+    d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
+    sim.physics.forward(disable_actuation=True)
+    return sim, m
+
+
+def _per_env(freq, amp, lag, lo=0, hi=None):
+    from farms_mujoco_amd.control import WaveController
+    return lambda m, psi: WaveController(m, psi, frequency=freq[lo:hi], amplitude_env=amp[lo:hi], phase_lag_env=lag[lo:hi])
+
+
+def _shared(freq, amp, lag):
+    """Today's controller with one parameter set for all envs (fp32 values, exactly)."""
+    import torch
+    from farms_mujoco_amd.control import WaveController
+
+    def make(m, psi):
+        c = WaveController(m, psi, frequency=float(freq))
+        c.amplitude = torch.as_tensor(amp, dtype=torch.float32, device='cuda:0')
+        c.phase_lag = torch.as_tensor(lag, dtype=torch.float32, device='cuda:0')
+        return c
+    return make
+
+
+def _run(sim, fused=True):
+    import torch
+    if fused:
+        sim.run(fused=True)
+    else:
+        for _ in range(sim.task.sim_iterations):
+            sim._env_step()
+    torch.cuda.synchronize()
+    return _outputs(sim)
+
+
+def _outputs(sim):
+    d, s = sim.physics.data, sim.task.data.sensors
+    out = {k: getattr(d, k).cpu().numpy() for k in ('qpos', 'qvel', 'ctrl', 'sensordata', 'xpos', 'xquat', 'xipos', 'status')}
+    out.update({k: getattr(s, k).array.cpu().numpy() for k in ('links', 'joints', 'xfrc')})
+    if s.contacts.names:
+        out['contacts'] = s.contacts.array.cpu().numpy()
+        out['ncon'] = d.ncon.cpu().numpy()
+    assert int(np.abs(out['status'] & 7).sum()) == 0
+    assert all(np.isfinite(v).all() for v in out.values())
+    return out
+
+
+def _env_of(out, e):
+    return {k: (v[:, e] if k in ('links', 'joints', 'xfrc', 'contacts') else v[e]) for k, v in out.items()}
+
+
+def _assert_bitwise(a, b, what):
+    for k in a:
+        print(what, k, 'max abs diff', float(np.abs(a[k].astype(np.float64) - b[k].astype(np.float64)).max()))
+    for k in a:
+        assert np.array_equal(a[k], b[k]), (what, k)
+
+
+# ---- 1. nothing per-env: the same call, the same bits ------------------------------------------------------------------------
+
+def _launch_through(mode, record=None):
+    """A stand-in for simulation._launch_fused that reaches the C entry ``mode`` names with the launch the Simulation prepared."""
+    import torch
+    from farms_mujoco_amd import _lib
+
+    def launch(phys, cd, a, ext):
+        assert ext is None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(phys.device).cuda_stream)
+        if mode == 'fmj_step_fused':
+            rc = phys._lib.fmj_step_fused(phys._ctx, ctypes.byref(cd), ctypes.byref(a), stream)
+        elif mode == 'ext_null':
+            rc = phys._lib.fmj_step_fused_ex(phys._ctx, ctypes.byref(cd), ctypes.byref(a), None, stream)
+        else:
+            z = mode if isinstance(mode, _lib.CFusedExt) else _lib.CFusedExt(ctypes.sizeof(_lib.CFusedExt), 0)
+            rc = phys._lib.fmj_step_fused_ex(phys._ctx, ctypes.byref(cd), ctypes.byref(a), ctypes.byref(z), stream)
+        if record is not None:
+            record.append(rc)
+        else:
+            _lib.check(rc)
+    return launch
+
+
+def test_null_and_zeroed_ext_are_fmj_step_fused_bitwise(monkeypatch):
+    from farms_mujoco_amd.control import WaveController
+    from farms_mujoco_amd.simulation import simulation
+    outs = {}
+    for mode in ('fmj_step_fused', 'ext_null', 'ext_zeroed'):
+        monkeypatch.setattr(simulation, '_launch_fused', _launch_through(mode))
+        sim, m = _make_sim('salamander', lambda m, psi: WaveController(m, psi))
+        outs[mode] = _run(sim)
+        info = sim.physics.kernel_info()
+        assert info['threads_per_env'] == 32 and info['dual_last_launch'] == 'lean', (mode, info)      # still the lean build
+    _assert_bitwise(outs['fmj_step_fused'], outs['ext_null'], 'ext = NULL')
+    _assert_bitwise(outs['fmj_step_fused'], outs['ext_zeroed'], 'zeroed ext')
+    assert np.abs(outs['ext_null']['xfrc']).max() > 0 and np.abs(outs['ext_null']['ctrl']).max() > 0.1
+
+
+def test_bad_ext_is_an_argument_error(monkeypatch):
+    """A size other than sizeof(fmj_fused_ext), a stride in (0, nu) and a per-env field without the wave controller: FMJ_ERR_ARG,
+    before anything is launched."""
+    import torch
+    from farms_mujoco_amd import _lib
+    from farms_mujoco_amd.control import NetworkController, WaveController, salamander_network
+    from farms_mujoco_amd.simulation import simulation
+    size = ctypes.sizeof(_lib.CFusedExt)
+    sim, m = _make_sim('salamander', lambda m, psi: WaveController(m, psi))
+    before = sim.physics.data.qpos.clone()
+    f = torch.ones(N, device='cuda:0')
+    for ext in (_lib.CFusedExt(size - 8, 0), _lib.CFusedExt(size, 0, None, m.nu - 1, 0), _lib.CFusedExt(size, 0, None, 0, 1),
+                _lib.CFusedExt(size, 0, None, -m.nu, 0)):
+        rcs = []
+        monkeypatch.setattr(simulation, '_launch_fused', _launch_through(ext, rcs))
+        sim.step_fused(1)
+        assert rcs == [FMJ_ERR_ARG], (rcs, sim.physics._lib.fmj_last_error())
+    torch.cuda.synchronize()
+    assert torch.equal(before, sim.physics.data.qpos)
+    # controller 0 (a ctrl tape) with a per-env wave field
+    tape_sim, m = _make_sim('salamander', lambda m, psi: NetworkController(m, salamander_network(m), N, env_phase=psi))
+    rcs = []
+    monkeypatch.setattr(simulation, '_launch_fused', _launch_through(_lib.CFusedExt(size, 0, f.data_ptr(), 0, 0), rcs))
+    tape_sim.step_fused(1)
+    assert rcs == [FMJ_ERR_ARG] and b'controller' in tape_sim.physics._lib.fmj_last_error()
+
+
+# ---- 2. uniform per-env rows are the shared parameters, in every register tier -------------------------------------------------
+
+@pytest.mark.parametrize('wps', ['2', '3', '4'])
+def test_uniform_rows_equal_shared_parameters_bitwise(wps, monkeypatch):
+    from farms_mujoco_amd.control import WaveController
+    from farms_mujoco_amd.model import wave_controller_params
+    monkeypatch.setenv('FMJ_WPS', wps)
+    monkeypatch.setenv('FMJ_DUAL_LEAN', '0')
+    shared_sim, m = _make_sim('salamander', lambda m, psi: WaveController(m, psi, frequency=1.25))
+    shared = _run(shared_sim)
+    sinfo = shared_sim.physics.kernel_info()
+    assert sinfo['dual_wps'] == int(wps) and sinfo['dual_build'] == 'generic' and sinfo['dual_last_launch'] == 'generic', sinfo
+    monkeypatch.delenv('FMJ_DUAL_LEAN')            # a context with the lean build enabled: the per-env launch must not take it
+    amp, lag = wave_controller_params(m, 0.3, 1.0)
+    rows_sim, _ = _make_sim('salamander', _per_env(np.full(N, 1.25), np.tile(amp, (N, 1)), np.tile(lag, (N, 1))))
+    rows = _run(rows_sim)
+    info = rows_sim.physics.kernel_info()
+    assert info['dual_wps'] == int(wps) and info['dual_build'] == 'lean' and info['dual_last_launch'] == 'generic', info
+    _assert_bitwise(shared, rows, f'WPS={wps} uniform rows vs shared')
+
+
+# ---- 3. an env owns its numbers ---------------------------------------------------------------------------------------------------
+
+CASES = {      # kind, threads per env of the step kernel, environment at fmj_create, sub-steps, fused
+    'two_envs_per_wave': ('salamander', 32, {}, 1, True),
+    'one_env_kernel': ('centipede', 64, {}, 1, True),
+    'two_waves_per_env': ('centipede', 128, {'FMJ_WIDE': '1'}, 1, True),
+    'two_waves_per_env_long': ('centipede_long', 128, {}, 1, True),
+    'constraint_kernels': ('walker', 32, {}, 1, True),
+    'substeps_3': ('salamander', 32, {}, 3, True),
+    'host_path_rows_ahead': ('salamander', 32, {}, 1, False),
+}
+
+
+@pytest.mark.parametrize('case', list(CASES))
+def test_env_equals_shared_batch_with_its_rows(case, monkeypatch):
+    """Env e of the per-env batch == env e of a batch in which EVERY env has e's frequency, amplitude row and lag row (today's
+    shared controller), from the same initial states: bitwise, for every e - so neither the wave partner nor the per-env indexing
+    shows in an env's numbers."""
+    kind, threads, env, substeps, fused = CASES[case]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    n = 3 if kind == 'centipede_long' else N
+    m = _model(kind, substeps)
+    freq, amp, lag = _params(m, n)
+    sim, _ = _make_sim(kind, _per_env(freq, amp, lag), n=n, substeps=substeps)
+    got = _run(sim, fused)
+    info = sim.physics.kernel_info()
+    assert info['threads_per_env'] == threads, info
+    if threads == 32 and kind != 'walker':
+        assert info['dual_last_launch'] == ('rare' if substeps > 1 else 'generic'), info
+    if kind == 'walker':
+        assert got['ncon'].max() > 0 and np.abs(got['contacts']).max() > 0      # standing on the plane
+    else:
+        assert np.abs(got['xfrc']).max() > 0
+    # not vacuous: the envs are commanded differently, and differently from a shared batch
+    assert np.abs(got['ctrl'][0] - got['ctrl'][1]).max() > 1e-2
+    for e in range(n):
+        ref_sim, _ = _make_sim(kind, _shared(freq[e], amp[e], lag[e]), n=n, substeps=substeps)
+        ref = _run(ref_sim, fused)
+        _assert_bitwise(_env_of(got, e), _env_of(ref, e), f'{case} env {e}')
+        other = (e + 1) % n
+        assert not np.array_equal(got['qpos'][other], ref['qpos'][other]), (case, e)      # the per-env batch is not the shared batch
+
+
+def test_undriven_env_gets_zero_commands():
+    m = _model('salamander')
+    freq, amp, lag = _params(m, N)
+    sim, _ = _make_sim('salamander', _per_env(freq, amp, lag))
+    got = _run(sim)
+    assert np.all(got['ctrl'][2] == 0.0) and np.abs(got['ctrl'][3]).max() > 1e-2      # env 2 has every amplitude zero, its wave partner not
+
+
+# ---- 4. against the oracle, one env at a time -------------------------------------------------------------------------------------
+
+def test_per_env_sweep_matches_the_oracle(oracle):
+    """The oracle's fused loop run once per env with that env's own wave dict (an independent fp64 clock per frequency); metric and
+    bounds of test_fused_loop_matches_oracle in tests/test_gpu_fused_parity.py."""
+    m = _model('salamander')
+    freq, amp, lag = _params(m, N)
+    sim, _ = _make_sim('salamander', _per_env(freq, amp, lag))
+    d = sim.physics.data
+    q0 = d.qpos.cpu().numpy().astype(np.float64); v0 = d.qvel.cpu().numpy().astype(np.float64)
+    h = sim.task._callbacks[0].handler
+    water = dict(surface=h.water._surface, velocity=h.water._velocity, viscosity=h.water._viscosity, gravity=-9.81, use_buoyancy=h.buoyancy)
+    psi = sim.task._controller.env_phase.cpu().numpy()
+    got = _run(sim)
+    ref = {k: [] for k in ('qpos', 'qvel', 'links', 'joints', 'xfrc')}
+    for e in range(N):
+        o = oracle.forward_debug(m, q0[e], v0[e])
+        s = o['sensordata'].copy(); s[6*(m.nbody - 1) + 3*m.n_sensor_joints:] = 0.0      # actuation disabled at reset
+        st = dict(qpos=q0[e:e + 1], qvel=v0[e:e + 1], xpos=o['xpos'][None], xquat=o['xquat'][None], xipos=o['xipos'][None], sensordata=s[None])
+        wave = dict(amplitude=amp[e], phase_lag=lag[e], env_phase=psi[e:e + 1], frequency=float(freq[e]))
+        r = oracle.run_fused(m, st, T, swim=h.swim_dict(), water=water, buffer_size=RING, controller=1, wave=wave)
+        for k in ref:
+            ref[k].append(r[k])
+    ref = {k: np.concatenate(v, axis=1 if k in ('links', 'joints', 'xfrc') else 0) for k, v in ref.items()}
+    errs = {k: _relerr(got[k], ref[k]) for k in ref}
+    print(errs)
+    assert errs['qpos'] < 1e-4 and errs['links'] < 1e-4 and errs['joints'] < 1e-3 and errs['xfrc'] < 1e-3, errs
+
+
+# ---- 5. the oscillator network ------------------------------------------------------------------------------------------------------
+
+T_NET = 40
+
+
+def _permuted_network(m, seed=5):
+    """salamander_network with its connection list shuffled: descriptor order differs from the library's CSR order."""
+    from farms_mujoco_amd.control import OscillatorNetwork, salamander_network
+    net = salamander_network(m)
+    order = np.random.default_rng(seed).permutation(net.n_conn)
+    assert not np.array_equal(np.argsort(net.conn_to[order], kind='stable'), np.arange(net.n_conn))
+    return _network_with(net, conn=np.c_[net.conn_to, net.conn_from, net.conn_weight, net.conn_bias][order])
+
+
+def _network_with(net, frequency=None, rate=None, amplitude=None, conn=None, gain=None, offset=None):
+    from farms_mujoco_amd.control import OscillatorNetwork
+    con = np.c_[net.conn_to, net.conn_from, net.conn_weight, net.conn_bias] if conn is None else conn
+    out = np.c_[net.out_a, net.out_b, net.out_gain if gain is None else gain, net.out_offset if offset is None else offset]
+    return OscillatorNetwork(net.frequency if frequency is None else frequency, net.rate if rate is None else rate,
+                             net.amplitude if amplitude is None else amplitude, con, out, initial_phase=net.initial_phase)
+
+
+def _net_params(net, n, seed=6):
+    """fp64 values that are exact in fp32 where the library rounds (so a one-env network created from a row rounds to the same)."""
+    rng = np.random.default_rng(seed)
+    f32 = lambda x: x.astype(np.float32).astype(np.float64)
+    return dict(frequency=rng.uniform(0.5, 2.0, (n, net.n_osc)), rate=f32(rng.uniform(10.0, 30.0, (n, net.n_osc))),
+                amplitude=f32(rng.uniform(0.05, 0.25, (n, net.n_osc))), conn_weight=f32(rng.uniform(10.0, 40.0, (n, net.n_conn))),
+                conn_bias=f32(net.conn_bias[None] + rng.uniform(-0.3, 0.3, (n, net.n_conn))),
+                out_gain=f32(net.out_gain[None]*rng.uniform(0.5, 1.5, (n, net.nu))),
+                out_offset=f32((net.out_gain[None] != 0)*rng.uniform(-0.05, 0.05, (n, net.nu))))
+
+
+def _tape_and_state(c, n_steps):
+    import torch
+    tape = c.ctrl_tape(n_steps).clone()
+    torch.cuda.synchronize()
+    return dict(tape=tape.cpu().numpy(), **{k: getattr(c, k).cpu().numpy() for k in ('phase', 'amp', 'damp')})
+
+
+def test_cpg_tape_ex_with_only_drive_is_cpg_tape_bitwise():
+    import torch
+    from farms_mujoco_amd import _lib
+    from farms_mujoco_amd.control import NetworkController
+    from farms_mujoco_amd.model import synthetic_batch
+    m = _model('salamander')
+    net = _permuted_network(m)
+    _, _, psi = synthetic_batch(m, N, seed=4)
+    drive = 1.0 + 0.1*np.arange(N)/N
+    old = _tape_and_state(NetworkController(m, net, N, env_phase=psi, drive=drive), T_NET)
+    outs = []
+    for with_struct in (True, False):
+        c = NetworkController(m, net, N, env_phase=psi, drive=drive)
+        tape = torch.empty(T_NET, N, m.nu, device='cuda:0')
+        p = _lib.CCpgEnvParams(ctypes.sizeof(_lib.CCpgEnvParams), 0)
+        p.drive = c.drive.data_ptr()
+        _lib.check(c._lib.fmj_cpg_tape_ex(c._ctx, N, T_NET, c.timestep, c.phase.data_ptr(), c.amp.data_ptr(), c.damp.data_ptr(),
+                                          ctypes.byref(p) if with_struct else None, tape.data_ptr(), None))
+        torch.cuda.synchronize()
+        outs.append(dict(tape=tape.cpu().numpy(), **{k: getattr(c, k).cpu().numpy() for k in ('phase', 'amp', 'damp')}))
+    _assert_bitwise(old, outs[0], 'fmj_cpg_tape_ex(drive only) vs fmj_cpg_tape')
+    assert not np.array_equal(old['tape'], outs[1]['tape'])      # p == NULL: no drive
+    assert np.abs(old['tape']).max() > 1e-3
+    bad = _lib.CCpgEnvParams(8, 0)
+    c = NetworkController(m, net, N, env_phase=psi)
+    assert c._lib.fmj_cpg_tape_ex(c._ctx, N, 1, c.timestep, c.phase.data_ptr(), c.amp.data_ptr(), c.damp.data_ptr(), ctypes.byref(bad),
+                                  tape.data_ptr(), None) == FMJ_ERR_ARG
+
+
+def test_network_env_equals_one_env_network_and_the_oracle(oracle):
+    """Every array of fmj_cpg_env_params set: env e's tape and state == a one-env network created from e's values (bitwise) and
+    the oracle's network of e's values (bounds of test_hip_tape_matches_oracle in tests/test_cpg_network.py)."""
+    from farms_mujoco_amd.control import NetworkController
+    from farms_mujoco_amd.model import synthetic_batch
+    m = _model('salamander')
+    net = _permuted_network(m)
+    _, _, psi = synthetic_batch(m, N, seed=4)
+    drive = 1.0 + 0.1*np.arange(N)/N
+    P = _net_params(net, N)
+    c = NetworkController(m, net, N, env_phase=psi, drive=drive, env_params=P)
+    assert set(c.env_params) == {'omega', 'rate', 'amplitude', 'conn_weight', 'conn_bias', 'out_gain', 'out_offset'}
+    ph0, a0, d0 = (x.cpu().numpy().astype(np.float64) for x in (c.phase, c.amp, c.damp))
+    got = _tape_and_state(c, T_NET)
+    shared = _tape_and_state(NetworkController(m, net, N, env_phase=psi, drive=drive), T_NET)
+    assert np.abs(got['tape'] - shared['tape']).max() > 1e-3 and np.abs(got['tape'][:, 0] - got['tape'][:, 1]).max() > 1e-3
+    for e in range(N):
+        con = np.c_[net.conn_to, net.conn_from, P['conn_weight'][e], P['conn_bias'][e]]
+        net_e = _network_with(net, P['frequency'][e], P['rate'][e], P['amplitude'][e], con, P['out_gain'][e], P['out_offset'][e])
+        one = _tape_and_state(NetworkController(m, net_e, 1, env_phase=psi[e:e + 1], drive=drive[e:e + 1]), T_NET)
+        mine = dict(tape=got['tape'][:, e:e + 1], **{k: got[k][e:e + 1] for k in ('phase', 'amp', 'damp')})
+        _assert_bitwise(mine, one, f'network env {e} vs one-env network')
+        ref, ph, amp, damp = oracle.cpg_tape(net_e, T_NET, m.timestep, ph0[e:e + 1], a0[e:e + 1], d0[e:e + 1],
+                                             drive=drive[e:e + 1].astype(np.float32))
+        dphi = (mine['phase'] - ph + np.pi) % (2*np.pi) - np.pi
+        print('env', e, 'tape err', np.abs(mine['tape'] - ref).max(), 'amp err', np.abs(mine['amp'] - amp).max(), 'phase err', np.abs(dphi).max())
+        assert np.abs(mine['tape'] - ref).max() < 2e-4
+        assert np.abs(mine['amp'] - amp).max() < 1e-5
+        assert np.abs(dphi).max() < 2e-4
+
+
+def test_network_env_params_shapes():
+    from farms_mujoco_amd.control import NetworkController, salamander_network
+    m = _model('salamander')
+    net = salamander_network(m)
+    with pytest.raises(ValueError, match=rf'conn_weight.*\({N}, {net.n_conn}\)'):
+        NetworkController(m, net, N, env_params=dict(conn_weight=np.ones((N, net.n_conn + 1))))
+    with pytest.raises(ValueError, match='unknown entry'):
+        NetworkController(m, net, N, env_params=dict(omega=np.ones((N, net.n_osc))))
+
+
+# ---- 6. sharded ---------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('n_shards', [2, 3])
+def test_sharded_sweep_equals_one_shard_bitwise(n_shards):
+    from farms_mujoco_amd.sharding import ShardedSimulation
+    n = 7
+    m = _model('salamander')
+    freq, amp, lag = _params(m, n)
+
+    def factory(lo, hi, device):      # each shard's controller from its slice of the sweep
+        return _make_sim('salamander', _per_env(freq, amp, lag, lo, hi), n=hi - lo, env_offset=lo, device=str(device))[0]
+    one = ShardedSimulation(factory, n, ['cuda:0'])
+    many = ShardedSimulation(factory, n, ['cuda:0']*n_shards)
+    one.run(chunk=RING); many.run(chunk=RING)
+    one.synchronize(); many.synchronize()
+    for f in ('qpos', 'qvel', 'ctrl', 'sensordata'):
+        assert np.array_equal(one.gather(f), many.gather(f)), f
+    assert int(np.abs(many.gather('status')).sum()) == 0
+    whole = _outputs(one.shards[0])
+    for (lo, hi), sh in zip(many.ranges, many.shards):
+        part = _outputs(sh)
+        for k in ('links', 'joints', 'xfrc'):
+            assert np.array_equal(whole[k][:, lo:hi], part[k]), k
+    assert np.abs(whole['xfrc']).max() > 0 and np.abs(whole['ctrl'][0] - whole['ctrl'][1]).max() > 1e-2
+
+
+# ---- 7. checkpoint --------------------------------------------------------------------------------------------------------------------
+
+def test_save_load_resumes_a_sweep_bitwise(tmp_path):
+    import torch
+    m = _model('salamander')
+    freq, amp, lag = _params(m, N)
+    cut = 5
+    make = lambda: _make_sim('salamander', _per_env(freq, amp, lag), ring=T)[0]
+    whole = make()
+    whole.step_fused(cut); whole.step_fused(T - cut)
+    first = make()
+    first.step_fused(cut)
+    ck = first.save_state(str(tmp_path/'state.npz'))
+    del first
+    resumed = make()
+    resumed.step_fused(3)                                   # a context that has already moved on: load_state overwrites all of it
+    resumed.load_state(ck)
+    assert (resumed.task.iteration, resumed.task.sim_iteration) == (cut, cut)
+    resumed.step_fused(T - cut)
+    torch.cuda.synchronize()
+    _assert_bitwise(_outputs(whole), _outputs(resumed), 'resumed sweep')
+    a, b = whole.physics.get_state(), resumed.physics.get_state()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    assert np.abs(a['ctrl'][0] - a['ctrl'][1]).max() > 1e-2
