@@ -3,11 +3,11 @@ import os, sys
 root = os.environ.get('GRAFT_REPO_ROOT', os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, 'tests'))
 import numpy as np, torch
-import test_gpu_contacts as tc
+from support_models import walker
 from farms_mujoco_amd.data import AnimatData
 from farms_mujoco_amd.options import SimulationOptions
 from farms_mujoco_amd.simulation.simulation import Simulation
-m = tc._walker(spawn_z=0.06)
+m = walker(spawn_z=0.06)
 n, T = 16, 240
 pairs = [(b, '') for b in m.body_names[1:] if b.endswith('_3') or b.startswith('body_')]
 rng = np.random.default_rng(3)

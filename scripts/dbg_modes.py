@@ -3,10 +3,11 @@ import os, sys
 root = os.environ.get('GRAFT_REPO_ROOT', os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, 'tests'))
 import numpy as np, torch
-import test_gpu_contacts as tc
+from support_models import walker
+from support_sims import set_state
 from oracle import oracle
 from farms_mujoco_amd.physics import BatchedPhysics
-m = tc._walker()
+m = walker()
 base = np.tile(m.qpos0, (1, 1))[0]
 def state(z, seed):
     r = np.random.default_rng(seed)
@@ -21,7 +22,7 @@ L, L2, Md, Md2, Hv = light[0], light[1], medium[0], medium[1], heavy[0]
 print('nefc', nefc)
 def run(qs, T):
     phys = BatchedPhysics(m, len(qs))
-    tc._set(phys, np.array(qs), np.zeros((len(qs), m.nv)))
+    set_state(phys, np.array(qs), np.zeros((len(qs), m.nv)))
     out = []
     for t in range(T):
         phys.step(1); torch.cuda.synchronize(); d = phys.data
@@ -37,7 +38,7 @@ for name, (qa, ia), (qb, ib) in (('Md: [Md,Md2][0] vs [L,Md][1]', ([Md, Md2], 0)
 print('--- rows of the first differing step')
 def upto(qs, T):
     phys = BatchedPhysics(m, len(qs))
-    tc._set(phys, np.array(qs), np.zeros((len(qs), m.nv)))
+    set_state(phys, np.array(qs), np.zeros((len(qs), m.nv)))
     if T: phys.step(T)
     rows, imp = phys.step_debug()
     torch.cuda.synchronize()

@@ -7,7 +7,7 @@ import numpy as np, torch
 from farms_mujoco_amd.model import salamander33, SOLVERS
 from farms_mujoco_amd.physics import BatchedPhysics
 from oracle import oracle
-from test_gpu_contacts import _trot_tape
+from support_models import trot_tape as _trot_tape
 for solver in sys.argv[1:] or ['newton', 'cg']:
     m = salamander33(contacts=True, limits=True, spawn_z=0.045)
     m.solver = SOLVERS[solver]; m.solver_iterations = 100

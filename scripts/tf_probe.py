@@ -7,7 +7,7 @@ import numpy as np, torch
 from farms_mujoco_amd.model import salamander33, SOLVERS, CONES
 from farms_mujoco_amd.physics import BatchedPhysics
 from oracle import oracle
-from test_gpu_contacts import _trot_tape
+from support_models import trot_tape as _trot_tape
 solver, cone = (sys.argv[1:] + ['newton', 'elliptic'])[:2]
 m = salamander33(contacts=True, limits=True, spawn_z=0.045)
 m.solver = SOLVERS[solver]; m.cone = CONES[cone]

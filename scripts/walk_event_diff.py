@@ -58,7 +58,7 @@ def main():
     from oracle import oracle
     from farms_mujoco_amd.model import SOLVERS
     from farms_mujoco_amd.physics import BatchedPhysics
-    from test_gpu_contacts import _trot_tape, _walker
+    from support_models import trot_tape as _trot_tape, walker as _walker
     solver = sys.argv[1] if len(sys.argv) > 1 else 'pgs'
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 32
     T = int(sys.argv[3]) if len(sys.argv) > 3 else 1000

@@ -37,7 +37,7 @@ def _servo_salamander(integrator, kv=2e-3, **kw):
 
 
 def _tree(seed, **kw):
-    from test_gpu_random_trees import random_tree
+    from support_models import random_tree
     return random_tree(seed, **kw)
 
 

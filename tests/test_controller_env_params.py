@@ -9,14 +9,10 @@ import os
 import numpy as np
 import pytest
 
+from support_capi import lib as _lib, FMJ_ERR_ARG
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMJ_ERR_ARG = 1
 N = 5
-
-
-def _lib():
-    from farms_mujoco_amd import _lib
-    return _lib, _lib.load()
 
 
 def _model_and_rows(seed=0):

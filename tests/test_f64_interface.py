@@ -11,36 +11,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from support_capi import (lib as _lib, create_ex as _create_ex, no_gpu as _no_gpu, F32, F64, FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED,
+                          FMJ_ERR_NODEVICE)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED, FMJ_ERR_NODEVICE = 1, 2, 4
-F32, F64 = 0, 1
-
-
-def _lib():
-    from farms_mujoco_amd import _lib
-    if not os.path.exists(_lib.SO_PATH):
-        pytest.skip('libfmj_hip.so not built')
-    return _lib, _lib.load()
-
-
-def _create_ex(m, precision=F64, size=None):
-    L, lib = _lib()
-    c = m.as_c(); ctx = ctypes.c_void_p()
-    opts = L.CCreateOptions(ctypes.sizeof(L.CCreateOptions) if size is None else size, precision)
-    rc = lib.fmj_create_ex(ctypes.byref(c), 4, 0, ctypes.byref(opts), ctypes.byref(ctx))
-    prec = None
-    if rc == 0:
-        prec = lib.fmj_precision(ctx)
-        lib.fmj_destroy(ctx)
-    return rc, lib.fmj_last_error().decode(), prec
-
-
-def _no_gpu():
-    try:
-        import torch
-        return not torch.cuda.is_available()
-    except Exception:
-        return True
 
 
 def test_entry_points_are_exported_and_the_abi_version_stays():

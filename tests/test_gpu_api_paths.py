@@ -7,64 +7,10 @@ import ctypes
 import numpy as np
 import pytest
 
+from parity_metrics import relerr as _relerr
+from support_sims import f64 as _f64, swim_sim as _swim_sim, oracle_initial_state as _oracle_state, swim_water as _swim_water
+
 pytestmark = pytest.mark.gpu
-
-
-def _relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return np.abs(a - b).max()/max(np.abs(b).max(), 1e-12)
-
-
-def _f64(t):
-    return t.cpu().numpy().astype(np.float64)
-
-
-def _swim_sim(n_envs, n_iterations, buffer_size=None, seed=0, data=None, handle_exceptions=False, controller='wave',
-              swimming_links=None):
-    import torch
-    from farms_mujoco_amd.model import salamander33, synthetic_batch
-    from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
-    from farms_mujoco_amd.control import WaveController
-    from farms_mujoco_amd.simulation.simulation import Simulation
-    m = salamander33()
-    qpos, qvel, psi = synthetic_batch(m, n_envs, seed=seed)
-    kw = dict(data=data) if data is not None else {}
-    ao = AnimatOptions.from_model(m)
-    if swimming_links is not None:
-        for link in ao.morphology.links:
-            link.swimming = link.swimming and link.name in swimming_links
-    sim = Simulation.from_sdf(SimulationOptions(timestep=m.timestep, n_iterations=n_iterations), ao,
-                              ArenaOptions(water=WaterOptions(height=0.0)), model=m, n_envs=n_envs,
-                              controller=WaveController(m, psi) if controller == 'wave' else controller,
-                              buffer_size=buffer_size or n_iterations, handle_exceptions=handle_exceptions, **kw)
-    sim.reset()
-    d = sim.physics.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32)
-    d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    sim.physics.forward(disable_actuation=True)
-    return sim, m, psi
-
-
-def _oracle_state(oracle, sim, m):
-    d = sim.physics.data
-    st = dict(qpos=_f64(d.qpos), qvel=_f64(d.qvel))
-    xp, xq, xi, sd = [], [], [], []
-    for e in range(st['qpos'].shape[0]):
-        o = oracle.forward_debug(m, st['qpos'][e], st['qvel'][e])
-        s = o['sensordata'].copy(); s[6*(m.nbody - 1) + 3*m.n_sensor_joints:] = 0.0
-        xp.append(o['xpos']); xq.append(o['xquat']); xi.append(o['xipos']); sd.append(s)
-    st.update(xpos=np.array(xp), xquat=np.array(xq), xipos=np.array(xi), sensordata=np.array(sd))
-    return st
-
-
-def _swim_water_wave(sim):
-    h = sim.task._callbacks[0].handler
-    c = sim.task._controller
-    water = dict(surface=h.water._surface, velocity=h.water._velocity, viscosity=h.water._viscosity, gravity=-9.81,
-                 use_buoyancy=h.buoyancy)
-    wave = dict(amplitude=c.amplitude.cpu().numpy(), phase_lag=c.phase_lag.cpu().numpy(),
-                env_phase=c.env_phase.cpu().numpy(), frequency=c.frequency)
-    return h.swim_dict(), water, wave
 
 
 # ---- BASELINE configs[0]: one salamander, one env, through the reference's loop -----------------------------------
@@ -78,7 +24,7 @@ def test_config0_single_env_run_and_iterator(oracle, driver):
     T = 1000
     sim, m, psi = _swim_sim(1, T)
     st = _oracle_state(oracle, sim, m)
-    swim, water, wave = _swim_water_wave(sim)
+    swim, water, wave = _swim_water(sim, wave=True)
     if driver == 'run':
         sim.run(fused=False)
     else:
@@ -405,7 +351,7 @@ def test_links_and_xfrc_subset_rows(oracle):
     assert np.all(xf[..., nx - 1, :] == 7.0)                                     # the dry extra row is never written
     assert np.abs(xf[-1, :, :nx - 1] - 7.0).min() > 1e-6                         # every swimming link got its row
     assert _relerr(xf, xu) < 5e-4
-    swim, water, wave = _swim_water_wave(sim_f)
+    swim, water, wave = _swim_water(sim_f, wave=True)
     links_body = [m.body_names.index(b) for b in links]
     ref = oracle.run_fused(m, st, T, swim=swim, water=water, buffer_size=T, controller=1, wave=wave, links_body=links_body,
                            n_xfrc=nx)
@@ -546,7 +492,7 @@ def test_host_callbacks_with_one_launch_per_iteration():
                 physics.data.xfrc_applied[:, 7, 1] += 0.02           # a sideways push on one link, on top of its drag
 
     def run(ahead):
-        sim, m, _ = _swim_sim(6, 40, controller='wave')
+        sim, m, _ = _swim_sim(6, 40)
         cb = Push()
         sim.task._callbacks.append(cb)
         assert not sim.task.fusable()
@@ -570,7 +516,7 @@ def test_host_callbacks_with_one_launch_per_iteration():
     assert torch.equal(cb_a.seen[0][1], cb_b.seen[0][1])           # iteration 0: both read the reset's rows, written by the same operator
     assert float(cb_a.seen[7][3].abs().max()) > 0                  # the callback saw the drag of its iteration in xfrc_applied
     # ... and the push moved the animal: the same run without it ends elsewhere
-    sim_c, _, _ = _swim_sim(6, 40, controller='wave')
+    sim_c, _, _ = _swim_sim(6, 40)
     sim_c.run(fused=False)
     assert not torch.equal(sim_c.physics.data.qpos, sim_a.physics.data.qpos)
     # a callback that edits the state itself opts out of the look-ahead

@@ -6,37 +6,19 @@ kernel)."""
 import numpy as np
 import pytest
 
+from support_sims import swim_sim, rows as _rows
+
 pytestmark = pytest.mark.gpu
-
-
-def _rows(sim):
-    s = sim.task.data.sensors
-    out = {k: getattr(s, k).array.cpu().numpy().copy() for k in ('links', 'joints', 'xfrc')}
-    if s.contacts.names:
-        out['contacts'] = s.contacts.array.cpu().numpy().copy()
-    return out
 
 
 def _state(sim):
     return sim.physics.get_state()
 
 
-def _swim(n, T, controller='wave', seed=3):
-    import torch
-    from farms_mujoco_amd.control import NetworkController, WaveController, salamander_network
-    from farms_mujoco_amd.model import salamander33, synthetic_batch
-    from farms_mujoco_amd.options import AnimatOptions, ArenaOptions, SimulationOptions, WaterOptions
-    from farms_mujoco_amd.simulation.simulation import Simulation
-    m = salamander33()
-    qpos, qvel, psi = synthetic_batch(m, n, seed=seed)
-    c = WaveController(m, psi) if controller == 'wave' else NetworkController(m, salamander_network(m), n, env_phase=psi)
-    sim = Simulation.from_sdf(SimulationOptions(timestep=m.timestep, n_iterations=T), AnimatOptions.from_model(m),
-                              ArenaOptions(water=WaterOptions(height=0.0)), model=m, n_envs=n, controller=c, buffer_size=T)
-    sim.reset()
-    d = sim.physics.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    sim.physics.forward(disable_actuation=True)
-    return sim
+def _swim(n, T, controller='wave'):
+    from farms_mujoco_amd.control import NetworkController, salamander_network
+    network = lambda m, psi: NetworkController(m, salamander_network(m), n, env_phase=psi)
+    return swim_sim(n, T, seed=3, controller_of=None if controller == 'wave' else network)[0]
 
 
 def _walk(n, T):

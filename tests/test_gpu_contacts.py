@@ -4,43 +4,12 @@ published soft-constraint model and is what the HIP path is held to."""
 import numpy as np
 import pytest
 
+from parity_metrics import relerr as _relerr
+from support_models import (walker as _walker, trot_tape as _trot_tape, box_walker as _box_walker, hfield_walker as _hfield_walker,
+                            salamander_self_collisions as _salamander_self_collisions, mesh_walker as _mesh_walker, scissors as _scissors)
+from support_sims import set_state
+
 pytestmark = pytest.mark.gpu
-
-
-def _relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return np.abs(a - b).max()/max(np.abs(b).max(), 1e-12)
-
-
-def _walker(spawn_z=0.045):
-    from farms_mujoco_amd.model import salamander33
-    return salamander33(contacts=True, limits=True, spawn_z=spawn_z)
-
-
-def _trot_tape(m, n, T, seed=0):
-    """Trot-like position control: axial wave + diagonal limb pairs swinging in antiphase."""
-    rng = np.random.default_rng(seed)
-    psi = rng.uniform(0, 2*np.pi, n)
-    t = np.arange(T)[:, None, None]*m.timestep
-    tape = np.zeros((T, n, m.nu))
-    for a in range(m.nu):
-        if m.actuator_tags[a] != 'position':
-            continue
-        name = m.joint_names[m.actuator_jntid[a]]
-        if name.startswith('joint_body_'):
-            k = int(name.split('_')[-1])
-            tape[:, :, a] = 0.2*np.sin(2*np.pi*1.0*t[:, :, 0] - 2*np.pi*k/11 + psi[None, :])
-        elif name.endswith('_1'):      # shoulder pitch
-            ph = 0.0 if ('front_L' in name or 'hind_R' in name) else np.pi
-            tape[:, :, a] = 0.3*np.sin(2*np.pi*1.0*t[:, :, 0] + ph + psi[None, :])
-    return tape
-
-
-def _set(phys, qpos, qvel):
-    import torch
-    d = phys.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    return d.qpos.cpu().numpy().astype(np.float64), d.qvel.cpu().numpy().astype(np.float64)
 
 
 def test_single_step_with_contacts_and_limit(oracle):
@@ -53,7 +22,7 @@ def test_single_step_with_contacts_and_limit(oracle):
     qpos[:, 7 + 3] = 1.25                         # one spine joint past its +1.2 rad limit
     qvel = rng.normal(size=(n, m.nv))*0.05
     phys = BatchedPhysics(m, n)
-    q32, v32 = _set(phys, qpos, qvel)
+    q32, v32, _ = set_state(phys, qpos, qvel)
     phys.step(1)
     torch.cuda.synchronize()
     ref = oracle.step(m, q32, v32, ctrl=np.zeros((n, m.nu)))
@@ -85,7 +54,7 @@ def test_many_contacts_more_rows_than_lanes(oracle):
     qpos[n//2:, 2] = 0.045                         # second half stands on its feet
     qvel = rng.normal(size=(n, m.nv))*0.02
     phys = BatchedPhysics(m, n)
-    q32, v32 = _set(phys, qpos, qvel)
+    q32, v32, _ = set_state(phys, qpos, qvel)
     phys.step(1)
     torch.cuda.synchronize()
     ref = oracle.step(m, q32, v32, ctrl=np.zeros((n, m.nu)))
@@ -114,7 +83,7 @@ def test_joint_limit_holds(oracle):
     n, T = 4, 400
     ctrl = np.zeros((n, m.nu)); a = m.actuator_names.index('actuator_position_joint_body_6'); ctrl[:, a] = 3.0
     phys = BatchedPhysics(m, n)
-    q32, v32 = _set(phys, np.tile(m.qpos0, (n, 1)), np.zeros((n, m.nv)))
+    q32, v32, _ = set_state(phys, np.tile(m.qpos0, (n, 1)), np.zeros((n, m.nv)))
     d = phys.data
     d.ctrl[:] = torch.as_tensor(ctrl, dtype=torch.float32)
     phys.step(T)
@@ -143,7 +112,7 @@ def test_walking_rollout(oracle):
     n, T = 8, 100
     tape = _trot_tape(m, n, T)
     phys = BatchedPhysics(m, n)
-    q32, v32 = _set(phys, np.tile(m.qpos0, (n, 1)), np.zeros((n, m.nv)))
+    q32, v32, _ = set_state(phys, np.tile(m.qpos0, (n, 1)), np.zeros((n, m.nv)))
     tape_t = torch.as_tensor(tape, dtype=torch.float32, device='cuda').contiguous()
     phys.step(T, ctrl_tape=tape_t)
     torch.cuda.synchronize()
@@ -171,7 +140,7 @@ def test_contacts2data_rows(oracle):
     m = _walker(spawn_z=0.04)
     n = 4
     phys = BatchedPhysics(m, n)
-    _set(phys, np.tile(m.qpos0, (n, 1)), np.zeros((n, m.nv)))
+    set_state(phys, np.tile(m.qpos0, (n, 1)), np.zeros((n, m.nv)))
     phys.step(30)
     links = m.body_names[1:]
     pairs = [(b, '') for b in links if b.endswith('_3') or b in ('body_0', 'body_5', 'body_11')]
@@ -208,7 +177,7 @@ def test_contact_pair_sensors_and_signs(oracle):
     phys = BatchedPhysics(m, n)
     rng = np.random.default_rng(4)
     qpos = np.tile(m.qpos0, (n, 1)); qpos[:, 7:] += rng.uniform(-0.1, 0.1, (n, m.nq - 7))
-    _set(phys, qpos, 0.02*rng.normal(size=(n, m.nv)))
+    set_state(phys, qpos, 0.02*rng.normal(size=(n, m.nv)))
     phys.step(40)
     foot, trunk = 'leg_front_L_3', 'body_5'
     pairs = [(foot, ''), (foot, 'world'), ('world', foot), ('world', ''), (trunk, ''), ('world', trunk)]
@@ -377,23 +346,6 @@ def test_full_size_config4_properties(oracle):
     assert np.array_equal(half.task.data.sensors.contacts.array.cpu().numpy(), rows[:, N//2:])
 
 
-def _box_walker():
-    """A free box trunk with two hinged box limbs above a plane: plane-box contacts (up to 4 corners per geom)."""
-    from farms_mujoco_amd.model import ModelBuilder, GEOM_BOX, GEOM_PLANE
-    b = ModelBuilder('boxbot', timestep=1e-3)
-    b.options['max_contacts'] = 16
-    b.add_body('trunk', pos=(0, 0, 0.06), mass=0.5, inertia=(2e-4, 6e-4, 7e-4), joint='free')
-    b.add_geom('trunk', GEOM_BOX, (0.06, 0.03, 0.015), friction=(0.8, 0, 0))
-    for side, y in (('L', 0.04), ('R', -0.04)):
-        b.add_body(f'limb_{side}', parent='trunk', pos=(0.03, y, 0.0), mass=0.05, inertia=(2e-6, 8e-6, 8e-6),
-                   joint='hinge', axis=(0, 1, 0), damping=1e-3, limited=True, range=(-0.6, 0.6))
-        b.add_geom(f'limb_{side}', GEOM_BOX, (0.03, 0.008, 0.008), pos=(0.03, 0, -0.02), quat=(0.9659258, 0, 0.258819, 0),
-                   friction=(1.0, 0, 0))
-        b.add_position_actuator(f'joint_limb_{side}', kp=0.05)
-    b.add_geom('world', GEOM_PLANE, (0, 0, 0), friction=(0, 0, 0))
-    return b.compile()
-
-
 def test_plane_box_contacts(oracle):
     """Box geoms against the plane (the box part): contact lists, forces and the state after a drop
     match the oracle's corner test."""
@@ -409,7 +361,7 @@ def test_plane_box_contacts(oracle):
     qpos[:, 7:] = rng.uniform(-0.3, 0.3, (n, m.nq - 7))
     qvel = 0.05*rng.normal(size=(n, m.nv))
     phys = BatchedPhysics(m, n)
-    q32, v32 = _set(phys, qpos, qvel)
+    q32, v32, _ = set_state(phys, qpos, qvel)
     phys.step(1)
     torch.cuda.synchronize()
     d = phys.data
@@ -449,48 +401,6 @@ def test_create_refuses_more_rows_than_the_solver_holds(oracle):
         BatchedPhysics(m, 2)
 
 
-def _terrain(seed=0, nr=17, nc=33, rx=0.8, ry=0.4, zt=0.03):
-    """Smooth random bumps, a few centimetres high, sampled on a grid."""
-    rng = np.random.default_rng(seed)
-    xs = np.linspace(-rx, rx, nc); ys = np.linspace(-ry, ry, nr)
-    z = np.zeros((nr, nc))
-    for _ in range(6):
-        kx, ky, ph = rng.uniform(3, 9), rng.uniform(3, 9), rng.uniform(0, 6.28)
-        z += rng.uniform(0.2, 1.0)*np.sin(kx*xs[None, :] + ph)*np.cos(ky*ys[:, None] - ph)
-    return z/np.abs(z).max(), (rx, ry, zt, 0.1)
-
-
-def _hfield_walker(spawn_z=0.075):
-    """salamander33 with its capsules / foot spheres over a heightfield instead of the plane."""
-    from farms_mujoco_amd.model import salamander33
-    import farms_mujoco_amd.model as mm
-    b_ref = salamander33(contacts=True, limits=True, spawn_z=spawn_z)
-    # rebuild through the builder API: same animat, heightfield arena
-    b = mm.ModelBuilder('salamander33_hf', timestep=1e-3)
-    m = b_ref
-    for i in range(1, m.nbody):
-        j = int(m.body_jntadr[i])
-        kw = dict(pos=m.body_pos[i], quat=m.body_quat[i], mass=m.body_mass[i], ipos=m.body_ipos[i], inertia=m.body_inertia[i], iquat=m.body_iquat[i])
-        if j < 0:
-            b.add_body(m.body_names[i], m.body_names[m.body_parentid[i]], **kw)
-        elif m.jnt_type[j] == 0:
-            b.add_body(m.body_names[i], 'world', joint='free', **kw)
-        else:
-            b.add_body(m.body_names[i], m.body_names[m.body_parentid[i]], joint='hinge', jname=m.joint_names[j], axis=m.jnt_axis[j],
-                       damping=m.dof_damping[m.jnt_dofadr[j]], limited=bool(m.jnt_limited[j]), range=m.jnt_range[j], **kw)
-    for g in range(m.ngeom):
-        if m.geom_type[g] != 0:
-            b.add_geom(m.body_names[m.geom_bodyid[g]], int(m.geom_type[g]), m.geom_size[g], pos=m.geom_pos[g], quat=m.geom_quat[g],
-                       friction=m.geom_friction[g])
-    data, size = _terrain()
-    b.add_hfield(data, size, pos=(0.4, 0.0, 0.0))
-    b.options['max_contacts'] = 32
-    for a in range(m.nu):
-        if m.actuator_tags[a] == 'position':
-            b.add_position_actuator(m.joint_names[m.actuator_jntid[a]], kp=m.actuator_gain[a])
-    return b.compile()
-
-
 def test_heightfield_contacts_match_oracle(oracle):
     """SURVEY 8 f4, the heightfield part (reference task.py:108-123, mjcf.py:486-522), met as the plane of the grid
     triangle under each candidate point: contact lists (positions, normals that differ from contact to contact, geom
@@ -505,7 +415,7 @@ def test_heightfield_contacts_match_oracle(oracle):
     qpos[:, 7:] += rng.uniform(-0.2, 0.2, (n, m.nq - 7))
     qvel = 0.02*rng.normal(size=(n, m.nv))
     phys = BatchedPhysics(m, n)
-    q32, v32 = _set(phys, qpos, qvel)
+    q32, v32, _ = set_state(phys, qpos, qvel)
     phys.step(1)
     torch.cuda.synchronize()
     d = phys.data
@@ -561,7 +471,7 @@ def test_flat_heightfield_equals_plane_on_the_gpu(oracle):
         m = build(kind)
         phys = BatchedPhysics(m, 3)
         q = np.tile(m.qpos0, (3, 1)); q[:, 3:7] = [0.995, 0.05, 0.08, 0.0]; q[:, 3:7] /= np.linalg.norm(q[0, 3:7])
-        _set(phys, q, np.zeros((3, m.nv)))
+        set_state(phys, q, np.zeros((3, m.nv)))
         phys.step(150)
         torch.cuda.synchronize()
         assert int(phys.data.status.abs().sum()) == 0 and int(phys.data.ncon.min()) >= 3
@@ -575,7 +485,6 @@ def test_self_collision_pairs_match_oracle(oracle):
     contact record, contact force and accelerations of a single step, then a rollout, against the oracle."""
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
-    from test_oracle_contacts import _scissors
     for capsule in (False, True):
         m, q = _scissors(0.1, capsule=capsule)
         n = 6
@@ -583,7 +492,7 @@ def test_self_collision_pairs_match_oracle(oracle):
         qpos = np.tile(q, (n, 1)) + rng.uniform(-0.03, 0.03, (n, 2)); qpos[n - 1] = [0.6, -0.6]      # the last env is open: no contact
         qvel = rng.normal(size=(n, 2))*0.2
         phys = BatchedPhysics(m, n)
-        q32, v32 = _set(phys, qpos, qvel)
+        q32, v32, _ = set_state(phys, qpos, qvel)
         phys.step(1)
         torch.cuda.synchronize()
         d = phys.data
@@ -604,33 +513,6 @@ def test_self_collision_pairs_match_oracle(oracle):
         ref = oracle.step(m, q32, v32, ctrl=np.zeros((n, m.nu)), n_steps=200)
         assert int(d.status.abs().sum()) == 0
         assert np.abs(d.qpos.cpu().numpy() - ref['qpos']).max() < 2e-4, capsule
-
-
-def _salamander_self_collisions(spawn_z=0.045):
-    """The walking salamander with explicit pairs between neighbouring limbs and between head and tail, over the plane."""
-    import farms_mujoco_amd.model as mm
-    ref = mm.salamander33(contacts=True, limits=True, spawn_z=spawn_z)
-    b = mm.ModelBuilder('salamander33_sc', timestep=1e-3)
-    m = ref
-    for i in range(1, m.nbody):
-        j = int(m.body_jntadr[i])
-        kw = dict(pos=m.body_pos[i], quat=m.body_quat[i], mass=m.body_mass[i], ipos=m.body_ipos[i], inertia=m.body_inertia[i], iquat=m.body_iquat[i])
-        if m.jnt_type[j] == 0:
-            b.add_body(m.body_names[i], 'world', joint='free', **kw)
-        else:
-            b.add_body(m.body_names[i], m.body_names[m.body_parentid[i]], joint='hinge', jname=m.joint_names[j], axis=m.jnt_axis[j],
-                       damping=m.dof_damping[m.jnt_dofadr[j]], limited=bool(m.jnt_limited[j]), range=m.jnt_range[j], **kw)
-    for g in range(m.ngeom):
-        b.add_geom(m.body_names[m.geom_bodyid[g]], int(m.geom_type[g]), m.geom_size[g], pos=m.geom_pos[g], quat=m.geom_quat[g],
-                   friction=m.geom_friction[g])
-    for a in range(m.nu):
-        if m.actuator_tags[a] == 'position':
-            b.add_position_actuator(m.joint_names[m.actuator_jntid[a]], kp=m.actuator_gain[a])
-    b.options['max_contacts'] = 32
-    for pair in (('leg_front_L_3', 'leg_front_R_3'), ('leg_hind_L_3', 'leg_hind_R_3'), ('body_0', 'body_11'), ('body_2', 'body_10'),
-                 ('leg_front_L_3', 'body_2'), ('leg_hind_R_3', 'body_6'), ('leg_front_R_3', 'body_1'), ('leg_hind_L_3', 'leg_front_L_3')):
-        b.add_contact_pair(*pair)
-    return b.compile()
 
 
 def test_self_collisions_with_ground_contacts_match_oracle(oracle):
@@ -668,7 +550,7 @@ def test_self_collisions_with_ground_contacts_match_oracle(oracle):
     qpos = np.array(poses)
     qvel = 0.02*rng.normal(size=(n, m.nv))
     phys = BatchedPhysics(m, n)
-    q32, v32 = _set(phys, qpos, qvel)
+    q32, v32, _ = set_state(phys, qpos, qvel)
     phys.step(1)
     torch.cuda.synchronize()
     d = phys.data
@@ -711,29 +593,6 @@ def test_self_collisions_with_ground_contacts_match_oracle(oracle):
     assert err.max() < 5e-3 and np.median(err) < 1e-3
 
 
-def _mesh_walker(seed=5):
-    """A free trunk with a convex-mesh hull (random points on an ellipsoid) and two hinged limbs ending in small convex
-    meshes, above a plane: every ground contact comes from a mesh vertex."""
-    from farms_mujoco_amd.model import ModelBuilder, GEOM_PLANE
-    rng = np.random.default_rng(seed)
-
-    def cloud(n, a, b, c):
-        v = rng.normal(size=(n, 3)); v /= np.linalg.norm(v, axis=1, keepdims=True)
-        return v*np.array([a, b, c])
-    b = ModelBuilder('meshbot', timestep=1e-3)
-    b.options['max_contacts'] = 16
-    b.add_body('trunk', pos=(0, 0, 0.06), mass=0.5, inertia=(2e-4, 6e-4, 7e-4), joint='free')
-    b.add_mesh_geom('trunk', cloud(60, 0.06, 0.03, 0.015), friction=(0.8, 0, 0))
-    for side, y in (('L', 0.04), ('R', -0.04)):
-        b.add_body(f'limb_{side}', parent='trunk', pos=(0.03, y, 0.0), mass=0.05, inertia=(2e-6, 8e-6, 8e-6),
-                   joint='hinge', axis=(0, 1, 0), damping=1e-3, limited=True, range=(-0.6, 0.6))
-        b.add_mesh_geom(f'limb_{side}', cloud(24, 0.03, 0.008, 0.008), pos=(0.03, 0, -0.02), quat=(0.9659258, 0, 0.258819, 0),
-                        friction=(1.0, 0, 0))
-        b.add_position_actuator(f'joint_limb_{side}', kp=0.05)
-    b.add_geom('world', GEOM_PLANE, (0, 0, 0), friction=(0, 0, 0))
-    return b.compile()
-
-
 def test_plane_mesh_contacts(oracle):
     """Convex mesh geoms against the plane (the mesh part): the contact lists (the up-to-4 deepest penetrating
     hull vertices per geom, deepest first), the forces and the state after a drop match the oracle."""
@@ -750,7 +609,7 @@ def test_plane_mesh_contacts(oracle):
     qpos[:, 7:] = rng.uniform(-0.3, 0.3, (n, m.nq - 7))
     qvel = 0.05*rng.normal(size=(n, m.nv))
     phys = BatchedPhysics(m, n)
-    q32, v32 = _set(phys, qpos, qvel)
+    q32, v32, _ = set_state(phys, qpos, qvel)
     phys.step(1)
     torch.cuda.synchronize()
     d = phys.data
@@ -865,7 +724,7 @@ def test_two_env_kernel_modes_do_not_depend_on_the_partner(oracle, monkeypatch):
     def run(qs):
         phys = BatchedPhysics(m, len(qs))
         assert phys.kernel_info()['threads_per_env'] == (32 if os.environ.get('FMJ_DUAL', '1') != '0' else 64)
-        q32, v32 = _set(phys, np.array(qs), np.zeros((len(qs), m.nv)))
+        q32, v32, _ = set_state(phys, np.array(qs), np.zeros((len(qs), m.nv)))
         phys.step(T)
         torch.cuda.synchronize()
         d = phys.data
@@ -920,7 +779,7 @@ def test_thousand_steps_of_walking(oracle, solver):
     n, T = 32, 1000
     tape = _trot_tape(m, n, T)
     phys = BatchedPhysics(m, n)
-    q32, v32 = _set(phys, np.tile(m.qpos0, (n, 1)), np.zeros((n, m.nv)))
+    q32, v32, _ = set_state(phys, np.tile(m.qpos0, (n, 1)), np.zeros((n, m.nv)))
     tape_t = torch.as_tensor(tape, dtype=torch.float32, device='cuda').contiguous()
     tape64 = tape_t.cpu().numpy().astype(np.float64)
     d = phys.data

@@ -10,17 +10,13 @@ import ctypes
 import numpy as np
 import pytest
 
+from parity_metrics import relerr as _relerr
+from support_capi import FMJ_ERR_ARG
+from support_sims import load_batch, outputs, env_of as _env_of, assert_bitwise as _assert_bitwise
+
 pytestmark = pytest.mark.gpu
 
 N, T, RING = 5, 12, 5
-FMJ_ERR_ARG = 1
-
-
-def _relerr(a, b):      # the metric of tests/test_gpu_fused_parity.py
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return np.abs(a - b).max()/max(np.abs(b).max(), 1e-12)
-
-
 def _model(kind, substeps=1):
     import farms_mujoco_amd.model as mm
     h = 1e-3/substeps
@@ -62,7 +58,6 @@ def _initial(m, n, kind, env_offset=0):
 
 def _make_sim(kind, controller_of, n=N, n_iterations=T, ring=RING, substeps=1, env_offset=0, device='cuda:0'):
     """A fused swimming (or walking) simulation whose controller is ``controller_of(m, psi)``."""
-    import torch
     from farms_mujoco_amd.data import AnimatData
     from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
     from farms_mujoco_amd.simulation.simulation import Simulation
@@ -79,11 +74,7 @@ def _make_sim(kind, controller_of, n=N, n_iterations=T, ring=RING, substeps=1, e
     sim = Simulation.from_sdf(SimulationOptions(timestep=1e-3, n_iterations=n_iterations, num_sub_steps=substeps),
                               AnimatOptions.from_model(m), arena, model=m, n_envs=n, controller=controller_of(m, psi),
                               buffer_size=ring, device=device, **kw)
-    sim.reset()
-    d = sim.physics.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32)
-    d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    sim.physics.forward(disable_actuation=True)
+    load_batch(sim, qpos, qvel)
     return sim, m
 
 
@@ -105,6 +96,12 @@ def _shared(freq, amp, lag):
     return make
 
 
+def _checked(sim):
+    out = outputs(sim, ('qpos', 'qvel', 'ctrl', 'sensordata', 'xpos', 'xquat', 'xipos', 'status'))
+    assert int(np.abs(out['status'] & 7).sum()) == 0
+    return out
+
+
 def _run(sim, fused=True):
     import torch
     if fused:
@@ -113,30 +110,7 @@ def _run(sim, fused=True):
         for _ in range(sim.task.sim_iterations):
             sim._env_step()
     torch.cuda.synchronize()
-    return _outputs(sim)
-
-
-def _outputs(sim):
-    d, s = sim.physics.data, sim.task.data.sensors
-    out = {k: getattr(d, k).cpu().numpy() for k in ('qpos', 'qvel', 'ctrl', 'sensordata', 'xpos', 'xquat', 'xipos', 'status')}
-    out.update({k: getattr(s, k).array.cpu().numpy() for k in ('links', 'joints', 'xfrc')})
-    if s.contacts.names:
-        out['contacts'] = s.contacts.array.cpu().numpy()
-        out['ncon'] = d.ncon.cpu().numpy()
-    assert int(np.abs(out['status'] & 7).sum()) == 0
-    assert all(np.isfinite(v).all() for v in out.values())
-    return out
-
-
-def _env_of(out, e):
-    return {k: (v[:, e] if k in ('links', 'joints', 'xfrc', 'contacts') else v[e]) for k, v in out.items()}
-
-
-def _assert_bitwise(a, b, what):
-    for k in a:
-        print(what, k, 'max abs diff', float(np.abs(a[k].astype(np.float64) - b[k].astype(np.float64)).max()))
-    for k in a:
-        assert np.array_equal(a[k], b[k]), (what, k)
+    return _checked(sim)
 
 
 # ---- 1. nothing per-env: the same call, the same bits ------------------------------------------------------------------------
@@ -435,9 +409,9 @@ def test_sharded_sweep_equals_one_shard_bitwise(n_shards):
     for f in ('qpos', 'qvel', 'ctrl', 'sensordata'):
         assert np.array_equal(one.gather(f), many.gather(f)), f
     assert int(np.abs(many.gather('status')).sum()) == 0
-    whole = _outputs(one.shards[0])
+    whole = _checked(one.shards[0])
     for (lo, hi), sh in zip(many.ranges, many.shards):
-        part = _outputs(sh)
+        part = _checked(sh)
         for k in ('links', 'joints', 'xfrc'):
             assert np.array_equal(whole[k][:, lo:hi], part[k]), k
     assert np.abs(whole['xfrc']).max() > 0 and np.abs(whole['ctrl'][0] - whole['ctrl'][1]).max() > 1e-2
@@ -463,7 +437,7 @@ def test_save_load_resumes_a_sweep_bitwise(tmp_path):
     assert (resumed.task.iteration, resumed.task.sim_iteration) == (cut, cut)
     resumed.step_fused(T - cut)
     torch.cuda.synchronize()
-    _assert_bitwise(_outputs(whole), _outputs(resumed), 'resumed sweep')
+    _assert_bitwise(_checked(whole), _checked(resumed), 'resumed sweep')
     a, b = whole.physics.get_state(), resumed.physics.get_state()
     for k in a:
         assert np.array_equal(a[k], b[k]), k

@@ -4,39 +4,11 @@ build (FMJ_DUAL_LEAN=0) in every register tier, and a launch shape it does not c
 import numpy as np
 import pytest
 
+from support_sims import swim_sim, outputs, assert_bitwise as _assert_bitwise
+
 pytestmark = pytest.mark.gpu
 
 N, T, RING = 7, 120, 40      # odd batch: the last wave has an idle half; more steps than ring rows: the ring wraps
-
-
-def _make_sim(n_envs, n_iterations, buffer_size):
-    import torch
-    from farms_mujoco_amd.model import salamander33, synthetic_batch
-    from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
-    from farms_mujoco_amd.control import WaveController
-    from farms_mujoco_amd.simulation.simulation import Simulation
-    m = salamander33(timestep=1e-3)
-    qpos, qvel, psi = synthetic_batch(m, n_envs, seed=0)
-    sim = Simulation.from_sdf(SimulationOptions(timestep=1e-3, n_iterations=n_iterations), AnimatOptions.from_model(m),
-                              ArenaOptions(water=WaterOptions(height=-0.11, velocity=[0.03, 0.0, -0.01])),      # the surface cuts the animal, a current
-                              model=m, n_envs=n_envs, controller=WaveController(m, psi), buffer_size=buffer_size)
-    sim.reset()
-    d = sim.physics.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32)
-    d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    sim.physics.forward(disable_actuation=True)
-    return sim
-
-
-def _outputs(sim):
-    import torch
-    torch.cuda.synchronize()
-    d, s = sim.physics.data, sim.task.data.sensors
-    assert int(d.status.abs().sum()) == 0
-    out = {k: getattr(d, k).cpu().numpy() for k in ('qpos', 'qvel', 'sensordata', 'xpos', 'xquat')}
-    out.update({k: getattr(s, k).array.cpu().numpy() for k in ('links', 'joints', 'xfrc')})
-    assert all(np.isfinite(v).all() for v in out.values())
-    return out
 
 
 def _run(monkeypatch, fused=True, **env):
@@ -46,7 +18,7 @@ def _run(monkeypatch, fused=True, **env):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    sim = _make_sim(N, T, RING)
+    sim = swim_sim(N, T, RING, water_kwargs=dict(height=-0.11, velocity=[0.03, 0.0, -0.01]))[0]      # the surface cuts the animal, a current
     launches = set()
     if fused:
         sim.run(fused=True)
@@ -55,14 +27,9 @@ def _run(monkeypatch, fused=True, **env):
             sim._env_step()
             launches.add(sim.physics.kernel_info()['dual_last_launch'])
         sim.physics.check_invalid_state()
-    return _outputs(sim), sim.physics.kernel_info(), launches
-
-
-def _assert_bitwise(a, b, what):
-    for k in a:
-        print(what, k, 'max abs diff', float(np.abs(a[k].astype(np.float64) - b[k].astype(np.float64)).max()))
-    for k in a:
-        assert np.array_equal(a[k], b[k]), (what, k)
+    out = outputs(sim, ('qpos', 'qvel', 'sensordata', 'xpos', 'xquat'))
+    assert int(sim.physics.data.status.abs().sum()) == 0
+    return out, sim.physics.kernel_info(), launches
 
 
 @pytest.mark.parametrize('wps', ['2', '3', '4'])

@@ -13,7 +13,8 @@ import pytest
 
 from parity_metrics import relerr, qpos_groups, qvel_groups, link_row_groups
 from wide_trees import WIDE_SHAPES, shape_tree, dof_depth
-from test_gpu_wide_random_trees import _inputs, _f64
+from support_models import random_tree, tree_inputs as _inputs
+from support_sims import f64 as _f64, swim_sim, wave_at, swim_oracle as _swim_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +24,6 @@ MODELS = (['salamander33', 'eel20', 'eel48', 'eel58', 'centipede', 'centipede_20
 
 def _make(name, integrator='Euler'):
     import farms_mujoco_amd.model as mm
-    from test_gpu_random_trees import random_tree
     if name.startswith('shape'):
         m = shape_tree(int(name[5:]))
     elif name.startswith('tree'):
@@ -199,33 +199,15 @@ def test_rollout_against_the_state_rounding_floor(oracle, name, T):
     assert max(per_env) <= 1e-4, (name, per_env)
 
 
-def _swim_sim(m, n, T, precision, seed=9):
-    import torch
-    import farms_mujoco_amd.model as mm
-    from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
-    from farms_mujoco_amd.control import WaveController
-    from farms_mujoco_amd.simulation.simulation import Simulation
-    qpos, qvel, psi = mm.synthetic_batch(m, n, seed=seed)
-    sim = Simulation.from_sdf(SimulationOptions(timestep=m.timestep, n_iterations=T), AnimatOptions.from_model(m),
-                              ArenaOptions(water=WaterOptions(height=0.0)), model=m, n_envs=n, precision=precision,
-                              controller=WaveController(m, psi, frequency=1.5), buffer_size=T)
-    sim.reset()
-    d = sim.physics.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    sim.physics.forward(disable_actuation=True)
-    return sim
-
-
 def test_swim_of_a_long_eel_through_the_api(oracle):
     """Simulation(precision='fp64') on eel(48), 40 iterations with drag and the wave controller: run() takes the per-iteration path
     by itself.  Rows and drag are fp32 operators on this path, so it is measured against the oracle's fused loop with fp32 storage:
     qpos at least 10x below that run's error, link and xfrc rows at or below it."""
     import torch
     from farms_mujoco_amd._lib import FmjError
-    from test_gpu_wide_models import _swim_oracle
     m = _make('eel48')
     T, n = 40, 12
-    sim = _swim_sim(m, n, T, 'fp64')
+    sim = swim_sim(n, T, m=m, seed=9, controller_of=wave_at(1.5), precision='fp64')[0]
     assert sim.physics.precision == 'fp64' and not sim.task.fusable()
     ref = _swim_oracle(oracle, sim, m, T)
     with oracle.fp32_storage():
@@ -247,13 +229,13 @@ def test_checkpoint_continues_bit_for_bit(tmp_path):
     import torch
     m = _make('eel20')
     T, n = 24, 4
-    a = _swim_sim(m, n, T, 'fp64')
+    a = swim_sim(n, T, m=m, seed=9, controller_of=wave_at(1.5), precision='fp64')[0]
     a.run()
-    b = _swim_sim(m, n, T, 'fp64')
+    b = swim_sim(n, T, m=m, seed=9, controller_of=wave_at(1.5), precision='fp64')[0]
     for _ in range(10):
         b._env_step()
     b.save_state(str(tmp_path/'mid.npz'))
-    c = _swim_sim(m, n, T, 'fp64')
+    c = swim_sim(n, T, m=m, seed=9, controller_of=wave_at(1.5), precision='fp64')[0]
     c.load_state(str(tmp_path/'mid.npz'))
     c.run()
     torch.cuda.synchronize()

@@ -2,62 +2,12 @@
 import numpy as np
 import pytest
 
+from parity_metrics import relerr as _relerr
+from support_models import SDF, sdf_options as _options
+from support_sims import (swim_sim as _make_sim, oracle_initial_state as _oracle_initial_state, swim_water as _swim_water,
+                          sdf_wave as _SdfWave)
+
 pytestmark = pytest.mark.gpu
-
-
-def _relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return np.abs(a - b).max()/max(np.abs(b).max(), 1e-12)
-
-
-def _make_sim(n_envs, n_iterations, buffer_size=None, units=None, water_kwargs=None, seed=0, env_offset=0, substeps=1,
-              swim_substep=None, model_hook=None):
-    import torch
-    from farms_mujoco_amd.model import salamander33, synthetic_batch
-    from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
-    from farms_mujoco_amd.control import WaveController
-    from farms_mujoco_amd.simulation.simulation import Simulation
-    from farms_mujoco_amd.units import SimulationUnitScaling
-    m = salamander33(timestep=1e-3/substeps)       # the model steps at timestep / num_sub_steps (reference mjcf.py:1187-1192)
-    if model_hook is not None:
-        model_hook(m)
-    qpos, qvel, psi = synthetic_batch(m, n_envs, seed=seed, env_offset=env_offset)
-    opts = SimulationOptions(timestep=1e-3, n_iterations=n_iterations, units=units or SimulationUnitScaling(), num_sub_steps=substeps)
-    arena = ArenaOptions(water=WaterOptions(**(water_kwargs or {})))
-    animat = AnimatOptions.from_model(m)
-    ctl = WaveController(m, psi)
-    kw = {}
-    if swim_substep is not None:                   # the swimming callback with its substep flag (TaskCallback(substep=...), task.py:415-420)
-        from farms_mujoco_amd.simulation.task import SwimmingCallback
-        kw['callbacks'] = [SwimmingCallback(animat, arena, substep=swim_substep)]
-    sim = Simulation.from_sdf(opts, animat, arena, model=m, n_envs=n_envs, controller=ctl,
-                              buffer_size=buffer_size or n_iterations, **kw)
-    sim.reset()
-    d = sim.physics.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32)
-    d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    sim.physics.forward(disable_actuation=True)
-    return sim, m, psi
-
-
-def _oracle_initial_state(oracle, sim, m):
-    d = sim.physics.data
-    st = dict(qpos=d.qpos.cpu().numpy().astype(np.float64), qvel=d.qvel.cpu().numpy().astype(np.float64))
-    n = st['qpos'].shape[0]
-    xp, xq, xi, sd = [], [], [], []
-    for e in range(n):
-        o = oracle.forward_debug(m, st['qpos'][e], st['qvel'][e])
-        s = o['sensordata'].copy(); s[6*(m.nbody - 1) + 3*m.n_sensor_joints:] = 0.0   # actuation disabled at reset
-        xp.append(o['xpos']); xq.append(o['xquat']); xi.append(o['xipos']); sd.append(s)
-    st.update(xpos=np.array(xp), xquat=np.array(xq), xipos=np.array(xi), sensordata=np.array(sd))
-    return st
-
-
-def _swim_water(sim):
-    h = [cb for cb in sim.task._callbacks][0].handler
-    w = h.water
-    return h.swim_dict(), dict(surface=w._surface, velocity=w._velocity, viscosity=w._viscosity, gravity=-9.81,
-                               use_buoyancy=h.buoyancy)
 
 
 def test_reset_forward_matches_oracle(oracle):
@@ -229,7 +179,6 @@ def test_from_sdf_end_to_end(oracle, tmp_path):
     """Simulation.from_sdf on a real SDF file (reference simulation.py:96-124 -> setup_mjcf_xml): compile, swim 150
     fused iterations with the host-callback-free fast path, compare with the oracle."""
     import torch
-    from test_sdf_compiler import SDF, _options
     from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, WaterOptions
     from farms_mujoco_amd.control import WaveController
     from farms_mujoco_amd.simulation.simulation import Simulation
@@ -265,7 +214,6 @@ def test_from_sdf_on_the_ground_with_the_primal_solvers(oracle, tmp_path, solver
     SDF with simulation_options.solver / cone, drops the animal on a flat arena and runs 200 fused iterations; state and link rows
     against the oracle stepping the same compiled model."""
     import torch
-    from test_sdf_compiler import SDF, _options
     from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, WaterOptions
     from farms_mujoco_amd.simulation.simulation import Simulation
     from farms_mujoco_amd.simulation.mjcf import setup_model
@@ -297,18 +245,6 @@ def test_from_sdf_on_the_ground_with_the_primal_solvers(oracle, tmp_path, solver
     print(solver, cone, 'from_sdf on the ground: qpos abs err per env', e)
     assert e.max() < 5e-5                                       # measured 2e-7 .. 1.3e-6
     assert _relerr(sim.task.data.sensors.links.array.cpu().numpy(), ref['links']) < 1e-3
-
-
-def _SdfWave(m, psi):
-    """Wave controller on every position actuator of an arbitrary model (joint names are not 'joint_body_*')."""
-    import torch
-    from farms_mujoco_amd.control import WaveController
-    c = WaveController(m, psi, frequency=1.5)
-    amp = np.array([0.25 if t == 'position' else 0.0 for t in m.actuator_tags])
-    lag = np.array([0.8*m.actuator_jntid[a] for a in range(m.nu)])
-    c.amplitude = torch.as_tensor(amp, dtype=torch.float32, device='cuda:0')
-    c.phase_lag = torch.as_tensor(lag, dtype=torch.float32, device='cuda:0')
-    return c
 
 
 @pytest.mark.parametrize('N', [4096, 8192])

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from parity_metrics import relerr, group_relerr, qvel_groups
+from support_sims import swim_sim as _make_sim, oracle_initial_state as _oracle_initial_state, swim_water as _swim_water
 
 pytestmark = pytest.mark.gpu
 
@@ -103,16 +104,14 @@ def test_implicitfast_fused_run_matches_oracle(oracle, substeps):
     controller drives the position actuators, the velocity servos hold 0 - a damper that implicitfast integrates implicitly."""
     import torch
     import farms_mujoco_amd.model as mm
-    from test_gpu_fused_parity import _make_sim, _oracle_initial_state, _swim_water
 
-    def servo(m, integrator='implicitfast'):
-        for a, tag in enumerate(m.actuator_tags):
-            if tag == 'velocity':
-                m.actuator_gain[a] = 2e-3; m.actuator_bias[a, 2] = -2e-3
-        m.integrator = mm.INTEGRATORS[integrator]
-
+    m = mm.salamander33(timestep=1e-3/substeps)
+    for a, tag in enumerate(m.actuator_tags):
+        if tag == 'velocity':
+            m.actuator_gain[a] = 2e-3; m.actuator_bias[a, 2] = -2e-3
+    m.integrator = mm.INTEGRATORS['implicitfast']
     n, T = 16, 200
-    sim, m, psi = _make_sim(n, T, model_hook=servo, substeps=substeps)      # (with sub-steps: the same instantiation of the two-env kernel carries both options)
+    sim, m, psi = _make_sim(n, T, m=m, substeps=substeps)      # (with sub-steps: the same instantiation of the two-env kernel carries both options)
     assert sim.task.fusable() and m.integrator == 3
     st = _oracle_initial_state(oracle, sim, m)
     swim, water = _swim_water(sim)

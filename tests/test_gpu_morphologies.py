@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from parity_metrics import relerr as _relerr, group_relerr, qpos_groups, qvel_groups, link_row_groups
+from support_sims import load_batch, oracle_initial_state, swim_water
 
 pytestmark = pytest.mark.gpu
 
@@ -61,7 +62,6 @@ def test_step_parity_other_morphologies(oracle, maker):
 def _bucket_sim(maker, n, T, ring, env_offset=0, seed=9, twins=()):
     """One morphology bucket of the mixed batch: fused swimming with drag, wave controller, inputs keyed by global env
     index."""
-    import torch
     import farms_mujoco_amd.model as mm
     from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
     from farms_mujoco_amd.control import WaveController
@@ -73,29 +73,14 @@ def _bucket_sim(maker, n, T, ring, env_offset=0, seed=9, twins=()):
     sim = Simulation.from_sdf(SimulationOptions(timestep=m.timestep, n_iterations=T), AnimatOptions.from_model(m),
                               ArenaOptions(water=WaterOptions(height=0.0)), model=m, n_envs=n,
                               controller=WaveController(m, psi, frequency=1.5), buffer_size=ring)
-    sim.reset()
-    d = sim.physics.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    sim.physics.forward(disable_actuation=True)
+    load_batch(sim, qpos, qvel)
     return sim, m
 
 
 def _bucket_oracle(oracle, sim, m, T, ring, envs):
     """The oracle's fused loop on a sample of a bucket's envs, from the bucket's own fp32 inputs."""
-    d = sim.physics.data
-    q = d.qpos[envs].cpu().numpy().astype(np.float64); v = d.qvel[envs].cpu().numpy().astype(np.float64)
-    st = dict(qpos=q, qvel=v)
-    fds = [oracle.forward_debug(m, q[i], v[i]) for i in range(len(envs))]
-    for k in ('xpos', 'xquat', 'xipos'):
-        st[k] = np.array([fd[k] for fd in fds])
-    sd = np.array([fd['sensordata'] for fd in fds]); sd[:, 6*(m.nbody - 1) + 3*m.n_sensor_joints:] = 0.0
-    st['sensordata'] = sd
-    h = sim.task._callbacks[0].handler
-    c = sim.task._controller
-    water = dict(surface=h.water._surface, velocity=h.water._velocity, viscosity=h.water._viscosity, gravity=-9.81, use_buoyancy=h.buoyancy)
-    wave = dict(amplitude=c.amplitude.cpu().numpy(), phase_lag=c.phase_lag.cpu().numpy(), env_phase=c.env_phase[envs].cpu().numpy(),
-                frequency=c.frequency)
-    return oracle.run_fused(m, st, T, swim=h.swim_dict(), water=water, buffer_size=ring, controller=1, wave=wave, n_threads=8)
+    swim, water, wave = swim_water(sim, wave=True, envs=envs)
+    return oracle.run_fused(m, oracle_initial_state(oracle, sim, m, envs), T, swim=swim, water=water, buffer_size=ring, controller=1, wave=wave, n_threads=8)
 
 
 # Absolute caps next to the "6 x floor" rule (round 4): the per-component metric divides by the size of each entry, and the entries of a

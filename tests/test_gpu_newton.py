@@ -2,30 +2,19 @@
 against the oracle's Newton (oracle/fmj_oracle.c solve_primal), itself cross-checked against a converged PGS on CPU
 (tests/test_oracle_solvers.py)."""
 import copy
+import functools
 
 import numpy as np
 import pytest
 
 from parity_metrics import group_relerr, qvel_groups
+from support_models import (walker, trot_tape as _trot_tape, scissors as _scissors, salamander_self_collisions as _salamander_self_collisions,
+                            random_tree, FMJ_WARN_CONTACTFULL)
+from support_sims import set_state as _set
 
 pytestmark = pytest.mark.gpu
 
-
-def _walker(spawn_z=0.045, solver='newton', cone='pyramidal', impratio=1.0):
-    from farms_mujoco_amd.model import salamander33, SOLVERS, CONES
-    m = salamander33(contacts=True, limits=True, spawn_z=spawn_z)
-    m.solver = SOLVERS[solver]; m.solver_iterations = 100; m.cone = CONES[cone]; m.impratio = impratio
-    return m
-
-
-def _set(phys, qpos, qvel, warm=None):
-    import torch
-    d = phys.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    if warm is not None:
-        d.qacc_warmstart[:] = torch.as_tensor(warm, dtype=torch.float32)
-    r64 = lambda t: t.cpu().numpy().astype(np.float64)
-    return r64(d.qpos), r64(d.qvel), r64(d.qacc_warmstart)
+_walker = functools.partial(walker, solver='newton')
 
 
 @pytest.mark.parametrize('solver', ['newton', 'cg'])
@@ -73,7 +62,6 @@ def test_newton_walk_follows_the_oracle(oracle, solver):
     and since Newton converges at every step (unlike PGS cut at 50 sweeps) the walk stays on the oracle's."""
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
-    from test_gpu_contacts import _trot_tape
     m = _walker(solver=solver)
     n, T = 8, 300
     tape = _trot_tape(m, n, T)
@@ -131,8 +119,6 @@ def test_newton_and_cg_with_self_collision_pairs(oracle, solver):
     import torch
     from farms_mujoco_amd.model import SOLVERS
     from farms_mujoco_amd.physics import BatchedPhysics
-    from test_oracle_contacts import _scissors
-    from test_gpu_contacts import _salamander_self_collisions
     for capsule in (False, True):
         m, q = _scissors(0.1, capsule=capsule)
         m.solver = SOLVERS[solver]; m.solver_iterations = 100
@@ -267,7 +253,6 @@ def test_elliptic_cone_walk_follows_the_oracle(oracle, solver):
     """300 steps of the trot with elliptic cones, fused loop with contact rows, against the oracle's walk with the same solver."""
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
-    from test_gpu_contacts import _trot_tape
     m = _walker(solver=solver, cone='elliptic')
     n, T = 8, 300
     tape = _trot_tape(m, n, T)
@@ -294,7 +279,6 @@ def test_elliptic_cone_teacher_forced_per_step(oracle):
     (rounded to fp32, as is the oracle's probe step): same contacts, row forces within 1e-3 of the largest force, velocity within 2e-3."""
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
-    from test_gpu_contacts import _trot_tape
     m = _walker(cone='elliptic')
     n, T = 8, 200
     tape = _trot_tape(m, n, T)
@@ -337,7 +321,6 @@ def test_primal_solvers_on_random_contact_trees(oracle, seed, solver, cone):
     import torch
     from farms_mujoco_amd.model import SOLVERS, CONES
     from farms_mujoco_amd.physics import BatchedPhysics
-    from test_gpu_random_trees import random_tree, FMJ_WARN_CONTACTFULL
     m = random_tree(seed, contacts=True)
     if m is None or m.nv == 0:
         pytest.skip('degenerate draw')
@@ -421,7 +404,6 @@ def test_primal_solvers_on_random_mesh_trees(oracle, seed, solver, cone):
     import torch
     from farms_mujoco_amd.model import SOLVERS, CONES
     from farms_mujoco_amd.physics import BatchedPhysics
-    from test_gpu_random_trees import random_tree, FMJ_WARN_CONTACTFULL
     m = random_tree(seed, contacts=True, meshes=True)
     assert m is not None and m.nv > 0 and m.nmeshvert > 0, f'seed {seed} no longer draws a tree with mesh geoms'
     m.solver = SOLVERS[solver]; m.cone = CONES[cone]; m.solver_iterations = 100

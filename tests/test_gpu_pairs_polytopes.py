@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 
 from parity_metrics import group_relerr, qvel_groups
-from test_oracle_contacts import _stack
+from support_models import stack as _stack
+from support_sims import sdf_wave as _SdfWave, oracle_initial_state as _oracle_initial_state
 
 pytestmark = pytest.mark.gpu
 
@@ -125,7 +126,6 @@ def test_from_sdf_mesh_collisions_and_self_collisions_end_to_end(oracle, tmp_pat
     import torch
     from farms_mujoco_amd.options import AnimatOptions, ArenaOptions, SimulationOptions, WaterOptions
     from farms_mujoco_amd.simulation.simulation import Simulation
-    from test_gpu_fused_parity import _SdfWave, _oracle_initial_state
     oct_ = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], float)
     (tmp_path / 'oct.obj').write_text(''.join(f'v {a} {b} {c}\n' for a, b, c in oct_))
     link = lambda name, x, geom: f'''<link name="{name}"><pose>{x} 0 0.06 0 0 0</pose>

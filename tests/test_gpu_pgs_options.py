@@ -4,32 +4,18 @@
     pgs_elliptic_block - also on models with explicit self-collision pairs;
   * the NOSLIP post-pass (oracle: noslip()) after PGS, and after Newton (which the device then runs on the dual problem).
 Every test compares the HIP path with the fp64 oracle on identical fp32 inputs."""
+import functools
+
 import numpy as np
 import pytest
 
 from parity_metrics import group_relerr, qvel_groups
+from support_models import walker, trot_tape as _trot_tape, salamander_self_collisions as _salamander_self_collisions
+from support_sims import set_state as _set
 
 pytestmark = pytest.mark.gpu
 
-
-def _walker(solver='pgs', cone='pyramidal', impratio=1.0, noslip=0, spawn_z=0.045, **kw):
-    from farms_mujoco_amd.model import salamander33, SOLVERS, CONES
-    m = salamander33(contacts=True, limits=True, spawn_z=spawn_z, **kw)
-    m.solver = SOLVERS[solver]; m.cone = CONES[cone]; m.impratio = impratio
-    m.noslip_iterations = noslip; m.noslip_tolerance = 1e-10
-    if solver != 'pgs':
-        m.solver_iterations = 100
-    return m
-
-
-def _set(phys, qpos, qvel, warm=None):
-    import torch
-    d = phys.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    if warm is not None:
-        d.qacc_warmstart[:] = torch.as_tensor(warm, dtype=torch.float32)
-    r = lambda t: t.cpu().numpy().astype(np.float64)
-    return r(d.qpos), r(d.qvel), r(d.qacc_warmstart)
+_walker = functools.partial(walker, solver='pgs', noslip=0)
 
 
 def _states(m, n, seed, belly=2):
@@ -93,7 +79,6 @@ def test_elliptic_cone_with_pgs_walk(oracle):
     from farms_mujoco_amd.data import AnimatData
     from farms_mujoco_amd.options import SimulationOptions
     from farms_mujoco_amd.simulation.simulation import Simulation
-    from test_gpu_contacts import _trot_tape
     m = _walker(cone='elliptic')
     n, T = 6, 100
     tape = _trot_tape(m, n, T).astype(np.float32)
@@ -118,7 +103,6 @@ def test_elliptic_cone_with_pairs(oracle):
     import torch
     from farms_mujoco_amd.model import CONES
     from farms_mujoco_amd.physics import BatchedPhysics
-    from test_gpu_contacts import _salamander_self_collisions
     m = _salamander_self_collisions()
     m.cone = CONES['elliptic']
     plane = int(np.nonzero(m.geom_type == 0)[0][0])

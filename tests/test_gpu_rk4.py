@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 
 from parity_metrics import relerr as _relerr
+from support_models import rand_state as _rand_state, walker as _walker
+from support_sims import set_state
 
 pytestmark = pytest.mark.gpu
 
@@ -15,7 +17,6 @@ def _physics(m, n):
 
 
 def _state(m, n, seed):
-    from test_gpu_step_parity import _rand_state
     return _rand_state(m, n, seed, qscale=0.2, vscale=0.3)
 
 
@@ -60,14 +61,13 @@ def test_rk4_step_matches_oracle_swimming(oracle):
 def test_rk4_walking_with_contacts_matches_oracle(oracle):
     """Limits + ground contacts (PGS): every pass makes its own contacts and solves its own rows from the step's warm start; 60 steps of
     the walker settling on the floor."""
-    from test_gpu_contacts import _walker, _set
     m = _walker()
     m.integrator = 1
     n, T = 8, 60
     phys, torch = _physics(m, n)
     rng = np.random.default_rng(4)
     q0 = np.tile(m.key_qpos, (n, 1)); q0[:, 7:] += rng.uniform(-0.1, 0.1, (n, m.nq - 7)); q0[:, 2] = 0.035 + 0.01*rng.uniform(size=n)
-    q32, v32 = _set(phys, q0, np.zeros((n, m.nv)))
+    q32, v32, _ = set_state(phys, q0, np.zeros((n, m.nv)))
     phys.step(T)
     torch.cuda.synchronize()
     d = phys.data

@@ -6,6 +6,8 @@ those of one shard holding every env - swimming (configs[1] / [2]), walking (con
 import numpy as np
 import pytest
 
+from support_sims import rows as _rows
+
 pytestmark = pytest.mark.gpu
 
 
@@ -15,11 +17,6 @@ def _swim_factory(T, morphology='salamander33'):
     def factory(lo, hi, device):
         return bench.build_sim(hi - lo, T, T, lo, str(device), morphology=morphology)[0]
     return factory
-
-
-def _rows(sim):
-    s = sim.task.data.sensors
-    return {k: getattr(s, k).array.cpu().numpy() for k in ('links', 'joints', 'xfrc')}
 
 
 @pytest.mark.parametrize('n_shards', [2, 3])

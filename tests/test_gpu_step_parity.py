@@ -7,24 +7,9 @@ import numpy as np
 import pytest
 
 from parity_metrics import relerr as _relerr, group_relerr, qpos_groups, qvel_groups
+from support_models import rand_state as _rand_state
 
 pytestmark = pytest.mark.gpu
-
-
-def _rand_state(m, n, seed, qscale=0.3, vscale=0.5):
-    """Random but physically sane state: arbitrary root pose, hinge angles +-qscale, ctrl near the pose
-    on the position actuators only (velocity / motor actuators idle, as in every BASELINE config)."""
-    rng = np.random.default_rng(seed)
-    qpos = np.tile(m.qpos0, (n, 1))
-    qpos[:, 7:] += rng.uniform(-qscale, qscale, (n, m.nq - 7))
-    q = rng.normal(size=(n, 4)); qpos[:, 3:7] = q/np.linalg.norm(q, axis=1, keepdims=True)
-    qpos[:, :3] += rng.uniform(-0.2, 0.2, (n, 3))
-    qvel = rng.normal(size=(n, m.nv))*vscale
-    ctrl = np.zeros((n, m.nu))
-    for a in range(m.nu):
-        if m.actuator_tags[a] == 'position':
-            ctrl[:, a] = qpos[:, m.jnt_qposadr[m.actuator_jntid[a]]] + rng.uniform(-0.05, 0.05, n)
-    return qpos, qvel, ctrl
 
 
 @pytest.fixture(scope='module')

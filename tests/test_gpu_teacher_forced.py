@@ -17,20 +17,15 @@ import numpy as np
 import pytest
 
 from parity_metrics import group_relerr, qvel_groups
+from support_models import walker as _walker, trot_tape as _trot_tape
 
 pytestmark = pytest.mark.gpu
-
-
-def _walker():
-    from farms_mujoco_amd.model import salamander33
-    return salamander33(contacts=True, limits=True, spawn_z=0.045)
 
 
 def test_teacher_forced_walk_per_step_parity_and_kkt(oracle):
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
     from farms_mujoco_amd.model import SOLVERS
-    from test_gpu_contacts import _trot_tape
     m = _walker()
     n, T = 8, 1000
     tape = _trot_tape(m, n, T)

@@ -5,30 +5,10 @@ import numpy as np
 import pytest
 
 from parity_metrics import relerr as _relerr, group_relerr, qpos_groups, qvel_groups, link_row_groups
+from support_models import finned_eel as _finned_eel
+from support_sims import swim_sim, wave_at, swim_oracle as _swim_oracle
 
 pytestmark = pytest.mark.gpu
-
-
-def _finned_eel(n_joints=40):
-    """An eel whose links 1..n carry a welded fin body (no joint): nbody past 64 with every dof inside one wave."""
-    import farms_mujoco_amd.model as mm
-    b = mm.ModelBuilder('finned_eel', timestep=1e-3)
-    L, n = 0.05, n_joints + 1
-    radii = np.linspace(0.015, 0.005, n)
-    for i in range(n):
-        r = radii[i]
-        mass = 1000.0*(np.pi*r*r*L + 4.0/3.0*np.pi*r**3)
-        kw = dict(pos=(0, 0, -0.1) if i == 0 else (L, 0, 0), mass=mass, ipos=(L/2, 0, 0), inertia=mm._capsule_inertia(mass, r, L))
-        if i == 0:
-            b.add_body('body_0', 'world', joint='free', **kw)
-        else:
-            b.add_body(f'body_{i}', f'body_{i-1}', joint='hinge', jname=f'joint_body_{i}', axis=(0, 0, 1), damping=5e-4, **kw)
-            fm = 0.2*mass
-            b.add_body(f'fin_{i}', f'body_{i}', pos=(L/2, 0, r), mass=fm, ipos=(0, 0, 0.005),
-                       inertia=(fm*2e-5, fm*3e-5, fm*1e-5))
-    for i in range(1, n):
-        b.add_position_actuator(f'joint_body_{i}', kp=0.5)
-    return b.compile()
 
 
 def _make(name):
@@ -98,40 +78,6 @@ def test_step_parity_wide_models(oracle, name, T):
     assert err < max(1e-4, 6*flo)
 
 
-def _swim_sim(m, n, T, seed=9):
-    import torch
-    import farms_mujoco_amd.model as mm
-    from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
-    from farms_mujoco_amd.control import WaveController
-    from farms_mujoco_amd.simulation.simulation import Simulation
-    qpos, qvel, psi = mm.synthetic_batch(m, n, seed=seed)
-    sim = Simulation.from_sdf(SimulationOptions(timestep=m.timestep, n_iterations=T), AnimatOptions.from_model(m),
-                              ArenaOptions(water=WaterOptions(height=0.0)), model=m, n_envs=n,
-                              controller=WaveController(m, psi, frequency=1.5), buffer_size=T)
-    sim.reset()
-    d = sim.physics.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    sim.physics.forward(disable_actuation=True)
-    return sim
-
-
-def _swim_oracle(oracle, sim, m, T):
-    d = sim.physics.data
-    q = d.qpos.cpu().numpy().astype(np.float64); v = d.qvel.cpu().numpy().astype(np.float64)
-    st = dict(qpos=q, qvel=v)
-    fds = [oracle.forward_debug(m, q[i], v[i]) for i in range(q.shape[0])]
-    for k in ('xpos', 'xquat', 'xipos'):
-        st[k] = np.array([fd[k] for fd in fds])
-    sd = np.array([fd['sensordata'] for fd in fds]); sd[:, 6*(m.nbody - 1) + 3*m.n_sensor_joints:] = 0.0
-    st['sensordata'] = sd
-    h = sim.task._callbacks[0].handler
-    c = sim.task._controller
-    water = dict(surface=h.water._surface, velocity=h.water._velocity, viscosity=h.water._viscosity, gravity=-9.81, use_buoyancy=h.buoyancy)
-    wave = dict(amplitude=c.amplitude.cpu().numpy(), phase_lag=c.phase_lag.cpu().numpy(), env_phase=c.env_phase.cpu().numpy(),
-                frequency=c.frequency)
-    return oracle.run_fused(m, st, T, swim=h.swim_dict(), water=water, buffer_size=T, controller=1, wave=wave, n_threads=8)
-
-
 def test_fused_swim_of_a_wide_centipede(oracle):
     """Simulation.run(fused=True) on centipede(20, 25): rows, drag + buoyancy, wave controller in the kernel, against the oracle's
     fused loop at 6x the fp32-storage floor."""
@@ -139,7 +85,7 @@ def test_fused_swim_of_a_wide_centipede(oracle):
     import farms_mujoco_amd.model as mm
     m = mm.centipede(20, 25)
     T = 40
-    sim = _swim_sim(m, 12, T)
+    sim = swim_sim(12, T, m=m, seed=9, controller_of=wave_at(1.5))[0]
     assert sim.physics.kernel_info()['threads_per_env'] == 128
     ref = _swim_oracle(oracle, sim, m, T)
     with oracle.fp32_storage():
@@ -224,9 +170,9 @@ def test_nan_state_freezes_a_wide_env():
     m = mm.centipede(20, 25)
     n, T, bad, dof = 5, 30, 2, 100
     assert dof >= 64 and dof < m.nv
-    clean = _swim_sim(m, n, T)
+    clean = swim_sim(n, T, m=m, seed=9, controller_of=wave_at(1.5))[0]
     clean.run(fused=True)
-    sim = _swim_sim(m, n, T)
+    sim = swim_sim(n, T, m=m, seed=9, controller_of=wave_at(1.5))[0]
     sim.physics.data.qvel[bad, dof] = float('nan')
     q_before = sim.physics.data.qpos[bad].clone()
     with pytest.raises(PhysicsError):
@@ -248,7 +194,7 @@ def test_checkpoint_of_a_wide_model_is_bitwise(tmp_path):
     import torch
     import farms_mujoco_amd.model as mm
     m = mm.centipede(20, 25)
-    sim = _swim_sim(m, 4, 100)
+    sim = swim_sim(4, 100, m=m, seed=9, controller_of=wave_at(1.5))[0]
     ck = sim.save_state(str(tmp_path/'state.npz'))
     sim.step_fused(50)
     torch.cuda.synchronize()

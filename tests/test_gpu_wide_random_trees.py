@@ -11,30 +11,10 @@ import pytest
 
 from parity_metrics import relerr, group_relerr, qpos_groups, qvel_groups, link_row_groups
 from wide_trees import WIDE_SHAPES, shape_tree, tree_properties, dof_depth
+from support_models import tree_inputs as _inputs, FMJ_WARN_BADQPOS
+from support_sims import f64 as _f64, swim_sim, wave_at, oracle_initial_state, swim_water, check_random_tree_vs_oracle
 
 pytestmark = pytest.mark.gpu
-
-FMJ_WARN_BADQPOS = 1          # include/fmj.h
-
-
-def _f64(t):
-    return t.cpu().numpy().astype(np.float64)
-
-
-def _inputs(m, n, seed):
-    """Random state per env: qpos around qpos0 (normalised free quaternions), qvel, ctrl, qpos_spring and external forces on every body
-    (those of index >= 64 included)."""
-    rng = np.random.default_rng(3000 + seed)
-    qpos = np.tile(m.qpos0, (n, 1)) + rng.uniform(-0.4, 0.4, (n, m.nq))
-    for j in range(m.njnt):
-        if m.jnt_type[j] == 0:
-            a = m.jnt_qposadr[j]; q = rng.normal(size=(n, 4)); qpos[:, a+3:a+7] = q/np.linalg.norm(q, axis=1, keepdims=True)
-    qvel = rng.normal(size=(n, m.nv))*0.5
-    ctrl = rng.uniform(-0.6, 0.6, (n, m.nu))
-    xf = rng.normal(size=(n, m.nbody, 6))*0.05; xf[:, 0] = 0
-    qs = np.tile(m.qpos_spring, (n, 1)) + rng.uniform(-0.1, 0.1, (n, m.nq))
-    return qpos, qvel, ctrl, xf, qs
-
 
 def _wide_phys(m, n, monkeypatch, qpos, qvel, ctrl=None, xf=None, qs=None):
     """BatchedPhysics of m in the two-wave kernel (FMJ_WIDE=1 is read at fmj_create; models past 64 take it anyway) with the inputs
@@ -219,7 +199,6 @@ def test_wide_forward_matches_oracle(oracle, disable_actuation, monkeypatch):
 def test_small_random_tree_on_the_wide_kernel(oracle, seed, monkeypatch):
     """FMJ_WIDE=1 on random_tree(0..19) (3..21 bodies): a second wave with no body and no dof, most lanes of the first idle; the
     assertions of test_random_tree_vs_oracle."""
-    from test_gpu_random_trees import check_random_tree_vs_oracle
     monkeypatch.setenv('FMJ_WIDE', '1')
     check_random_tree_vs_oracle(oracle, seed, 128)
 
@@ -299,49 +278,21 @@ def test_wide_implicitfast_step_matches_oracle(oracle, clamp, monkeypatch):
 
 # ---- sub-steps in the fused loop ---------------------------------------------------------------------------------------------------
 
-def _substep_sim(n, T, substeps, sub_links):
-    import torch
-    import farms_mujoco_amd.model as mm
-    from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
-    from farms_mujoco_amd.control import WaveController
-    from farms_mujoco_amd.simulation.simulation import Simulation
-    from farms_mujoco_amd.simulation.task import SwimmingCallback
-    m = mm.centipede(20, 25, timestep=1e-3/substeps)
-    qpos, qvel, psi = mm.synthetic_batch(m, n, seed=9)
-    animat, arena = AnimatOptions.from_model(m), ArenaOptions(water=WaterOptions(height=0.0))
-    sim = Simulation.from_sdf(SimulationOptions(timestep=1e-3, n_iterations=T, num_sub_steps=substeps), animat, arena, model=m, n_envs=n,
-                              controller=WaveController(m, psi, frequency=1.5), buffer_size=T,
-                              callbacks=[SwimmingCallback(animat, arena, substep=sub_links)])
-    sim.reset()
-    d = sim.physics.data
-    d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    sim.physics.forward(disable_actuation=True)
-    return sim, m
-
-
 @pytest.mark.parametrize('substeps,sub_links', [(2, False), (3, True), (5, True)])
 def test_wide_fused_substeps_match_oracle(oracle, substeps, sub_links):
     """num_sub_steps > 1 in the fused launch of centipede(20, 25) in water: state, links rows and xfrc rows against the oracle's
     run_fused (the counters of test_fused_substeps_match_oracle) at 6x the fp32-storage floor per component."""
     import torch
+    import farms_mujoco_amd.model as mm
     n, T = 4, 24
-    sim, m = _substep_sim(n, T, substeps, sub_links)
+    m = mm.centipede(20, 25, timestep=1e-3/substeps)
+    sim = swim_sim(n, T, m=m, seed=9, controller_of=wave_at(1.5), substeps=substeps, swim_substep=sub_links)[0]
     assert sim.physics.kernel_info()['threads_per_env'] == 128
     assert sim.task.fusable() and sim.task.substeps == substeps and sim.task.substeps_links == sub_links
     d = sim.physics.data
-    q = _f64(d.qpos); v = _f64(d.qvel)
-    st = dict(qpos=q, qvel=v)
-    fds = [oracle.forward_debug(m, q[i], v[i]) for i in range(n)]
-    for k in ('xpos', 'xquat', 'xipos'):
-        st[k] = np.array([fd[k] for fd in fds])
-    sd = np.array([fd['sensordata'] for fd in fds]); sd[:, 6*(m.nbody - 1) + 3*m.n_sensor_joints:] = 0.0
-    st['sensordata'] = sd
-    h = sim.task._callbacks[0].handler
-    c = sim.task._controller
-    water = dict(surface=h.water._surface, velocity=h.water._velocity, viscosity=h.water._viscosity, gravity=-9.81, use_buoyancy=h.buoyancy)
-    wave = dict(amplitude=c.amplitude.cpu().numpy(), phase_lag=c.phase_lag.cpu().numpy(), env_phase=c.env_phase.cpu().numpy(),
-                frequency=c.frequency)
-    kw = dict(swim=h.swim_dict(), water=water, buffer_size=T, controller=1, wave=wave, n_threads=8, substeps=substeps,
+    st = oracle_initial_state(oracle, sim, m)
+    swim, water, wave = swim_water(sim, wave=True)
+    kw = dict(swim=swim, water=water, buffer_size=T, controller=1, wave=wave, n_threads=8, substeps=substeps,
               substep_links=sub_links, n_iterations=T)
     ref = oracle.run_fused(m, st, T, **kw)
     with oracle.fp32_storage():

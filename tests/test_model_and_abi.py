@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from farms_mujoco_amd.model import salamander33, eel, centipede, ModelBuilder, JNT_FREE, np_mass_matrix
+from support_models import box_walker as _box_walker
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -174,23 +175,6 @@ def test_model_size_limits_are_refused_with_a_message_that_names_them():
     m.noslip_iterations = -1
     rc, msg = create(m)
     assert rc != 0 and (rc == 4 or 'noslip' in msg), (rc, msg)
-
-
-def _box_walker():
-    """A free box trunk with two limited hinged box limbs above a plane: dof chains of 7 (row length 8), 2 + 4 * max_contacts rows."""
-    from farms_mujoco_amd.model import ModelBuilder, GEOM_BOX, GEOM_PLANE
-    b = ModelBuilder('boxbot', timestep=1e-3)
-    b.options['max_contacts'] = 16
-    b.add_body('trunk', pos=(0, 0, 0.06), mass=0.5, inertia=(2e-4, 6e-4, 7e-4), joint='free')
-    b.add_geom('trunk', GEOM_BOX, (0.06, 0.03, 0.015), friction=(0.8, 0, 0))
-    for side, y in (('L', 0.04), ('R', -0.04)):
-        b.add_body(f'limb_{side}', parent='trunk', pos=(0.03, y, 0.0), mass=0.05, inertia=(2e-6, 8e-6, 8e-6),
-                   joint='hinge', axis=(0, 1, 0), damping=1e-3, limited=True, range=(-0.6, 0.6))
-        b.add_geom(f'limb_{side}', GEOM_BOX, (0.03, 0.008, 0.008), pos=(0.03, 0, -0.02), quat=(0.9659258, 0, 0.258819, 0),
-                   friction=(1.0, 0, 0))
-        b.add_position_actuator(f'joint_limb_{side}', kp=0.05)
-    b.add_geom('world', GEOM_PLANE, (0, 0, 0), friction=(0, 0, 0))
-    return b.compile()
 
 
 def test_model_refusals_come_before_the_device_lookup():

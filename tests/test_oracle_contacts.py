@@ -3,6 +3,7 @@ They cannot prove bit-parity with MuJoCo (absent), but they pin the model to sta
 import numpy as np
 
 from farms_mujoco_amd.model import ModelBuilder, GEOM_PLANE, GEOM_SPHERE, GEOM_CAPSULE
+from support_models import scissors as _scissors, stack as _stack
 
 
 def _ball(mu=1.0, h=1e-3, mass=0.5, r=0.05, gravity=(0, 0, -9.81)):
@@ -227,25 +228,6 @@ def test_box_settles_on_heightfield_slope(oracle):
     assert abs(quat2mat(o['qpos'][0, 3:7])[:, 2] @ n_exp - 1.0) < 1e-3      # box z axis along the slope normal
 
 
-def _scissors(theta=0.35, r=0.03, L=0.2, friction=0.0, capsule=False):
-    """A fixed post with two equal arms hinged about z at the origin, tip spheres (or capsules along the arms) in an
-    explicit contact pair: the arms close like scissors."""
-    from farms_mujoco_amd.model import GEOM_CAPSULE, axisangle2quat
-    b = ModelBuilder('scissors', timestep=1e-3, gravity=(0, 0, 0))
-    b.add_body('post', 'world', pos=(0, 0, 0.5), mass=1.0, inertia=(1e-3, 1e-3, 1e-3))
-    for name, sgn in (('arm_a', +1), ('arm_b', -1)):
-        b.add_body(name, 'post', mass=0.2, ipos=(L/2, 0, 0), inertia=(1e-5, 7e-4, 7e-4), joint='hinge', axis=(0, 0, 1), damping=1e-3,
-                   qpos0=0.0)
-        if capsule:                    # the outer half of the arm: the two capsules only meet when the arms close
-            b.add_geom(name, GEOM_CAPSULE, (r, L/4), pos=(0.75*L, 0, 0), quat=axisangle2quat([0, 1, 0], np.pi/2))
-        else:
-            b.add_geom(name, GEOM_SPHERE, (r,), pos=(L, 0, 0))
-    b.add_contact_pair('arm_a', 'arm_b', friction=friction)
-    b.options['max_contacts'] = 4
-    m = b.compile()
-    return m, np.array([theta, -theta])
-
-
 def test_self_collision_pair_geometry_and_symmetry(oracle):
     """Explicit contact pair between two tip spheres (reference mjcf.py:1012-1033: contact/pair, condim 3, friction 0):
     normal from geom1 to geom2, position midway, distance = centre distance - 2 r; the contact pushes the two arms apart
@@ -349,25 +331,6 @@ def test_mesh_keeps_its_four_deepest_vertices(oracle):
 
 
 # ---- explicit pairs with a box, a cylinder or a convex mesh (include/fmj.h, ABI 6; reference mjcf.py:1012-1033,270-413) --------------
-
-def _stack(lower, upper, z, tilt=0.0, max_contacts=8, gravity=(0, 0, 0), **pair_kw):
-    """A welded base carrying geom `lower`, and a body on a vertical slide joint carrying geom `upper`, in an explicit pair.
-    lower / upper = (type, size[, vertices]); the slider's qpos is its height z."""
-    from farms_mujoco_amd.model import GEOM_MESH, axisangle2quat
-    b = ModelBuilder('stack', timestep=1e-3, gravity=gravity)
-    b.add_body('base', 'world', pos=(0, 0, 0), mass=1.0, inertia=(1e-3, 1e-3, 1e-3))
-    b.add_body('top', 'base', mass=0.5, inertia=(1e-3, 1e-3, 1e-3), joint='slide', axis=(0, 0, 1), damping=0.0, qpos0=0.0)
-    for body, (gt, size, *rest) in (('base', lower), ('top', upper)):
-        quat = axisangle2quat([1, 0, 0], tilt) if body == 'top' else (1, 0, 0, 0)
-        if gt == GEOM_MESH:
-            b.add_mesh_geom(body, rest[0], quat=quat)
-        else:
-            b.add_geom(body, gt, size, quat=quat)
-    b.add_contact_pair('base', 'top', **pair_kw)
-    b.options['max_contacts'] = max_contacts
-    m = b.compile()
-    return m, np.array([z])
-
 
 def _pair_contacts(oracle, m, q):
     o = oracle.forward_debug(m, q, np.zeros(m.nv))

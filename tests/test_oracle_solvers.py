@@ -9,17 +9,13 @@ import numpy as np
 import pytest
 
 from farms_mujoco_amd.model import ModelBuilder, GEOM_PLANE, GEOM_BOX, GEOM_SPHERE, SOLVERS, CONES
+from support_models import walker as _walker, trot_tape as _trot_tape, random_tree
 
 
 def _with(m, solver, iterations, tolerance):
     m2 = copy.copy(m)
     m2.solver = SOLVERS[solver]; m2.solver_iterations = iterations; m2.solver_tolerance = tolerance
     return m2
-
-
-def _walker():
-    from farms_mujoco_amd.model import salamander33
-    return salamander33(contacts=True, limits=True, spawn_z=0.045)
 
 
 def _box_bot():
@@ -94,7 +90,6 @@ def test_pgs_newton_cg_agree_on_the_box_bot(oracle):
 
 @pytest.mark.parametrize('seed', range(100, 110))
 def test_pgs_newton_cg_agree_on_random_contact_trees(oracle, seed):
-    from test_gpu_random_trees import random_tree
     m = random_tree(seed, contacts=True)
     if m is None or m.nv == 0:
         pytest.skip('degenerate draw')
@@ -118,7 +113,6 @@ def test_newton_walk_equals_the_converged_pgs_walk(oracle):
     same walk to 1e-6: two algorithms, one trajectory - and a measure of how little the walking dynamics amplifies a 1e-9
     difference per step (x100 in 300 steps; it is not chaotic on this horizon).  PGS cut at 50 sweeps (the configuration
     BASELINE configs[3] names) is a different, unconverged map: it drifts from that walk by ~1e-2."""
-    from test_gpu_contacts import _trot_tape
     m = _walker()
     n, T = 2, 200
     tape = _trot_tape(m, n, T)

@@ -7,61 +7,13 @@ from farms_mujoco_amd.model import ModelBuilder, np_mass_matrix, np_kinematics, 
 from farms_mujoco_amd.options import AnimatOptions, SimulationOptions, ArenaOptions
 from farms_mujoco_amd.simulation.mjcf import sdf2model, setup_model, get_local_transform
 from farms_mujoco_amd.units import SimulationUnitScaling
-
-SDF = """<?xml version="1.0"?>
-<sdf version="1.6">
-  <model name="swimmer">
-    <pose>0 0 0 0 0 0</pose>
-    <link name="head">
-      <pose>0 0 0 0 0 0</pose>
-      <inertial><pose>0.05 0 0 0 0 0</pose><mass>0.10</mass>
-        <inertia><ixx>2e-5</ixx><ixy>0</ixy><ixz>0</ixz><iyy>9e-5</iyy><iyz>0</iyz><izz>9e-5</izz></inertia></inertial>
-      <collision name="head_col"><pose>0.05 0 0 0 1.5707963267948966 0</pose>
-        <geometry><capsule><radius>0.02</radius><length>0.1</length></capsule></geometry></collision>
-    </link>
-    <link name="trunk">
-      <pose>0.1 0 0 0 0 0.3</pose>
-      <inertial><pose>0.05 0 0 0 0 0.2</pose><mass>0.08</mass>
-        <inertia><ixx>1.5e-5</ixx><ixy>1e-6</ixy><ixz>0</ixz><iyy>7e-5</iyy><iyz>0</iyz><izz>7e-5</izz></inertia></inertial>
-      <collision name="trunk_col"><pose>0.05 0 0 0 0 0</pose><geometry><sphere><radius>0.02</radius></sphere></geometry></collision>
-    </link>
-    <link name="tail">
-      <pose>0.19553365 0.02955202 0 0 0 0.3</pose>
-      <inertial><pose>0.04 0 0 0 0 0</pose><mass>0.04</mass>
-        <inertia><ixx>5e-6</ixx><ixy>0</ixy><ixz>0</ixz><iyy>2e-5</iyy><iyz>0</iyz><izz>2e-5</izz></inertia></inertial>
-    </link>
-    <link name="fin">
-      <pose>0.15 0.03 0 0 0 1.0</pose>
-      <inertial><pose>0.01 0 0 0 0 0</pose><mass>0.005</mass>
-        <inertia><ixx>1e-6</ixx><ixy>0</ixy><ixz>0</ixz><iyy>1e-6</iyy><iyz>0</iyz><izz>1e-6</izz></inertia></inertial>
-    </link>
-    <joint name="j_trunk" type="revolute"><parent>head</parent><child>trunk</child><pose>0 0 0 0 0 0</pose>
-      <axis><xyz>0 0 1</xyz><limit><lower>-1.0</lower><upper>1.0</upper></limit></axis></joint>
-    <joint name="j_tail" type="revolute"><parent>trunk</parent><child>tail</child><pose>0 0 0 0 0 0</pose>
-      <axis><xyz>0 0 1</xyz></axis></joint>
-    <joint name="j_fin" type="continuous"><parent>trunk</parent><child>fin</child><pose>0.002 0 0 0 0 0</pose>
-      <axis><xyz>0 1 0</xyz></axis></joint>
-  </model>
-</sdf>
-"""
-
+from support_models import SDF, sdf_options as _options
 
 @pytest.fixture
 def sdf_path(tmp_path):
     p = tmp_path/'swimmer.sdf'
     p.write_text(SDF)
     return str(p)
-
-
-def _options(sdf_path):
-    links = [AnimatOptions.link(n, swimming=True, drag_coefficients=[[-0.01, -0.5, -0.5], [-1e-6, -1e-5, -1e-5]])
-             for n in ('head', 'trunk', 'tail', 'fin')]
-    joints = [AnimatOptions.joint('j_trunk', initial=(0.1, 0.0), damping=1e-3, stiffness=0.02),
-              AnimatOptions.joint('j_tail', initial=(-0.2, 0.5), damping=2e-3), AnimatOptions.joint('j_fin', damping=1e-4)]
-    motors = [AnimatOptions.motor('j_trunk', gains=(0.5, 0.01)), AnimatOptions.motor('j_tail', gains=(0.4, 0.0), limits_torque=[-0.3, 0.3]),
-              AnimatOptions.motor('j_fin', gains=(0.05, 0.0))]
-    return AnimatOptions(name='swimmer', links=links, joints=joints, motors=motors, sdf=sdf_path,
-                         spawn_pose=(0.1, -0.2, -0.05, 0.0, 0.0, 0.4), spawn_velocity=(0.1, 0, 0, 0, 0, 0.2))
 
 
 def test_reader(sdf_path):

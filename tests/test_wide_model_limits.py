@@ -11,28 +11,9 @@ import sys
 import numpy as np
 import pytest
 
+from support_capi import create as _create, no_gpu as _no_gpu, FMJ_ERR_UNSUPPORTED, FMJ_ERR_NODEVICE
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FMJ_ERR_UNSUPPORTED, FMJ_ERR_NODEVICE = 2, 4
-
-
-def _create(m):
-    from farms_mujoco_amd import _lib
-    if not os.path.exists(_lib.SO_PATH):
-        pytest.skip('libfmj_hip.so not built')
-    lib = _lib.load()
-    c = m.as_c(); ctx = ctypes.c_void_p()
-    rc = lib.fmj_create(ctypes.byref(c), 4, 0, ctypes.byref(ctx))
-    if rc == 0:
-        lib.fmj_destroy(ctx)
-    return rc, lib.fmj_last_error().decode()
-
-
-def _no_gpu():
-    try:
-        import torch
-        return not torch.cuda.is_available()
-    except Exception:
-        return True
 
 
 def test_wide_model_sizes():

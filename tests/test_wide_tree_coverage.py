@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from wide_trees import WIDE_SHAPES, shape_tree, tree_properties, elimination_rounds
-from test_wide_model_limits import _create, _no_gpu, FMJ_ERR_NODEVICE
+from support_capi import create as _create, no_gpu as _no_gpu, FMJ_ERR_NODEVICE
 
 
 @pytest.fixture(scope='module')
@@ -89,7 +89,7 @@ RANDOM_TREE_DIGEST = '00dcf40a493afc37f913a6f2610ae325581e73e4'
 
 def random_tree_digest():
     import hashlib
-    from test_gpu_random_trees import random_tree
+    from support_models import random_tree
     h = hashlib.sha1()
     for seed in range(20):
         m = random_tree(seed)
