@@ -472,100 +472,22 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
       const int g = sl;                              // fmj_create: ngeom <= 32 for this kernel
       const float4 pn = pn0, pp = pp0;
       int cnt = 0; float rad = 0.f, mu = 0.f;
-      if (g < M.ngeom) {
-        const int4 gi = GTABI(g, 0);
-        if (gi.x == FMJ_GEOM_SPHERE || gi.x == FMJ_GEOM_CAPSULE) {
-          const float4 gs = GTAB(g, 1), gp = GTAB(g, 2), gq = GTAB(g, 3);
-          const float4 bp = *(const float4*)(PO + gi.y * 8), bq = *(const float4*)(PO + gi.y * 8 + 4);
-          const q4 bqq = {bq.x, bq.y, bq.z, bq.w};
-          const v3 cen = add3(mk3(bp.x, bp.y, bp.z), qrot(bqq, mk3(gp.x, gp.y, gp.z)));
-          rad = gs.x; mu = fmaxf(fmaxf(pp.x, gs.w), 1e-5f);
-          v3 ax = mk3(0.f, 0.f, 0.f);
-          if (gi.x == FMJ_GEOM_CAPSULE) { const q4 gqq = {gq.x, gq.y, gq.z, gq.w}; ax = scl3(qrot(qmul(bqq, gqq), mk3(0.f, 0.f, 1.f)), gs.y); }
-          const v3 c0 = add3(cen, ax), c1 = sub3(cen, ax);
-          v3 n0, n1;
-          const float d0 = ground_dist(M, 0, pn, pp, c0, &n0) - rad;
-          const float d1 = ground_dist(M, 0, pn, pp, c1, &n1) - rad;
-          const bool a0 = d0 < 0.f, a1 = gi.x == FMJ_GEOM_CAPSULE && d1 < 0.f;
-          if (a0) { g_cq[0] = c0; g_dq[0] = d0; g_nq[0] = n0; cnt = 1; }
-          if (a1) { if (cnt == 0) { g_cq[0] = c1; g_dq[0] = d1; g_nq[0] = n1; } else { g_cq[1] = c1; g_dq[1] = d1; g_nq[1] = n1; } cnt++; }
-        }
-      }
-      if (M.any_box) {
-        const int4 gi = g < M.ngeom ? GTABI(g, 0) : make_int4(-1, 0, 0, 0);
-        if (gi.x == FMJ_GEOM_BOX) {
-          const float4 gs = GTAB(g, 1), gp = GTAB(g, 2), gq = GTAB(g, 3);
-          const float4 bp = *(const float4*)(PO + gi.y * 8), bq = *(const float4*)(PO + gi.y * 8 + 4);
-          const q4 bqq = {bq.x, bq.y, bq.z, bq.w}, gqq = {gq.x, gq.y, gq.z, gq.w};
-          const q4 wq = qmul(bqq, gqq);
-          const v3 cen = add3(mk3(bp.x, bp.y, bp.z), qrot(bqq, mk3(gp.x, gp.y, gp.z)));
-          const v3 ex = scl3(qrot(wq, mk3(1.f, 0.f, 0.f)), gs.x), ey = scl3(qrot(wq, mk3(0.f, 1.f, 0.f)), gs.y), ez = scl3(qrot(wq, mk3(0.f, 0.f, 1.f)), gs.z);
-          mu = fmaxf(fmaxf(pp.x, gs.w), 1e-5f);
-#pragma unroll
-          for (int corner = 0; corner < 8; corner++) {
-            const v3 c = add3(add3(cen, (corner & 1) ? ex : scl3(ex, -1.f)), add3((corner & 2) ? ey : scl3(ey, -1.f), (corner & 4) ? ez : scl3(ez, -1.f)));
-            v3 nc;
-            const float d = ground_dist(M, 0, pn, pp, c, &nc);
-            const bool pen = d < 0.f && cnt < 4;
-#pragma unroll
-            for (int k = 0; k < 4; k++) if (pen && cnt == k) { g_cq[k] = c; g_dq[k] = d; g_nq[k] = nc; }
-            cnt += pen ? 1 : 0;
-          }
-        }
-        if (gi.x == FMJ_GEOM_CYLINDER) {      // rim points (the oracle's collide_ground, MuJoCo's mjc_PlaneCylinder construction)
-          const float4 gs = GTAB(g, 1), gp = GTAB(g, 2), gq = GTAB(g, 3);
-          const float4 bp = *(const float4*)(PO + gi.y * 8), bq = *(const float4*)(PO + gi.y * 8 + 4);
-          const q4 bqq = {bq.x, bq.y, bq.z, bq.w}, gqq = {gq.x, gq.y, gq.z, gq.w};
-          const q4 wq = qmul(bqq, gqq);
-          const v3 cen = add3(mk3(bp.x, bp.y, bp.z), qrot(bqq, mk3(gp.x, gp.y, gp.z)));
-          v3 nrm_;
-          const float dist = ground_dist(M, 0, pn, pp, cen, &nrm_);
-          v3 axis = qrot(wq, mk3(0.f, 0.f, 1.f));
-          float prjaxis = dot3(nrm_, axis);
-          if (prjaxis > 0.f) { axis = scl3(axis, -1.f); prjaxis = -prjaxis; }
-          v3 vec = sub3(scl3(axis, prjaxis), nrm_);
-          const float len2 = dot3(vec, vec);
-          if (len2 >= 1e-30f) vec = scl3(vec, gs.x / sqrtf(len2)); else vec = scl3(qrot(wq, mk3(1.f, 0.f, 0.f)), gs.x);
-          const float prjvec = dot3(vec, nrm_);
-          axis = scl3(axis, gs.y); prjaxis *= gs.y;
-          mu = fmaxf(fmaxf(pp.x, gs.w), 1e-5f);
-          const float d0 = dist + prjaxis + prjvec;
-          if (d0 < 0.f) {
-            g_cq[0] = add3(cen, add3(vec, axis)); g_dq[0] = d0; cnt = 1;
-            const float d1 = dist - prjaxis + prjvec;
-            if (d1 < 0.f) { g_cq[1] = add3(cen, sub3(vec, axis)); g_dq[1] = d1; cnt = 2; }
-            v3 vec1 = cross(vec, axis);
-            const float l1 = sqrtf(dot3(vec1, vec1));
-            if (l1 > 1e-15f) vec1 = scl3(vec1, gs.x * 0.8660254037844386f / l1);
-            const float prjvec1 = dot3(vec1, nrm_);
-#pragma unroll
-            for (int sg = 0; sg < 2; sg++) {
-              const float sgn = sg ? -1.f : 1.f;
-              const float d2 = dist + prjaxis - 0.5f * prjvec + sgn * prjvec1;
-              const v3 c2 = add3(cen, add3(scl3(vec1, sgn), sub3(axis, scl3(vec, 0.5f))));
-              const bool pen = d2 < 0.f;
-#pragma unroll
-              for (int k = 1; k < 4; k++) if (pen && cnt == k) { g_cq[k] = c2; g_dq[k] = d2; }
-              cnt += pen ? 1 : 0;
-            }
-          }
-#pragma unroll
-          for (int k = 0; k < 4; k++) g_nq[k] = nrm_;
-        }
-      }
+#define NP_CQ g_cq
+#define NP_NQ g_nq
+#define NP_DQ g_dq
+#define NP_PL 0
+#include "fmj_narrow_ground.inc"      // sphere / capsule, box, cylinder: cnt, rad, mu and the first cnt entries of g_cq / g_nq / g_dq
+#undef NP_CQ
+#undef NP_NQ
+#undef NP_DQ
+#undef NP_PL
       int before = 0, total = 0;
 #pragma unroll
       for (int k = 0; k < 4; k++) { const unsigned bk = HALF_BALLOT(cnt > k); before += __popc(bk & lt32); total += __popc(bk); }
       g_slot = before; ncon = total; g_cnt = cnt; g_rad = rad; g_mu = mu;
     }
     // joint limit rows (mj_instantiateLimit): lane = dof, rows ordered by joint then side (-1, +1)
-    const float4 lim = DT2(mydof, 3);
-    float dist_lo = 0.f, dist_hi = 0.f; bool act_lo = false, act_hi = false;
-    if (d_scalar && lim.x != 0.f) {
-      const float qj = QP[d_qadr];
-      dist_lo = qj - lim.y; dist_hi = lim.z - qj;
-      act_lo = dist_lo < lim.w; act_hi = dist_hi < lim.w;
-    }
+    JOINT_LIMIT_ACT(DT2(mydof, 3));
     if (retired) { act_lo = false; act_hi = false; }
     const unsigned m_lo = HALF_BALLOT(act_lo), m_hi = HALF_BALLOT(act_hi);
     const int e_lo = __popc(m_lo & lt32) + __popc(m_hi & lt32);
@@ -583,23 +505,12 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
     // the two row counts, wave-uniform
     const int nefcA = __builtin_amdgcn_readlane(nefc, 0), nefcB = __builtin_amdgcn_readlane(nefc, 32);
     const int nconA = __builtin_amdgcn_readlane(ncon, 0), nconB = __builtin_amdgcn_readlane(ncon, 32);
-    {   // contact records: frame x = normal, t1 from (0,1,0) or (0,0,1) made orthogonal, t2 = n x t1 (mju_makeFrame)
+    {   // contact records (CONTACT_RECORD of fmj_narrow.inc)
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const int cslot = g_slot + k;
-        if (k < g_cnt && cslot < ncon) {
-          const v3 nrm = g_nq[k];
-          v3 t1 = (nrm.y < -0.5f || nrm.y > 0.5f) ? mk3(0.f, 0.f, 1.f) : mk3(0.f, 1.f, 0.f);
-          t1 = sub3(t1, scl3(nrm, dot3(t1, nrm)));
-          t1 = scl3(t1, 1.0f / sqrtf(dot3(t1, t1)));
-          const v3 t2 = cross(nrm, t1);
-          const v3 pos = sub3(g_cq[k], scl3(nrm, g_rad + 0.5f * g_dq[k]));
-          float* ct = CT + cslot * 16;
-          *(float4*)(ct) = make_float4(pos.x, pos.y, pos.z, nrm.x);
-          *(float4*)(ct + 4) = make_float4(nrm.y, nrm.z, t1.x, t1.y);
-          *(float4*)(ct + 8) = make_float4(t1.z, t2.x, t2.y, t2.z);
-          *(float4*)(ct + 12) = make_float4(g_dq[k], g_mu, __int_as_float(sl | ((GTABI(sl, 0).z + 1) << 16)), pp0.z);
-        }
+        if (k < g_cnt && cslot < ncon)
+          CONTACT_RECORD(cslot, g_nq[k], sub3(g_cq[k], scl3(nrm, g_rad + 0.5f * g_dq[k])), g_dq[k], g_mu, __int_as_float(sl | ((GTABI(sl, 0).z + 1) << 16)), pp0.z);
       }
     }
     WSYNC();
@@ -654,14 +565,7 @@ __global__ void __launch_bounds__(64, FMJ_C2_WPS) fmj_step_cons2_kernel(const De
           ROUND_BODY2(NG_); \
           p0 = np0; p1 = np1; p2 = np2; a0 = na0; a1 = na1; a2 = na2; dep = ndep; ro += (int)sizeof(DualRound); \
         }
-        if (MAXD >= 32) ROUNDS_AT((MAXD >= 32 ? 8 : 1), dep > 28)
-        if (MAXD >= 28) ROUNDS_AT((MAXD >= 28 ? 7 : 1), dep > 24)
-        if (MAXD >= 24) ROUNDS_AT((MAXD >= 24 ? 6 : 1), dep > 20)
-        if (MAXD >= 20) ROUNDS_AT((MAXD >= 20 ? 5 : 1), dep > 16)
-        if (MAXD >= 16) ROUNDS_AT((MAXD >= 16 ? 4 : 1), dep > 12)
-        if (MAXD >= 12) ROUNDS_AT((MAXD >= 12 ? 3 : 1), dep > 8)
-        if (MAXD >= 8) ROUNDS_AT((MAXD >= 8 ? 2 : 1), dep > 4)
-        ROUNDS_AT(1, dep >= 0)
+        DEPTH_LADDER(ROUNDS_AT, dep >= 0)
 #undef ROUNDS_AT
       }
 #undef ROUND_BODY2

@@ -107,27 +107,9 @@
         }
         float R, kimp, bb;
         row_params(sr0, sr1, si0, si1, si2, si3, si4, ep[0], ep[1], dapx, hstepc, &R, &kimp, &bb);
-        float y[MAXD];
-        {
-          const float* yr = YC + (isr ? e : 0) * RS;
-#pragma unroll
-          for (int g4 = 0; g4 < MAXD / 4; g4++) { const float4 v = *(const float4*)(yr + 4 * g4); y[4 * g4] = v.x; y[4 * g4 + 1] = v.y; y[4 * g4 + 2] = v.z; y[4 * g4 + 3] = v.w; }
-        }
-#define ANC4(tab_, dd_) ((int)((tab_[(dd_) >> 2] >> (8 * ((dd_) & 3))) & 0xffu))      /* 4 * dof: the byte offset into a float array */
-#define LDSF(base_, off4_) (*(const float*)((const char*)(base_) + (off4_)))
-        uint32_t atab[MAXD / 4];                                 // the chain's dof at each depth (ancl1: all dofs, the dof itself beyond its depth)
-        {
-          const unsigned crow = (unsigned)(chain < 0 ? 0 : chain) * (MAXD / 4);
-#pragma unroll
-          for (int g4 = 0; g4 < MAXD / 4; g4++) atab[g4] = gptr(M.ancl1)[crow + g4];
-        }
-        float vel = 0.f, jxs = 0.f, jqw = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < MAXD; dd++) {
-          const int o4 = ANC4(atab, dd);
-          const float j = y[dd];
-          vel = fmaf(j, LDSF(eQV, o4), vel); jxs = fmaf(j, LDSF(eXS, o4), jxs); jqw = fmaf(j, LDSF(eQW, o4), jqw);
-        }
+#define ROW_ENV(a_) e##a_
+#include "fmj_rows_chain.inc"      // y: the row of J by depth; ANC4, LDSF, atab: the chain's dof at each depth; vel, jxs, jqw
+#undef ROW_ENV
         const float aref = -bb * vel - kimp * (ep[0] - ep[1]);
         const float tl10 = eTS[0], tl20 = eTS[1], tl21 = eTS[2];
         const char* const HMb = (const char*)eHM - (size_t)T0 * RS * 4;      // rows of the lane dofs, addressed by dof
@@ -181,13 +163,11 @@
       float areg[64];
       float diag = 1.f;                                      // A_jj + R_j
       {
-        typedef float f16_t __attribute__((ext_vector_type(16)));
-        const int kh = lane >> 5, r32 = lane & 31;
-        const int nsteps = (nv + 1) >> 1;
-#define ZOP(YC_, CH_, DK_, K_) ({ const int ch_ = (CH_); const int lc_ = ch_ >= 0 && (K_) < nv ? (int)LCB[(K_) * nv + ch_] : -2; \
-                                   lc_ == (DK_) ? (YC_)[(DK_)] : 0.f; })
-#define SWAP32(x_, y_) { const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(x_), __float_as_uint(y_), false, false); \
-                         x_ = __uint_as_float(sw_[0]); y_ = __uint_as_float(sw_[1]); }
+#define MFMA_A_NEFC nefc_r
+#define MFMA_A_OPERANDS_ONLY CR_PAIR      // PAIR assembles one 32-row matrix per env in its own loop below
+#include "fmj_rows_mfma_a.inc"      // kh, r32, nsteps, ZOP, SWAP32; SOLO: areg = the lane's row of Z Z'
+#undef MFMA_A_NEFC
+#undef MFMA_A_OPERANDS_ONLY
 #if CR_PAIR
         const float* const ycA = lds + LL.SCR + r32 * RS;
         const float* const ycB = ycA + LL.rowsz;
@@ -211,42 +191,6 @@
         }
 #pragma unroll
         for (int f = 32; f < 64; f++) areg[f] = 0.f;
-#else
-        const float* const yc0 = rb + r32 * RS;
-        const float* const yc1 = yc0 + 32 * RS;
-        const int ch0 = r32 < nefc_r ? (int)CHN[r32] - 1 : -1;
-        const int ch1 = r32 + 32 < nefc_r ? (int)CHN[r32 + 32] - 1 : -1;
-        f16_t a00, a01, a10, a11;
-#pragma unroll
-        for (int v = 0; v < 16; v++) { a00[v] = 0.f; a01[v] = 0.f; a10[v] = 0.f; a11[v] = 0.f; }
-        if (nefc_r > 32) {
-          for (int t = 0; t < nsteps; t++) {
-            const int k = 2 * t + kh;
-            const int dk = k < nv ? (int)LCB[k * nv + k] : -1;
-            const float z0 = ZOP(yc0, ch0, dk, k), z1 = ZOP(yc1, ch1, dk, k);
-            a00 = __builtin_amdgcn_mfma_f32_32x32x2f32(z0, z0, a00, 0, 0, 0);      // rows (operand 1) x columns (operand 2): the lane keeps a column = a row of A
-            a01 = __builtin_amdgcn_mfma_f32_32x32x2f32(z0, z1, a01, 0, 0, 0);
-            a10 = __builtin_amdgcn_mfma_f32_32x32x2f32(z1, z0, a10, 0, 0, 0);
-            a11 = __builtin_amdgcn_mfma_f32_32x32x2f32(z1, z1, a11, 0, 0, 0);
-          }
-        } else {
-          for (int t = 0; t < nsteps; t++) {
-            const int k = 2 * t + kh;
-            const int dk = k < nv ? (int)LCB[k * nv + k] : -1;
-            const float z0 = ZOP(yc0, ch0, dk, k);
-            a00 = __builtin_amdgcn_mfma_f32_32x32x2f32(z0, z0, a00, 0, 0, 0);
-          }
-          // swapped with the zeros of a01: both halves of every column to lanes 0 .. 31, exact zeros to the lanes without rows
-        }
-#pragma unroll
-        for (int v = 0; v < 16; v++) {
-          float x_ = a00[v], y_ = a01[v];
-          SWAP32(x_, y_);
-          areg[8 * (v >> 2) + (v & 3)] = x_; areg[8 * (v >> 2) + 4 + (v & 3)] = y_;
-          float x1_ = a10[v], y1_ = a11[v];
-          SWAP32(x1_, y1_);
-          areg[32 + 8 * (v >> 2) + (v & 3)] = x1_; areg[32 + 8 * (v >> 2) + 4 + (v & 3)] = y1_;
-        }
 #endif
 #undef ZOP
 #undef SWAP32

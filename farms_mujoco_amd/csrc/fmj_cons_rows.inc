@@ -87,30 +87,9 @@
         }
         float R, kimp, bb;
         row_params(sr0, sr1, si0, si1, si2, si3, si4, ep[0], ep[1], dapx, h, &R, &kimp, &bb);
-        float y[MAXD];
-        {
-          const float* yr = YC + (isr ? e : 0) * RS;
-#pragma unroll
-          for (int g4 = 0; g4 < MAXD / 4; g4++) { const float4 v = *(const float4*)(yr + 4 * g4); y[4 * g4] = v.x; y[4 * g4 + 1] = v.y; y[4 * g4 + 2] = v.z; y[4 * g4 + 3] = v.w; }
-        }
-        // The chain's dof at each depth comes from the model's ancestor table (ancl1: byte = 4 * dof of the ancestor at that depth,
-        // the dof itself beyond its own depth), five words per row instead of a pointer chase of 19 dependent ds_bpermute.  Slots
-        // beyond the chain name the chain's last dof: J is zero there, so whatever finite value is read is multiplied by 0.
-#define ANC4(tab_, dd_) ((int)((tab_[(dd_) >> 2] >> (8 * ((dd_) & 3))) & 0xffu))      /* 4 * dof: the byte offset into a float array */
-#define LDSF(base_, off4_) (*(const float*)((const char*)(base_) + (off4_)))
-        uint32_t atab[MAXD / 4];
-        {
-          const unsigned crow = (unsigned)(chain < 0 ? 0 : chain) * (MAXD / 4);
-#pragma unroll
-          for (int g4 = 0; g4 < MAXD / 4; g4++) atab[g4] = gptr(M.ancl1)[crow + g4];
-        }
-        float vel = 0.f, jxs = 0.f, jqw = 0.f;
-#pragma unroll
-        for (int dd = 0; dd < MAXD; dd++) {
-          const int o4 = ANC4(atab, dd);
-          const float j = y[dd];
-          vel = fmaf(j, LDSF(QV, o4), vel); jxs = fmaf(j, LDSF(XS, o4), jxs); jqw = fmaf(j, LDSF(QW, o4), jqw);
-        }
+#define ROW_ENV(a_) a_
+#include "fmj_rows_chain.inc"      // y: the row of J by depth; ANC4, LDSF, atab: the chain's dof at each depth; vel, jxs, jqw
+#undef ROW_ENV
         // fork part of a pair row: the first body's chain beyond lcae, the depth of the deepest dof both chains share
         const int fchain = (haspx && isr && e >= e_p0) ? (int)CHF[e] - 1 : -1;
         const int lcae = (fchain >= 0 && chain >= 0) ? (int)LCB0[chain * nv + fchain] : -1;
@@ -245,54 +224,11 @@
         const int fchain = (haspx && isr && je >= e_p0) ? (int)CHF[je] - 1 : -1;
         float areg[FMJ_NA];
         {
-          // round 5: on the matrix cores, exactly as the two-env kernel's SOLO mode does it (fmj_cons2_rows.inc (7): same operands, same
-          // order of the sums - an env gets the same A from either kernel).  Every row of Z spread over the dofs (entry k = the row's entry at
-          // the depth of dof k if dof k lies on its chain, else 0) makes A = Z Z' a plain product: 32 x 32 x 2 fp32 MFMA steps over pairs of
-          // dofs, operand lane i = row i & 31 of the block of 32 rows, dof 2t + (i >> 5); the result leaves column j (= row j, A is symmetric)
-          // in lanes j and j + 32, half of its entries each, and v_permlane32_swap of two results puts both halves of the first into lanes
-          // 0 .. 31 and of the second into lanes 32 .. 63.
-          typedef float f16_t __attribute__((ext_vector_type(16)));
+          // on the matrix cores, by the text the two-env kernel's SOLO mode runs (fmj_cons2_rows.inc (7)): an env gets the same A from either kernel
           const int8_t* LCB = (const int8_t*)LC;
-          const int kh = lane >> 5, r32 = lane & 31;
-          const int nsteps = (nv + 1) >> 1;
-#define ZOP(YC_, CH_, DK_, K_) ({ const int ch_ = (CH_); const int lc_ = ch_ >= 0 && (K_) < nv ? (int)LCB[(K_) * nv + ch_] : -2; \
-                                   lc_ == (DK_) ? (YC_)[(DK_)] : 0.f; })
-#define SWAP32(x_, y_) { const auto sw_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(x_), __float_as_uint(y_), false, false); \
-                         x_ = __uint_as_float(sw_[0]); y_ = __uint_as_float(sw_[1]); }
-          const float* const yc0 = YC + r32 * RS;
-          const float* const yc1 = yc0 + 32 * RS;
-          const int ch0 = r32 < nefc ? (int)CHN[r32] - 1 : -1;
-          const int ch1 = r32 + 32 < nefc ? (int)CHN[r32 + 32] - 1 : -1;
-          f16_t a00, a01, a10, a11;
-#pragma unroll
-          for (int v = 0; v < 16; v++) { a00[v] = 0.f; a01[v] = 0.f; a10[v] = 0.f; a11[v] = 0.f; }
-          if (nefc > 32) {
-            for (int t = 0; t < nsteps; t++) {
-              const int k = 2 * t + kh;
-              const int dk = k < nv ? (int)LCB[k * nv + k] : -1;
-              const float z0 = ZOP(yc0, ch0, dk, k), z1 = ZOP(yc1, ch1, dk, k);
-              a00 = __builtin_amdgcn_mfma_f32_32x32x2f32(z0, z0, a00, 0, 0, 0);
-              a01 = __builtin_amdgcn_mfma_f32_32x32x2f32(z0, z1, a01, 0, 0, 0);
-              a10 = __builtin_amdgcn_mfma_f32_32x32x2f32(z1, z0, a10, 0, 0, 0);
-              a11 = __builtin_amdgcn_mfma_f32_32x32x2f32(z1, z1, a11, 0, 0, 0);
-            }
-          } else {
-            for (int t = 0; t < nsteps; t++) {
-              const int k = 2 * t + kh;
-              const int dk = k < nv ? (int)LCB[k * nv + k] : -1;
-              const float z0 = ZOP(yc0, ch0, dk, k);
-              a00 = __builtin_amdgcn_mfma_f32_32x32x2f32(z0, z0, a00, 0, 0, 0);
-            }
-          }
-#pragma unroll
-          for (int v = 0; v < 16; v++) {
-            float x_ = a00[v], y_ = a01[v];
-            SWAP32(x_, y_);
-            areg[8 * (v >> 2) + (v & 3)] = x_; areg[8 * (v >> 2) + 4 + (v & 3)] = y_;
-            float x1_ = a10[v], y1_ = a11[v];
-            SWAP32(x1_, y1_);
-            areg[32 + 8 * (v >> 2) + (v & 3)] = x1_; areg[32 + 8 * (v >> 2) + 4 + (v & 3)] = y1_;
-          }
+#define MFMA_A_NEFC nefc
+#include "fmj_rows_mfma_a.inc"      // areg = the lane's row of Z Z'
+#undef MFMA_A_NEFC
 #undef ZOP
 #undef SWAP32
           const float Rj = isr ? EP[je * 8 + 2] : 0.f;

@@ -618,6 +618,28 @@ typedef float f2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void pk_fnma(f2_t& acc, const f2_t tt, const f2_t v) {
   asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]" : "+v"(acc) : "v"(tt), "v"(v));
 }
+// The depth ladder of the factorisation drivers.  A pivot at depth d has entries in slots 0 .. d - 1 only and the rounds come deepest
+// level first, so a driver runs one loop per float4 group count, one after the other: RA_(NG, COND) is the driver's loop over rounds
+// that move NG groups, run while COND holds on the driver's `dep` (the current round's depth); LAST_ is the condition of the last
+// loop (one group).  MAXD is the driver's row length: the loops of longer rows fold away.
+#define DEPTH_LADDER(RA_, LAST_) \
+    if (MAXD >= 64) RA_((MAXD >= 64 ? 16 : 1), dep > 60) \
+    if (MAXD >= 60) RA_((MAXD >= 60 ? 15 : 1), dep > 56) \
+    if (MAXD >= 56) RA_((MAXD >= 56 ? 14 : 1), dep > 52) \
+    if (MAXD >= 52) RA_((MAXD >= 52 ? 13 : 1), dep > 48) \
+    if (MAXD >= 48) RA_((MAXD >= 48 ? 12 : 1), dep > 44) \
+    if (MAXD >= 44) RA_((MAXD >= 44 ? 11 : 1), dep > 40) \
+    if (MAXD >= 40) RA_((MAXD >= 40 ? 10 : 1), dep > 36) \
+    if (MAXD >= 36) RA_((MAXD >= 36 ? 9 : 1), dep > 32) \
+    if (MAXD >= 32) RA_((MAXD >= 32 ? 8 : 1), dep > 28) \
+    if (MAXD >= 28) RA_((MAXD >= 28 ? 7 : 1), dep > 24) \
+    if (MAXD >= 24) RA_((MAXD >= 24 ? 6 : 1), dep > 20) \
+    if (MAXD >= 20) RA_((MAXD >= 20 ? 5 : 1), dep > 16) \
+    if (MAXD >= 16) RA_((MAXD >= 16 ? 4 : 1), dep > 12) \
+    if (MAXD >= 12) RA_((MAXD >= 12 ? 3 : 1), dep > 8) \
+    if (MAXD >= 8) RA_((MAXD >= 8 ? 2 : 1), dep > 4) \
+    RA_(1, LAST_)
+
 template <int MAXD>
 __device__ __forceinline__ void ldl_factor(float* HR, float* DV, const WideRound* rounds, int nround, int maxdep, int lane, bool isd, int ddepth,
                                            f2_t (&r)[MAXD / 2], float diag, float& dinv_mine, float& x) {
@@ -667,22 +689,7 @@ __device__ __forceinline__ void ldl_factor(float* HR, float* DV, const WideRound
       ROUND_BODY(NG_); \
       p0 = np0; p1 = np1; p2 = np2; p3 = np3; p4 = np4; p5 = np5; a0 = na0; a1 = na1; a2 = na2; a3 = na3; a4 = na4; a5 = na5; dep = ndep; np = nnp; rd++; \
     }
-    if (MAXD >= 64) ROUNDS_AT((MAXD >= 64 ? 16 : 1), dep > 60)
-    if (MAXD >= 60) ROUNDS_AT((MAXD >= 60 ? 15 : 1), dep > 56)
-    if (MAXD >= 56) ROUNDS_AT((MAXD >= 56 ? 14 : 1), dep > 52)
-    if (MAXD >= 52) ROUNDS_AT((MAXD >= 52 ? 13 : 1), dep > 48)
-    if (MAXD >= 48) ROUNDS_AT((MAXD >= 48 ? 12 : 1), dep > 44)
-    if (MAXD >= 44) ROUNDS_AT((MAXD >= 44 ? 11 : 1), dep > 40)
-    if (MAXD >= 40) ROUNDS_AT((MAXD >= 40 ? 10 : 1), dep > 36)
-    if (MAXD >= 36) ROUNDS_AT((MAXD >= 36 ? 9 : 1), dep > 32)
-    if (MAXD >= 32) ROUNDS_AT((MAXD >= 32 ? 8 : 1), dep > 28)
-    if (MAXD >= 28) ROUNDS_AT((MAXD >= 28 ? 7 : 1), dep > 24)
-    if (MAXD >= 24) ROUNDS_AT((MAXD >= 24 ? 6 : 1), dep > 20)
-    if (MAXD >= 20) ROUNDS_AT((MAXD >= 20 ? 5 : 1), dep > 16)
-    if (MAXD >= 16) ROUNDS_AT((MAXD >= 16 ? 4 : 1), dep > 12)
-    if (MAXD >= 12) ROUNDS_AT((MAXD >= 12 ? 3 : 1), dep > 8)
-    if (MAXD >= 8) ROUNDS_AT((MAXD >= 8 ? 2 : 1), dep > 4)
-    ROUNDS_AT(1, true)
+    DEPTH_LADDER(ROUNDS_AT, true)
 #undef ROUNDS_AT
   }
 #undef ROUND_BODY
@@ -751,14 +758,7 @@ __device__ __forceinline__ void ldl_factor2(float* HM, float* HR, float* DVM, fl
       ROUND_BODY2(NG_); \
       p0 = np0; p1 = np1; p2 = np2; a0 = na0; a1 = na1; a2 = na2; dep = ndep; rd++; \
     }
-    if (MAXD >= 32) ROUNDS_AT((MAXD >= 32 ? 8 : 1), dep > 28)
-    if (MAXD >= 28) ROUNDS_AT((MAXD >= 28 ? 7 : 1), dep > 24)
-    if (MAXD >= 24) ROUNDS_AT((MAXD >= 24 ? 6 : 1), dep > 20)
-    if (MAXD >= 20) ROUNDS_AT((MAXD >= 20 ? 5 : 1), dep > 16)
-    if (MAXD >= 16) ROUNDS_AT((MAXD >= 16 ? 4 : 1), dep > 12)
-    if (MAXD >= 12) ROUNDS_AT((MAXD >= 12 ? 3 : 1), dep > 8)
-    if (MAXD >= 8) ROUNDS_AT((MAXD >= 8 ? 2 : 1), dep > 4)
-    ROUNDS_AT(1, true)
+    DEPTH_LADDER(ROUNDS_AT, true)
 #undef ROUNDS_AT
   }
 #undef ROUND_BODY2
@@ -878,114 +878,19 @@ __device__ __forceinline__ void row_params(float sr0, float sr1, float si0, floa
   *kimp = K * imp; *bb = B;
 }
 
-// ---- polytopes (box, cylinder, convex mesh) in explicit pairs: include/fmj.h (ABI 6), oracle poly_vertex / poly_signed / collide_pair
-__device__ __forceinline__ bool geom_is_round(int t) { return t == FMJ_GEOM_SPHERE || t == FMJ_GEOM_CAPSULE; }
-// vertex k of polytope (type, size row gs) in the geom frame
-template <class MT>
-__device__ __forceinline__ v3 poly_vertex(MT& M, int type, float4 gs, int k) {
-  if (type == FMJ_GEOM_BOX) return mk3((k & 1) ? gs.x : -gs.x, (k & 2) ? gs.y : -gs.y, (k & 4) ? gs.z : -gs.z);
-  if (type == FMJ_GEOM_CYLINDER) {          // 12 points on each rim in steps of 150 degrees, the first on +x; k < 12: the +z rim
-    float sn, cs;
-    sincospif((float)(((k % 12) * 5) % 12) * (1.0f / 6.0f), &sn, &cs);
-    return mk3(gs.x * cs, gs.x * sn, k < 12 ? gs.y : -gs.y);
-  }
-  const float4 v = ldg4(M.mesh_vert, (unsigned)(__float_as_int(gs.x) + k));
-  return mk3(v.x, v.y, v.z);
-}
-// signed distance of x (geom frame) to the polytope = max over its faces of (n . x - d), and that face's outward normal
-template <class MT>
-__device__ __forceinline__ float poly_signed(MT& M, int type, float4 gs, int face0, int nface, v3 x, v3* n) {
-  if (type == FMJ_GEOM_BOX) {
-    const float sx = fabsf(x.x) - gs.x, sy = fabsf(x.y) - gs.y, sz = fabsf(x.z) - gs.z;
-    float s = sx; *n = mk3(x.x < 0.f ? -1.f : 1.f, 0.f, 0.f);
-    if (sy > s) { s = sy; *n = mk3(0.f, x.y < 0.f ? -1.f : 1.f, 0.f); }
-    if (sz > s) { s = sz; *n = mk3(0.f, 0.f, x.z < 0.f ? -1.f : 1.f); }
-    return s;
-  }
-  if (type == FMJ_GEOM_CYLINDER) {
-    const float r = sqrtf(x.x * x.x + x.y * x.y);
-    float s = fabsf(x.z) - gs.y; *n = mk3(0.f, 0.f, x.z < 0.f ? -1.f : 1.f);
-    if (r - gs.x > s) { s = r - gs.x; *n = r > 1e-15f ? mk3(x.x / r, x.y / r, 0.f) : mk3(1.f, 0.f, 0.f); }
-    return s;
-  }
-  float s = -1e30f; *n = mk3(0.f, 0.f, 1.f);
-  for (int f = 0; f < nface; f++) {
-    const float4 pl = ldg4(M.mesh_face, (unsigned)(face0 + f));
-    const float sf = pl.x * x.x + pl.y * x.y + pl.z * x.z - pl.w;
-    if (sf > s) { s = sf; *n = mk3(pl.x, pl.y, pl.z); }
-  }
-  return s;
-}
-__device__ __forceinline__ float geom_rbound(int type, float4 gs) {
-  return type == FMJ_GEOM_SPHERE ? gs.x : type == FMJ_GEOM_CAPSULE ? gs.x + gs.y : type == FMJ_GEOM_CYLINDER ? sqrtf(gs.x * gs.x + gs.y * gs.y)
-       : type == FMJ_GEOM_BOX ? sqrtf(gs.x * gs.x + gs.y * gs.y + gs.z * gs.z) : gs.z;
-}
-// explicit pair (g1, g2) with at least one polytope: up to 4 contacts (position, normal from geom1 to geom2, distance), PO = body poses in LDS
-template <class MT>
-__device__ __forceinline__ int pair_polytope(MT& M, const float* PO, int g1, int g2, v3* cq, v3* nq, float* dq) {
-  int type[2], face0[2], nface[2], nvert[2]; float4 gs[2]; v3 pos[2]; q4 wq[2], wqc[2];
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const int g = k ? g2 : g1;
-    const int4 gi = GTABI(g, 0);
-    const float4 gp = GTAB(g, 2), gq = GTAB(g, 3);
-    gs[k] = GTAB(g, 1);
-    type[k] = gi.x; face0[k] = gi.w; nface[k] = __float_as_int(GTAB(g, 5).w);
-    nvert[k] = gi.x == FMJ_GEOM_BOX ? 8 : gi.x == FMJ_GEOM_CYLINDER ? 24 : gi.x == FMJ_GEOM_MESH ? __float_as_int(gs[k].y) : 0;
-    const float4 bp = *(const float4*)(PO + gi.y * 8), bq = *(const float4*)(PO + gi.y * 8 + 4);
-    const q4 bqq = {bq.x, bq.y, bq.z, bq.w}, gqq = {gq.x, gq.y, gq.z, gq.w};
-    wq[k] = qmul(bqq, gqq); wqc[k] = q4{wq[k].w, -wq[k].x, -wq[k].y, -wq[k].z};
-    pos[k] = add3(mk3(bp.x, bp.y, bp.z), qrot(bqq, mk3(gp.x, gp.y, gp.z)));
-  }
-  const v3 dc = sub3(pos[1], pos[0]);
-  if (sqrtf(dot3(dc, dc)) > geom_rbound(type[0], gs[0]) + geom_rbound(type[1], gs[1])) return 0;
-  const bool r0 = geom_is_round(type[0]), r1 = geom_is_round(type[1]);
-  int cnt = 0;
-  if (r0 != r1) {                              // polytope against sphere / capsule: the round geom's centres against the faces
-    const int rk = r0 ? 0 : 1, pk = 1 - rk;
-    const float rad = gs[rk].x, half = gs[rk].y;
-    const int ncen = type[rk] == FMJ_GEOM_CAPSULE ? 2 : 1;
-    const v3 ax = qrot(wq[rk], mk3(0.f, 0.f, 1.f));
-    for (int c = 0; c < ncen; c++) {
-      const float sgn = ncen == 2 ? (c == 0 ? 1.f : -1.f) : 0.f;
-      const v3 cw = add3(pos[rk], scl3(ax, sgn * half));
-      v3 nl;
-      const float dist = poly_signed(M, type[pk], gs[pk], face0[pk], nface[pk], qrot(wqc[pk], sub3(cw, pos[pk])), &nl) - rad;
-      if (dist < 0.f) {
-        const v3 nw = qrot(wq[pk], nl);
-        const v3 cp = sub3(cw, scl3(nw, rad + 0.5f * dist)), n12 = pk == 0 ? nw : scl3(nw, -1.f);
-#pragma unroll
-        for (int q = 0; q < 2; q++) if (cnt == q) { cq[q] = cp; nq[q] = n12; dq[q] = dist; }
-        cnt++;
-      }
+// Joint-limit activation (mj_instantiateLimit) of the lane's dof from row 3 of its dof table (flag, lower, upper, margin).
+// reads d_scalar, d_qadr, QP of the including kernel;  defines lim, dist_lo, dist_hi, act_lo, act_hi.  The ballots that number the
+// rows stay in the kernels: 64-bit in the one-env kernel, per half in the two-env kernel.
+#define JOINT_LIMIT_ACT(row_) \
+    const float4 lim = (row_); \
+    float dist_lo = 0.f, dist_hi = 0.f; bool act_lo = false, act_hi = false; \
+    if (d_scalar && lim.x != 0.f) { \
+      const float qj = QP[d_qadr]; \
+      dist_lo = qj - lim.y; dist_hi = lim.z - qj; \
+      act_lo = dist_lo < lim.w; act_hi = dist_hi < lim.w; \
     }
-    return cnt;
-  }
-  for (int side = 0; side < 2; side++) {       // side 0: geom1's vertices in geom2; side 1: geom2's vertices in geom1
-    const int va = side, fb = 1 - side;
-    for (int k = 0; k < nvert[va]; k++) {
-      const v3 vw = add3(pos[va], qrot(wq[va], poly_vertex(M, type[va], gs[va], k)));
-      v3 nl;
-      float td = poly_signed(M, type[fb], gs[fb], face0[fb], nface[fb], qrot(wqc[fb], sub3(vw, pos[fb])), &nl);
-      if (!(td < 0.f)) continue;
-      const v3 nw = qrot(wq[fb], nl);
-      v3 tc = sub3(vw, scl3(nw, 0.5f * td)), tn = fb == 0 ? nw : scl3(nw, -1.f);
-      bool have = true;                          // insertion by depth, ties keep the earlier candidate (the rule of mesh against ground)
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const bool empty = q >= cnt;
-        if (have && (empty || td < dq[q])) {
-          const float sd = dq[q]; const v3 sc = cq[q], sn = nq[q];
-          dq[q] = td; cq[q] = tc; nq[q] = tn;
-          td = sd; tc = sc; tn = sn;
-          have = !empty;
-        }
-      }
-      if (cnt < 4) cnt++;
-    }
-  }
-  return cnt;
-}
+
+#include "fmj_narrow.inc"      // collision helpers: polytopes of explicit pairs, ground_dist, CONTACT_RECORD
 
 // ---- elliptic cone on the dual side (mj_solPGS's block update, the noslip pass): oracle cone_zone / qcqp2 / pgs_elliptic_block in fp32
 // forces of one elliptic contact at the residuals jar = (normal, tangent 1, tangent 2): mj_constraintUpdate's three zones (the warm start)
@@ -1015,35 +920,6 @@ __device__ __forceinline__ bool qcqp2_dev(float a11, float a12, float a22, float
   }
   *x1 = v1 * d; *x2 = v2 * d;
   return la != 0.f;
-}
-
-// Height of world point p above ground entry pl along the local surface normal, and that normal.  Plane: n . p - offset.
-// Heightfield (MuJoCo hfield semantics: nrow x ncol samples over [-rx, rx] x [-ry, ry] of the geom frame, elevation = data *
-// size z): the plane of the grid triangle under p (cells split along the diagonal (c, r) - (c + 1, r + 1)); nothing outside
-// the grid.  PTAB(pl, 1).y != 0 marks a heightfield, PTAB(pl, 0) then holds its position, (pl, 2) its quaternion, (pl, 3)
-// rx, ry, size z.
-template <class MT>
-__device__ __forceinline__ float ground_dist(MT& M, int pl, float4 pn, float4 pp, v3 p, v3* n) {
-  if (pp.y == 0.f) { *n = mk3(pn.x, pn.y, pn.z); return dot3(p, *n) - pn.w; }
-  const float4 hq = PTAB(pl, 2), hs = PTAB(pl, 3);
-  const q4 q = {hq.x, hq.y, hq.z, hq.w}, qc = {hq.x, -hq.y, -hq.z, -hq.w};
-  const v3 pl_ = qrot(qc, sub3(p, mk3(pn.x, pn.y, pn.z)));
-  const int nc = M.hf_ncol, nr = M.hf_nrow;
-  const float sx = (float)(nc - 1) / (2.f * hs.x), sy = (float)(nr - 1) / (2.f * hs.y);
-  const float gx = (pl_.x + hs.x) * sx, gy = (pl_.y + hs.y) * sy;
-  *n = qrot(q, mk3(0.f, 0.f, 1.f));
-  if (!(gx >= 0.f && gx <= (float)(nc - 1) && gy >= 0.f && gy <= (float)(nr - 1))) return 1e30f;
-  const int c = min((int)gx, nc - 2), r = min((int)gy, nr - 2);
-  const float fx = gx - (float)c, fy = gy - (float)r;
-  const float AS1* D = gptr(M.hf_data) + (size_t)r * nc + c;
-  const float z00 = D[0] * hs.z, z10 = D[1] * hs.z, z01 = D[nc] * hs.z, z11 = D[nc + 1] * hs.z;
-  float zs, gxs, gys;                                          // surface height under p and its slopes per cell
-  if (fx >= fy) { gxs = z10 - z00; gys = z11 - z10; } else { gxs = z11 - z01; gys = z01 - z00; }
-  zs = z00 + gxs * fx + gys * fy;
-  const v3 nl = mk3(-gxs * sx, -gys * sy, 1.f);
-  const float inv = 1.0f / sqrtf(dot3(nl, nl));
-  *n = qrot(q, scl3(nl, inv));
-  return (pl_.z - zs) * inv;                                   // n_z (p_z - z_surface)
 }
 
 // One contact-sensor row (reference sensors.pyx:20-137,158-182): accumulate every contact whose keys hit `row`.
@@ -1426,13 +1302,7 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
       if (isd) { XS[lane] = xs; DI[lane] = dinv_m; SD[lane] = sqrtf(dinv_m); XV[lane] = dinv_h; }   // 1 / D of H waits in XV
       STAMP(12);  // factor M + qacc_smooth
       // (2) joint limit rows (mj_instantiateLimit): lane = dof, rows ordered by joint then side (-1, +1)
-      const float4 lim = DTAB(dlo, 3);
-      float dist_lo = 0.f, dist_hi = 0.f; bool act_lo = false, act_hi = false;
-      if (d_scalar && lim.x != 0.f) {
-        const float qj = QP[d_qadr];
-        dist_lo = qj - lim.y; dist_hi = lim.z - qj;
-        act_lo = dist_lo < lim.w; act_hi = dist_hi < lim.w;
-      }
+      JOINT_LIMIT_ACT(DTAB(dlo, 3));
       const unsigned long long m_lo = __ballot(act_lo), m_hi = __ballot(act_hi);
       const unsigned long long lt = (1ull << lane) - 1ull;
       const int e_lo = __popcll(m_lo & lt) + __popcll(m_hi & lt);
@@ -1446,92 +1316,18 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
         const float4 pn = PTAB(pl, 0), pp = PTAB(pl, 1);
         for (int g0 = 0; g0 < M.ngeom; g0 += 64) {
           const int g = g0 + lane;
-          // up to 4 contacts per geom: sphere 1, capsule 2 (segment ends), box the first 4 penetrating corners in
-          // corner order (what the oracle's collide_ground does), cylinder its rim points
           int cnt = 0; v3 cq[4], nq[4]; float dq[4]; float rad = 0.f, mu = 0.f;
 #pragma unroll
           for (int k = 0; k < 4; k++) { cq[k] = mk3(0.f, 0.f, 0.f); nq[k] = mk3(0.f, 0.f, 1.f); dq[k] = 0.f; }
-          if (g < M.ngeom) {
-            const int4 gi = GTABI(g, 0);
-            if (gi.x == FMJ_GEOM_SPHERE || gi.x == FMJ_GEOM_CAPSULE) {
-              const float4 gs = GTAB(g, 1), gp = GTAB(g, 2), gq = GTAB(g, 3);
-              const float4 bp = *(const float4*)(PO + gi.y * 8), bq = *(const float4*)(PO + gi.y * 8 + 4);
-              const q4 bqq = {bq.x, bq.y, bq.z, bq.w};
-              const v3 cen = add3(mk3(bp.x, bp.y, bp.z), qrot(bqq, mk3(gp.x, gp.y, gp.z)));
-              rad = gs.x; mu = fmaxf(fmaxf(pp.x, gs.w), 1e-5f);
-              v3 ax = mk3(0.f, 0.f, 0.f);
-              if (gi.x == FMJ_GEOM_CAPSULE) { const q4 gqq = {gq.x, gq.y, gq.z, gq.w}; ax = scl3(qrot(qmul(bqq, gqq), mk3(0.f, 0.f, 1.f)), gs.y); }
-              const v3 c0 = add3(cen, ax), c1 = sub3(cen, ax);
-              v3 n0, n1;
-              const float d0 = ground_dist(M, pl, pn, pp, c0, &n0) - rad;
-              const float d1 = ground_dist(M, pl, pn, pp, c1, &n1) - rad;
-              const bool a0 = d0 < 0.f, a1 = gi.x == FMJ_GEOM_CAPSULE && d1 < 0.f;
-              if (a0) { cq[0] = c0; dq[0] = d0; nq[0] = n0; cnt = 1; }
-              if (a1) { if (cnt == 0) { cq[0] = c1; dq[0] = d1; nq[0] = n1; } else { cq[1] = c1; dq[1] = d1; nq[1] = n1; } cnt++; }
-            }
-          }
-          if (M.any_box) {
-            const int4 gi = g < M.ngeom ? GTABI(g, 0) : make_int4(-1, 0, 0, 0);
-            if (gi.x == FMJ_GEOM_BOX) {
-              const float4 gs = GTAB(g, 1), gp = GTAB(g, 2), gq = GTAB(g, 3);
-              const float4 bp = *(const float4*)(PO + gi.y * 8), bq = *(const float4*)(PO + gi.y * 8 + 4);
-              const q4 bqq = {bq.x, bq.y, bq.z, bq.w}, gqq = {gq.x, gq.y, gq.z, gq.w};
-              const q4 wq = qmul(bqq, gqq);
-              const v3 cen = add3(mk3(bp.x, bp.y, bp.z), qrot(bqq, mk3(gp.x, gp.y, gp.z)));
-              const v3 ex = scl3(qrot(wq, mk3(1.f, 0.f, 0.f)), gs.x), ey = scl3(qrot(wq, mk3(0.f, 1.f, 0.f)), gs.y), ez = scl3(qrot(wq, mk3(0.f, 0.f, 1.f)), gs.z);
-              mu = fmaxf(fmaxf(pp.x, gs.w), 1e-5f);
-#pragma unroll
-              for (int corner = 0; corner < 8; corner++) {
-                const v3 c = add3(add3(cen, (corner & 1) ? ex : scl3(ex, -1.f)), add3((corner & 2) ? ey : scl3(ey, -1.f), (corner & 4) ? ez : scl3(ez, -1.f)));
-                v3 nc;
-                const float d = ground_dist(M, pl, pn, pp, c, &nc);
-                const bool pen = d < 0.f && cnt < 4;
-#pragma unroll
-                for (int k = 0; k < 4; k++) if (pen && cnt == k) { cq[k] = c; dq[k] = d; nq[k] = nc; }
-                cnt += pen ? 1 : 0;
-              }
-            }
-            if (gi.x == FMJ_GEOM_CYLINDER) {      // rim points (the oracle's collide_ground, MuJoCo's mjc_PlaneCylinder construction)
-              const float4 gs = GTAB(g, 1), gp = GTAB(g, 2), gq = GTAB(g, 3);
-              const float4 bp = *(const float4*)(PO + gi.y * 8), bq = *(const float4*)(PO + gi.y * 8 + 4);
-              const q4 bqq = {bq.x, bq.y, bq.z, bq.w}, gqq = {gq.x, gq.y, gq.z, gq.w};
-              const q4 wq = qmul(bqq, gqq);
-              const v3 cen = add3(mk3(bp.x, bp.y, bp.z), qrot(bqq, mk3(gp.x, gp.y, gp.z)));
-              v3 nrm_;                                         // a heightfield is taken as the plane under the cylinder's centre
-              const float dist = ground_dist(M, pl, pn, pp, cen, &nrm_);
-              v3 axis = qrot(wq, mk3(0.f, 0.f, 1.f));
-              float prjaxis = dot3(nrm_, axis);
-              if (prjaxis > 0.f) { axis = scl3(axis, -1.f); prjaxis = -prjaxis; }
-              v3 vec = sub3(scl3(axis, prjaxis), nrm_);
-              const float len2 = dot3(vec, vec);
-              if (len2 >= 1e-30f) vec = scl3(vec, gs.x / sqrtf(len2)); else vec = scl3(qrot(wq, mk3(1.f, 0.f, 0.f)), gs.x);
-              const float prjvec = dot3(vec, nrm_);
-              axis = scl3(axis, gs.y); prjaxis *= gs.y;
-              mu = fmaxf(fmaxf(pp.x, gs.w), 1e-5f);
-              const float d0 = dist + prjaxis + prjvec;
-              if (d0 < 0.f) {
-                cq[0] = add3(cen, add3(vec, axis)); dq[0] = d0; cnt = 1;
-                const float d1 = dist - prjaxis + prjvec;
-                if (d1 < 0.f) { cq[1] = add3(cen, sub3(vec, axis)); dq[1] = d1; cnt = 2; }
-                v3 vec1 = cross(vec, axis);
-                const float l1 = sqrtf(dot3(vec1, vec1));
-                if (l1 > 1e-15f) vec1 = scl3(vec1, gs.x * 0.8660254037844386f / l1);
-                const float prjvec1 = dot3(vec1, nrm_);
-#pragma unroll
-                for (int sg = 0; sg < 2; sg++) {
-                  const float sgn = sg ? -1.f : 1.f;
-                  const float d2 = dist + prjaxis - 0.5f * prjvec + sgn * prjvec1;
-                  const v3 c2 = add3(cen, add3(scl3(vec1, sgn), sub3(axis, scl3(vec, 0.5f))));
-                  const bool pen = d2 < 0.f;
-#pragma unroll
-                  for (int k = 1; k < 4; k++) if (pen && cnt == k) { cq[k] = c2; dq[k] = d2; }
-                  cnt += pen ? 1 : 0;
-                }
-              }
-#pragma unroll
-              for (int k = 0; k < 4; k++) nq[k] = nrm_;
-            }
-          }
+#define NP_CQ cq
+#define NP_NQ nq
+#define NP_DQ dq
+#define NP_PL pl
+#include "fmj_narrow_ground.inc"      // sphere / capsule, box, cylinder: cnt, rad, mu and the first cnt entries of cq / nq / dq
+#undef NP_CQ
+#undef NP_NQ
+#undef NP_DQ
+#undef NP_PL
           if (MESH && M.any_mesh) {      // convex mesh: its deepest penetrating vertices, deepest first (include/fmj.h)
             const int4 gi = g < M.ngeom ? GTABI(g, 0) : make_int4(-1, 0, 0, 0);
             if (gi.x == FMJ_GEOM_MESH) {
@@ -1575,19 +1371,8 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
           for (int k = 0; k < 4; k++) {
             const int slot = s0 + k;
             if (k < cnt && slot < M.max_contacts) {
-              // frame: x = normal, t1 from (0,1,0) or (0,0,1) made orthogonal, t2 = n x t1 (mju_makeFrame)
-              const v3 nrm = nq[k];
-              v3 t1 = (nrm.y < -0.5f || nrm.y > 0.5f) ? mk3(0.f, 0.f, 1.f) : mk3(0.f, 1.f, 0.f);
-              t1 = sub3(t1, scl3(nrm, dot3(t1, nrm)));
-              t1 = scl3(t1, 1.0f / sqrtf(dot3(t1, t1)));
-              const v3 t2 = cross(nrm, t1);
-              const v3 pos = sub3(cq[k], scl3(nrm, rad + 0.5f * dq[k]));
-              float* ct = CT + slot * 16;
-              *(float4*)(ct) = make_float4(pos.x, pos.y, pos.z, nrm.x);
-              *(float4*)(ct + 4) = make_float4(nrm.y, nrm.z, t1.x, t1.y);
-              *(float4*)(ct + 8) = make_float4(t1.z, t2.x, t2.y, t2.z);
               // geom | (last dof of its body's chain + 1) << 16: the Jacobian rows need the chain without a table read per contact
-              *(float4*)(ct + 12) = make_float4(dq[k], mu, __int_as_float(g | ((GTABI(g, 0).z + 1) << 16)), pp.z);
+              CONTACT_RECORD(slot, nq[k], sub3(cq[k], scl3(nrm, rad + 0.5f * dq[k])), dq[k], mu, __int_as_float(g | ((GTABI(g, 0).z + 1) << 16)), pp.z);
             }
           }
         }
@@ -1646,18 +1431,8 @@ __global__ void __launch_bounds__(64, (CONS || MAXD > 32) ? 2 : 4) fmj_step_kern
 #pragma unroll
           for (int k = 0; k < 4; k++) {
             const int slot = s0 + k;
-            if (k < pcnt && slot < M.max_contacts) {
-              const v3 nrm = pnq[k], pos = pcq[k];
-              v3 t1 = (nrm.y < -0.5f || nrm.y > 0.5f) ? mk3(0.f, 0.f, 1.f) : mk3(0.f, 1.f, 0.f);
-              t1 = sub3(t1, scl3(nrm, dot3(t1, nrm)));
-              t1 = scl3(t1, 1.0f / sqrtf(dot3(t1, t1)));
-              const v3 t2 = cross(nrm, t1);
-              float* ct = CT + slot * 16;
-              *(float4*)(ct) = make_float4(pos.x, pos.y, pos.z, nrm.x);
-              *(float4*)(ct + 4) = make_float4(nrm.y, nrm.z, t1.x, t1.y);
-              *(float4*)(ct + 8) = make_float4(t1.z, t2.x, t2.y, t2.z);
-              *(float4*)(ct + 12) = make_float4(pdq[k], mu, __int_as_float(g2 | ((GTABI(g2, 0).z + 1) << 16)), __int_as_float(g1 | ((pr + 1) << 16)));
-            }
+            if (k < pcnt && slot < M.max_contacts)
+              CONTACT_RECORD(slot, pnq[k], pcq[k], pdq[k], mu, __int_as_float(g2 | ((GTABI(g2, 0).z + 1) << 16)), __int_as_float(g1 | ((pr + 1) << 16)));
           }
         }
       }
@@ -1755,6 +1530,9 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 //   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc      the other step kernels
 //   fmj_stage_{carry_in,step_head,k,c,v,f,q,m,dbg_h,euler_check,euler_commit,euler_root}.inc      stages shared by fmj_step_kernel and fmj_step_wide_kernel
 //   fmj_stage2_{k,c,v,f,s}.inc                 stages shared by fmj_step_dual2_kernel and fmj_step_cons2_kernel
+//   fmj_narrow.inc                             collision helpers (device functions, CONTACT_RECORD), included once ahead of the kernels
+//   fmj_narrow_ground.inc                      one geom against one ground entry, shared by fmj_step_kernel and fmj_step_cons2_kernel
+//   fmj_rows_{chain,mfma_a}.inc                a row's chain and A = Z Z' on the matrix cores, shared by fmj_cons_rows.inc and fmj_cons2_rows.inc
 // scripts/device_listing.sh prints one digest of the device assembly per translation unit: a refactor keeps all of them.
 
 #define FMJ_CAT2(a, b) a##b

@@ -88,22 +88,7 @@ __device__ __forceinline__ void ldl_factor_wg(float* HR, float* DV, float* XW, c
       ROUND_BODY_W(NG_); \
       p0 = np0; p1 = np1; p2 = np2; p3 = np3; p4 = np4; p5 = np5; a0 = na0; a1 = na1; a2 = na2; a3 = na3; a4 = na4; a5 = na5; dep = ndep; np = nnp; rd++; \
     }
-    if (MAXD >= 64) ROUNDS_AT_W((MAXD >= 64 ? 16 : 1), dep > 60)
-    if (MAXD >= 60) ROUNDS_AT_W((MAXD >= 60 ? 15 : 1), dep > 56)
-    if (MAXD >= 56) ROUNDS_AT_W((MAXD >= 56 ? 14 : 1), dep > 52)
-    if (MAXD >= 52) ROUNDS_AT_W((MAXD >= 52 ? 13 : 1), dep > 48)
-    if (MAXD >= 48) ROUNDS_AT_W((MAXD >= 48 ? 12 : 1), dep > 44)
-    if (MAXD >= 44) ROUNDS_AT_W((MAXD >= 44 ? 11 : 1), dep > 40)
-    if (MAXD >= 40) ROUNDS_AT_W((MAXD >= 40 ? 10 : 1), dep > 36)
-    if (MAXD >= 36) ROUNDS_AT_W((MAXD >= 36 ? 9 : 1), dep > 32)
-    if (MAXD >= 32) ROUNDS_AT_W((MAXD >= 32 ? 8 : 1), dep > 28)
-    if (MAXD >= 28) ROUNDS_AT_W((MAXD >= 28 ? 7 : 1), dep > 24)
-    if (MAXD >= 24) ROUNDS_AT_W((MAXD >= 24 ? 6 : 1), dep > 20)
-    if (MAXD >= 20) ROUNDS_AT_W((MAXD >= 20 ? 5 : 1), dep > 16)
-    if (MAXD >= 16) ROUNDS_AT_W((MAXD >= 16 ? 4 : 1), dep > 12)
-    if (MAXD >= 12) ROUNDS_AT_W((MAXD >= 12 ? 3 : 1), dep > 8)
-    if (MAXD >= 8) ROUNDS_AT_W((MAXD >= 8 ? 2 : 1), dep > 4)
-    ROUNDS_AT_W(1, true)
+    DEPTH_LADDER(ROUNDS_AT_W, true)
 #undef ROUNDS_AT_W
   }
 #undef ROUND_BODY_W
