@@ -141,10 +141,32 @@ __device__ __forceinline__ bool drag_same_frames2(v3 com_pos, q4 q_wxyz, v3 lin_
 // load through the laundered argument pointer plus a compare and a branch inside each step (the rows_ahead tests alone were 0.8 % of
 // the headline, round 5), and the tail pass and the xfrc_applied hand-over of rows_ahead are not compiled.  The arithmetic is the
 // generic build's: the two are bitwise equal on the same launch (tests/test_gpu_dual2_lean.py).
+// Issue priority of the fused builds (DESIGN.md section 2, "The two waves of a SIMD": measurements and candidates).  The waves of a
+// headline launch are all resident from its first cycle and run the same step loop; at equal priority a SIMD's VALU issue goes to its
+// older wave, which finishes early and leaves the younger one to run the tail of the launch alone.  FMJ_DUAL_PRIO_POLICY decides, at
+// compile time, what a launch with StepArgs::dual_prio set does about it: 0 nothing; P > 0 (a power of two) the waves of a SIMD swap
+// s_setprio 1 / 0 every P steps, told apart by the parity of their wave slot.  Scheduling only: no arithmetic is involved, and
+// FMJ_DUAL_PRIO=0 at fmj_create (dual_prio = 0) gives the same bits.
+// FMJ_DUAL_PRIO_MAX_WPS: the register tiers (waves per SIMD) whose builds carry the policy.  Two waves sit in slots 0 and 1; with
+// three, two share a parity and take turns against the third, which still pays (measured at 6144 envs).  The 128-register builds
+// (WPS = 4) have no scalar to spare (DESIGN.md section 2).
+#ifndef FMJ_DUAL_PRIO_POLICY
+#define FMJ_DUAL_PRIO_POLICY 1
+#endif
+#ifndef FMJ_DUAL_PRIO_MAX_WPS
+#define FMJ_DUAL_PRIO_MAX_WPS 3
+#endif
+static_assert(FMJ_DUAL_PRIO_POLICY >= 0 && (FMJ_DUAL_PRIO_POLICY & (FMJ_DUAL_PRIO_POLICY - 1)) == 0, "priority policy: 0 or a power of two");
+#define FMJ_HWREG_WAVE_SLOT (4 | (0 << 6) | (3 << 11))      // s_getreg operand: HW_REG_HW_ID, bits 3:0 = the wave's slot on its SIMD
+#define FMJ_HWREG_HW_ID (4 | (0 << 6) | (31 << 11))         // the whole register: slot, SIMD, pipe, CU, SH, SE, ...
+#define FMJ_HWREG_XCC_ID (20 | (0 << 6) | (31 << 11))       // HW_REG_XCC_ID: bits 3:0 = the XCC
 template <bool FUSED, int MAXD, int WPS, bool SUBS = false, bool LEAN = false>
 __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel M_by_value, const StepArgs A_by_value) {
   static_assert(!LEAN || (FUSED && !SUBS), "the lean build is a fused launch without the rare options");
   extern __shared__ __align__(16) float lds[];
+#ifdef FMJ_STAMPS
+  const unsigned long long life_t0 = __builtin_amdgcn_s_memtime();      // the wave's entry (scripts/wave_lifetimes.py)
+#endif
   // the two arguments, addressed in the kernarg segment instead of being held in SGPRs
   const char AS4* const karg = (const char AS4*)__builtin_amdgcn_kernarg_segment_ptr();
   const DevModel AS4* Mp = (const DevModel AS4*)karg;
@@ -345,6 +367,10 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
   unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
 #endif
   const int n_steps = A.n_steps;
+  // the priority switch and the slot parity in one loop-carried scalar: 0 = leave priorities alone, else 2 | parity
+  constexpr int PRIO = (FUSED && WPS <= FMJ_DUAL_PRIO_MAX_WPS) ? FMJ_DUAL_PRIO_POLICY : 0, PRIO_P = PRIO > 0 ? PRIO : 1;
+  int prio_sw = 0;
+  if (PRIO != 0 && A.dual_prio) prio_sw = 2 | (int)(__builtin_amdgcn_s_getreg(FMJ_HWREG_WAVE_SLOT) & 1u);
   int ring = FUSED ? it0 % A.buffer_size : 0;      // ring index of the current iteration, advanced by wrap-around (no division per step)
   // what a lane carries across the steps: its index, (depth, subtree size, body, joint row) packed in one register, the
   // resident actuator slot (11), the drag on its body (6), the carried motor torque, the warning bits, the step count
@@ -367,6 +393,10 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
 #pragma unroll 1
   for (int step = 0; step < n_loop; step++) {
     if (__all(frozen)) break;
+    if (PRIO > 0 && prio_sw && (step & (PRIO_P - 1)) == 0) {      // (uniform) the waves of a SIMD swap priority every PRIO_P steps
+      if (((step / PRIO_P) ^ prio_sw) & 1) __builtin_amdgcn_s_setprio(1);
+      else __builtin_amdgcn_s_setprio(0);
+    }
     asm volatile("" : "+s"(Ap));                 // arguments are re-read inside the step, never carried across it
     asm volatile("" : "+s"(Mp));
     // per-lane indices, masks and LDS addresses are recomputed inside every step: hoisted out of the loop they would be
@@ -829,6 +859,15 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
   if (env == 0 && lane == 0 && A.qacc) {     // stamp i = time up to marker i: 1 joints row, 2 K, 3 C, 4 V, 5 F, 0 row + drag, 6 S, 7 Q, 8 M, 9 L, 10 X, 11 Euler
 #pragma unroll
     for (int i = 0; i < NSTAMP; i++) gptr(A.qacc)[i] = stamp_acc[i];
+  }
+  // this wave's entry and exit times and its placement, as raw words over the last six qacc slots of each of its envs (after the
+  // qacc values other lanes stored there, in program order).  With nv - 6 < NSTAMP they also replace the tail of env 0's phase stamps:
+  // scripts/stamps.py then reads slots >= nv - 6 of env 0 wrong (the eel, nv = 26)
+  if (sl == 0 && exists && A.qacc && nv >= 6) {
+    const unsigned long long life_t1 = __builtin_amdgcn_s_memtime();
+    unsigned AS1* const w = (unsigned AS1*)(gptr(A.qacc) + (size_t)env * nv + nv - 6);
+    w[0] = (unsigned)life_t0; w[1] = (unsigned)(life_t0 >> 32); w[2] = (unsigned)life_t1; w[3] = (unsigned)(life_t1 >> 32);
+    w[4] = __builtin_amdgcn_s_getreg(FMJ_HWREG_HW_ID); w[5] = __builtin_amdgcn_s_getreg(FMJ_HWREG_XCC_ID);
   }
 #endif
 #undef HALF_ANY

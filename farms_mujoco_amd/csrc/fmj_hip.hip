@@ -25,6 +25,7 @@
 
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -188,6 +189,7 @@ struct StepArgs {
   // water / units
   float surface, viscosity, wvx, wvy, wvz, wgravity; int use_buoyancy;
   float inv_meters, inv_velocity, inv_angvel, inv_torques, newtons, torques;
+  int dual_prio;              // two-env step kernel, fused: 1 = the waves of a SIMD take turns at issue priority (fmj_dual2.inc; in the 4-byte hole in front of w_amp)
   // wave controller
   const float* w_amp; const float* w_lag; const float* w_env; float w_freq;
   // per-env wave parameters (fmj_fused_ext): the env's own frequency [n_envs] or NULL; element stride between the envs' rows of w_amp / w_lag (0: one shared row)
@@ -200,6 +202,7 @@ struct StepArgs {
 };
 
 static_assert(alignof(DevModel) == 8 && alignof(StepArgs) == 8, "kernarg layout of (DevModel, StepArgs)");
+static_assert(offsetof(StepArgs, w_amp) == offsetof(StepArgs, dual_prio) + 4, "dual_prio fills padding: the kernarg layout of every other kernel is unchanged");
 #define FMJ_KARG_A_OFF ((sizeof(DevModel) + 7) & ~(size_t)7)
 
 // The step-kernel instantiations of one row length (fmj_tu_kernel_<rs>): the one-env kernel by what its constraint code covers
@@ -230,6 +233,7 @@ struct fmj_ctx {
   StepVariant variant = SV_PLAIN;        // of the one-env kernel
   int dual_wps = 4;           // waves per SIMD the dual2 build is registered for: 2, 3 or 4, the most the batch fills (FMJ_WPS overrides)
   int dual_lean = 1;          // fused launches of the flagship shape run the LEAN dual2 build (FMJ_DUAL_LEAN=0: always the generic one)
+  int dual_prio = 1;          // fused dual2 launches let the waves of a SIMD take turns at issue priority (FMJ_DUAL_PRIO=0: priorities left alone)
   int dual_last = FMJ_DUAL_BUILD_NONE;      // FMJ_DUAL_BUILD_* of the last dual2 launch (fmj_dual_build_info)
   size_t lds_bytes = 0, lds_bytes_dual2 = 0, lds_bytes_cons2 = 0, lds_bytes_wide = 0;
   int* d_resume = nullptr;    // [n_envs] hand-over of the two-env constraint kernel to the one-env kernel
@@ -1872,7 +1876,9 @@ static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream) 
     const bool lean = c->dual_lean && fused && !rare && !A.rows_ahead && A.controller == 1 && A.do_readout && A.do_drag && !A.disable_actuation &&
                       !D.any_stiffness && !A.xfrc_applied_out && !A.w_freq_env && !A.w_amp_stride && !A.w_lag_stride;      // per-env wave fields: the generic builds
     c->dual_last = lean ? FMJ_DUAL_BUILD_LEAN : (rare ? FMJ_DUAL_BUILD_RARE : FMJ_DUAL_BUILD_GENERIC);
-    return launch("dual step kernel", step_kernel(D.rs, fused, dual[lean ? 2 : rare][c->dual_wps - 2]), pairs, 64, c->lds_bytes_dual2, stream, D, A);
+    StepArgs A2 = A;
+    A2.dual_prio = fused ? c->dual_prio : 0;
+    return launch("dual step kernel", step_kernel(D.rs, fused, dual[lean ? 2 : rare][c->dual_wps - 2]), pairs, 64, c->lds_bytes_dual2, stream, D, A2);
   }
   if (D.cons && (!A.qacc_warmstart || !A.contact || !A.ncon))
     return set_err(FMJ_ERR_ARG, "fmj_data: qacc_warmstart, contact and ncon are required for models with limits / contacts");
@@ -2471,6 +2477,8 @@ static int choose_path(fmj_ctx* c, const ModelFacts& F) {
     if (w && (w[0] == '2' || w[0] == '3' || w[0] == '4')) c->dual_wps = w[0] - '0';
     const char* l = getenv("FMJ_DUAL_LEAN");      // 0: every launch runs the generic build (tests and A/B runs compare the two)
     if (l && l[0] == '0') c->dual_lean = 0;
+    const char* p = getenv("FMJ_DUAL_PRIO");      // 0: no s_setprio in any launch (tests and A/B runs compare the two)
+    if (p && p[0] == '0') c->dual_prio = 0;
   }
   c->path = F.wide ? PATH_TWO_WAVE : D.dual_ok ? PATH_TWO_ENV : D.cons2_ok ? PATH_CONS2_ONE_ENV : PATH_ONE_ENV;
   c->variant = one_env_variant(D);
@@ -2613,12 +2621,13 @@ int fmj_kernel_info(const fmj_ctx* c, int32_t* lds_bytes_per_env, int32_t* threa
   return FMJ_OK;
 }
 
-int fmj_dual_build_info(const fmj_ctx* c, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch) {
+int fmj_dual_build_info(const fmj_ctx* c, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch, int32_t* prio_enabled) {
   if (!c) return set_err(FMJ_ERR_ARG, "fmj_dual_build_info: NULL ctx");
   const bool dual = c->path == PATH_TWO_ENV;
   if (waves_per_simd) *waves_per_simd = dual ? c->dual_wps : 0;
   if (lean_enabled) *lean_enabled = dual ? c->dual_lean : 0;
   if (last_launch) *last_launch = c->dual_last;
+  if (prio_enabled) *prio_enabled = (dual && c->dual_wps <= FMJ_DUAL_PRIO_MAX_WPS && FMJ_DUAL_PRIO_POLICY != 0) ? c->dual_prio : 0;      // what the context's builds really run
   return FMJ_OK;
 }
 

@@ -246,10 +246,11 @@ class BatchedPhysics:
         info = dict(lds_bytes_per_env=lds.value, threads_per_env=thr.value)
         if hasattr(self._lib, 'fmj_dual_build_info') and self._lib.fmj_dual_build_info.argtypes:     # absent only from an A/B base build (FMJ_SO)
             # the two-env step kernel's build (include/fmj.h: fmj_dual_build_info): register tier, whether fused launches of the
-            # flagship shape run the lean build, and what the last step launch ran
-            wps, lean, last = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-            _lib.check(self._lib.fmj_dual_build_info(self._ctx, ctypes.byref(wps), ctypes.byref(lean), ctypes.byref(last)))
+            # flagship shape run the lean build, what the last step launch ran, and whether fused launches alternate the issue
+            # priority of the waves of a SIMD (an A/B base build from before that argument leaves it at 0)
+            wps, lean, last, prio = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+            _lib.check(self._lib.fmj_dual_build_info(self._ctx, ctypes.byref(wps), ctypes.byref(lean), ctypes.byref(last), ctypes.byref(prio)))
             if wps.value:
                 info.update(dual_wps=wps.value, dual_build='lean' if lean.value else 'generic',
-                            dual_last_launch=(None, 'generic', 'rare', 'lean')[last.value])
+                            dual_last_launch=(None, 'generic', 'rare', 'lean')[last.value], dual_prio=bool(prio.value))
         return info

@@ -324,9 +324,13 @@ int fmj_kernel_info(const fmj_ctx* ctx, int32_t* lds_bytes_per_env, int32_t* thr
  * tier, 2, 3 or 4 (chosen from the batch size at fmj_create; FMJ_WPS=2|3|4 overrides).  *lean_enabled: 1 when fmj_step_fused launches of
  * the shape of a fused run - wave controller, readout and drag on, substeps = 1, no rows_ahead, no joint stiffness, Euler - run the
  * build with those options folded in at compile time (bitwise the same results; FMJ_DUAL_LEAN=0 in the environment at fmj_create turns
- * it off, for comparisons).  *last_launch: the FMJ_DUAL_BUILD_* the last step launch of the context ran.  Any pointer may be NULL. */
+ * it off, for comparisons).  *last_launch: the FMJ_DUAL_BUILD_* the last step launch of the context ran.  *prio_enabled (appended; the
+ * parameters in front of it are as before): 1 when the fused launches of the kernel let the waves that share a SIMD take turns at
+ * issue priority (s_setprio; scheduling only, bitwise the same results; FMJ_DUAL_PRIO=0 in the environment at fmj_create turns it off); 0 for a
+ * register tier whose builds do not carry the policy (today waves_per_simd = 4).
+ * Any pointer may be NULL. */
 enum { FMJ_DUAL_BUILD_NONE = 0, FMJ_DUAL_BUILD_GENERIC = 1, FMJ_DUAL_BUILD_RARE = 2, FMJ_DUAL_BUILD_LEAN = 3 };
-int fmj_dual_build_info(const fmj_ctx* ctx, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch);
+int fmj_dual_build_info(const fmj_ctx* ctx, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch, int32_t* prio_enabled);
 
 /* ---- swimming links (SwimmingHandler.__init__, reference drag.pyx:333-387) ------------------
  * n_xfrc_rows: rows per env of the xfrc array (len(data.sensors.xfrc.names); the env stride of every xfrc row
