@@ -101,7 +101,7 @@ SYMBOLS = {
     'fmj_abi_version': (ctypes.c_int, []),
     'fmj_get_sensor_layout': (ctypes.c_int, [_VP, ctypes.POINTER(CSensorLayout)]),
     'fmj_kernel_info': (ctypes.c_int, [_VP, _I, _I]),
-    'fmj_dual_build_info': (ctypes.c_int, [_VP, _I, _I, _I, _I]),
+    'fmj_dual_build_info': (ctypes.c_int, [_VP, _I, _I, _I, _I, _I]),
     'fmj_set_swimming': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, _I, _I, _I, _D, _D, _D, _D]),
     'fmj_set_actuator_forcerange': (ctypes.c_int, [_VP, ctypes.c_int32, _I, _D]),
     'fmj_drag_link': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _VP, ctypes.c_int64, _VP, ctypes.c_int64, _D,

@@ -145,8 +145,9 @@ __device__ __forceinline__ bool drag_same_frames2(v3 com_pos, q4 q_wxyz, v3 lin_
 // headline launch are all resident from its first cycle and run the same step loop; at equal priority a SIMD's VALU issue goes to its
 // older wave, which finishes early and leaves the younger one to run the tail of the launch alone.  FMJ_DUAL_PRIO_POLICY decides, at
 // compile time, what a launch with StepArgs::dual_prio set does about it: 0 nothing; P > 0 (a power of two) the waves of a SIMD swap
-// s_setprio 1 / 0 every P steps, told apart by the parity of their wave slot.  Scheduling only: no arithmetic is involved, and
-// FMJ_DUAL_PRIO=0 at fmj_create (dual_prio = 0) gives the same bits.
+// s_setprio 1 / 0 every P steps, told apart by the parity of their wave slot; FMJ_DUAL_PRIO_PHASE (below) adds what they do inside
+// a step.  Scheduling only: no arithmetic is involved, and FMJ_DUAL_PRIO=0 at fmj_create (dual_prio = 0) executes no s_setprio
+// and gives the same bits.
 // FMJ_DUAL_PRIO_MAX_WPS: the register tiers (waves per SIMD) whose builds carry the policy.  Two waves sit in slots 0 and 1; with
 // three, two share a parity and take turns against the third, which still pays (measured at 6144 envs).  The 128-register builds
 // (WPS = 4) have no scalar to spare (DESIGN.md section 2).
@@ -157,6 +158,54 @@ __device__ __forceinline__ bool drag_same_frames2(v3 com_pos, q4 q_wxyz, v3 lin_
 #define FMJ_DUAL_PRIO_MAX_WPS 3
 #endif
 static_assert(FMJ_DUAL_PRIO_POLICY >= 0 && (FMJ_DUAL_PRIO_POLICY & (FMJ_DUAL_PRIO_POLICY - 1)) == 0, "priority policy: 0 or a power of two");
+// FMJ_DUAL_PRIO_PHASE: what s_setprio a wave executes at which point INSIDE a step (DESIGN.md section 2, "Issue priority by phase").
+// A step is not uniform: L and X are chains of dependent LDS round trips with little VALU between them, S and M dense VALU streams.
+// The switch points are phase boundaries of the step loop (the STAMP sites); a policy is one row of levels per point, first for the
+// wave whose turn the step is (((step / P) ^ slot) & 1, the "winner"), then for the other one, -1 = no instruction there:
+//   1 (A) alternate at the top of the step, nothing inside it (round 8)
+//   2 (B) alternate at the top; both waves at 2 from L's entry to the end of X, then back to the step's level
+//   3 (C) no alternation: 1 at the top, 0 from S's entry, 2 from L's entry to the end of X
+//   4 (D) alternate at the top; the step's winner gives way (0) from S's entry to L's entry
+//   5 (E) alternate at the top and flip again at L's entry
+//   6 (F) B, and both waves at 2 inside V (its pointer-jumping rounds) as well
+//   7 (G) B with the turn kept inside L ... X: the step's winner at 3, the other wave at 2
+//   8 (H) B without the way back: both waves stay at 2 through Euler, until the top of the next step
+// Every point is a uniform scalar branch on prio_sw and the step's parity around literal s_setprio, as the top of the step is.
+// H is the default: the best of the eight in a same-box A/B against A (+ 3.5 %; B + 1.9, C + 0.9, G + 1.1, F - 0.5, E - 1.4,
+// D - 3.1 %); the others stay for measurements (-DFMJ_DUAL_PRIO_PHASE=<id>, scripts/build_variant.sh).  With 1 the generated code
+// is round 8's, instruction for instruction.
+#ifndef FMJ_DUAL_PRIO_PHASE
+#define FMJ_DUAL_PRIO_PHASE 8
+#endif
+enum { FMJ_PRIO_TOP = 0, FMJ_PRIO_V = 1, FMJ_PRIO_VEND = 2, FMJ_PRIO_S = 3, FMJ_PRIO_L = 4, FMJ_PRIO_XEND = 5, FMJ_PRIO_NPOINTS = 6 };
+#if FMJ_DUAL_PRIO_PHASE == 1
+#define FMJ_PRIO_LEVELS { 1, 0,  -1, -1,  -1, -1,  -1, -1,  -1, -1,  -1, -1}
+#elif FMJ_DUAL_PRIO_PHASE == 2
+#define FMJ_PRIO_LEVELS { 1, 0,  -1, -1,  -1, -1,  -1, -1,   2,  2,   1,  0}
+#elif FMJ_DUAL_PRIO_PHASE == 3
+#define FMJ_PRIO_LEVELS { 1, 1,  -1, -1,  -1, -1,   0,  0,   2,  2,   1,  1}
+#elif FMJ_DUAL_PRIO_PHASE == 4
+#define FMJ_PRIO_LEVELS { 1, 0,  -1, -1,  -1, -1,   0, -1,   1, -1,  -1, -1}
+#elif FMJ_DUAL_PRIO_PHASE == 5
+#define FMJ_PRIO_LEVELS { 1, 0,  -1, -1,  -1, -1,  -1, -1,   0,  1,  -1, -1}
+#elif FMJ_DUAL_PRIO_PHASE == 6
+#define FMJ_PRIO_LEVELS { 1, 0,   2,  2,   1,  0,  -1, -1,   2,  2,   1,  0}
+#elif FMJ_DUAL_PRIO_PHASE == 7
+#define FMJ_PRIO_LEVELS { 1, 0,  -1, -1,  -1, -1,  -1, -1,   3,  2,   1,  0}
+#elif FMJ_DUAL_PRIO_PHASE == 8
+#define FMJ_PRIO_LEVELS { 1, 0,  -1, -1,  -1, -1,  -1, -1,   2,  2,  -1, -1}
+#else
+#error "FMJ_DUAL_PRIO_PHASE: 1 (A) .. 8 (H)"
+#endif
+// (PRIO, PRIO_P, prio_sw and step are the step loop's; the period P gates the top of the step only)
+#define FMJ_PRIO_AT(PT_) do { \
+    constexpr int lv_[2 * FMJ_PRIO_NPOINTS] = FMJ_PRIO_LEVELS; \
+    constexpr int w_ = lv_[2 * (PT_)], l_ = lv_[2 * (PT_) + 1]; \
+    if (PRIO > 0 && (w_ >= 0 || l_ >= 0) && prio_sw && ((PT_) != FMJ_PRIO_TOP || (step & (PRIO_P - 1)) == 0)) { \
+      if (w_ == l_) __builtin_amdgcn_s_setprio(w_ >= 0 ? w_ : 0); \
+      else if (((step / PRIO_P) ^ prio_sw) & 1) { if (w_ >= 0) __builtin_amdgcn_s_setprio(w_ >= 0 ? w_ : 0); } \
+      else { if (l_ >= 0) __builtin_amdgcn_s_setprio(l_ >= 0 ? l_ : 0); } \
+    } } while (0)
 #define FMJ_HWREG_WAVE_SLOT (4 | (0 << 6) | (3 << 11))      // s_getreg operand: HW_REG_HW_ID, bits 3:0 = the wave's slot on its SIMD
 #define FMJ_HWREG_HW_ID (4 | (0 << 6) | (31 << 11))         // the whole register: slot, SIMD, pipe, CU, SH, SE, ...
 #define FMJ_HWREG_XCC_ID (20 | (0 << 6) | (31 << 11))       // HW_REG_XCC_ID: bits 3:0 = the XCC
@@ -393,10 +442,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
 #pragma unroll 1
   for (int step = 0; step < n_loop; step++) {
     if (__all(frozen)) break;
-    if (PRIO > 0 && prio_sw && (step & (PRIO_P - 1)) == 0) {      // (uniform) the waves of a SIMD swap priority every PRIO_P steps
-      if (((step / PRIO_P) ^ prio_sw) & 1) __builtin_amdgcn_s_setprio(1);
-      else __builtin_amdgcn_s_setprio(0);
-    }
+    FMJ_PRIO_AT(FMJ_PRIO_TOP);      // (uniform) the waves of a SIMD swap priority every PRIO_P steps
     asm volatile("" : "+s"(Ap));                 // arguments are re-read inside the step, never carried across it
     asm volatile("" : "+s"(Mp));
     // per-lane indices, masks and LDS addresses are recomputed inside every step: hoisted out of the loop they would be
@@ -492,9 +538,11 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
 #include "fmj_stage2_c.inc"
     }
     STAMP(3);
+    FMJ_PRIO_AT(FMJ_PRIO_V);
     // ---- V: joint velocity, cvel = chain sum of joint velocities, cacc = chain sum of cvel_parent x vJ - g
 #include "fmj_stage2_v.inc"
     STAMP(4);
+    FMJ_PRIO_AT(FMJ_PRIO_VEND);
     // ---- F: body force (inertial minus external) about the tree CoM
     const v3 dcom = sub3(xi, com);
     s6 fbody;
@@ -533,6 +581,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
       }
     }
     STAMP(0);
+    FMJ_PRIO_AT(FMJ_PRIO_S);
     // ---- S: subtree sums as prefix-sum differences inside the half (fp64 DPP scans, see fmj_hip.hip)
     {
       const float4 c_ipos = RES ? r_ipos : BT2(bl, 2);            // .w = subtree mass (model constant)
@@ -653,6 +702,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
     }
     WSYNC();                                         // CD / F / CI are dead from here: the published rows overlay them
     STAMP(8);
+    FMJ_PRIO_AT(FMJ_PRIO_L);
     // ---- L: L'DL over the lane dofs by rounds (as in ldl_factor); the 3x3 Schur complement of the translational dofs rides along
     // The leaves-first sweep of the solve rides in the rounds: when dof k is a pivot its right-hand side x_k is complete
     // (every descendant was a pivot before it) and t_ = row_k[depth_a] / D_k is exactly L[k][a], so each ancestor a does
@@ -780,6 +830,7 @@ __global__ void __launch_bounds__(64, WPS) fmj_step_dual2_kernel(const DevModel 
       my_qacc = x;
     }
     STAMP(10);
+    FMJ_PRIO_AT(FMJ_PRIO_XEND);
     // ---- Euler
     const float hstep = OPT_INTEGRATE ? M.h : 0.f;
     const float pre_qd = QV[mydof];

@@ -2621,13 +2621,15 @@ int fmj_kernel_info(const fmj_ctx* c, int32_t* lds_bytes_per_env, int32_t* threa
   return FMJ_OK;
 }
 
-int fmj_dual_build_info(const fmj_ctx* c, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch, int32_t* prio_enabled) {
+int fmj_dual_build_info(const fmj_ctx* c, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch, int32_t* prio_enabled, int32_t* prio_policy) {
   if (!c) return set_err(FMJ_ERR_ARG, "fmj_dual_build_info: NULL ctx");
   const bool dual = c->path == PATH_TWO_ENV;
   if (waves_per_simd) *waves_per_simd = dual ? c->dual_wps : 0;
   if (lean_enabled) *lean_enabled = dual ? c->dual_lean : 0;
   if (last_launch) *last_launch = c->dual_last;
-  if (prio_enabled) *prio_enabled = (dual && c->dual_wps <= FMJ_DUAL_PRIO_MAX_WPS && FMJ_DUAL_PRIO_POLICY != 0) ? c->dual_prio : 0;      // what the context's builds really run
+  const int prio = (dual && c->dual_wps <= FMJ_DUAL_PRIO_MAX_WPS && FMJ_DUAL_PRIO_POLICY != 0) ? c->dual_prio : 0;      // what the context's builds really run
+  if (prio_enabled) *prio_enabled = prio;
+  if (prio_policy) *prio_policy = prio ? FMJ_DUAL_PRIO_PHASE : 0;
   return FMJ_OK;
 }
 

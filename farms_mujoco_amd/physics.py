@@ -247,10 +247,13 @@ class BatchedPhysics:
         if hasattr(self._lib, 'fmj_dual_build_info') and self._lib.fmj_dual_build_info.argtypes:     # absent only from an A/B base build (FMJ_SO)
             # the two-env step kernel's build (include/fmj.h: fmj_dual_build_info): register tier, whether fused launches of the
             # flagship shape run the lean build, what the last step launch ran, and whether fused launches alternate the issue
-            # priority of the waves of a SIMD (an A/B base build from before that argument leaves it at 0)
-            wps, lean, last, prio = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-            _lib.check(self._lib.fmj_dual_build_info(self._ctx, ctypes.byref(wps), ctypes.byref(lean), ctypes.byref(last), ctypes.byref(prio)))
+            # priority of the waves of a SIMD and by which policy (csrc/fmj_dual2.inc, FMJ_DUAL_PRIO_PHASE; 0 = none).  An A/B base build
+            # from before either argument leaves it at 0
+            wps, lean, last, prio, pol = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+            _lib.check(self._lib.fmj_dual_build_info(self._ctx, ctypes.byref(wps), ctypes.byref(lean), ctypes.byref(last), ctypes.byref(prio),
+                                                     ctypes.byref(pol)))
             if wps.value:
                 info.update(dual_wps=wps.value, dual_build='lean' if lean.value else 'generic',
-                            dual_last_launch=(None, 'generic', 'rare', 'lean')[last.value], dual_prio=bool(prio.value))
+                            dual_last_launch=(None, 'generic', 'rare', 'lean')[last.value], dual_prio=bool(prio.value),
+                            dual_prio_policy=pol.value)
         return info

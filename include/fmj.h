@@ -327,10 +327,14 @@ int fmj_kernel_info(const fmj_ctx* ctx, int32_t* lds_bytes_per_env, int32_t* thr
  * it off, for comparisons).  *last_launch: the FMJ_DUAL_BUILD_* the last step launch of the context ran.  *prio_enabled (appended; the
  * parameters in front of it are as before): 1 when the fused launches of the kernel let the waves that share a SIMD take turns at
  * issue priority (s_setprio; scheduling only, bitwise the same results; FMJ_DUAL_PRIO=0 in the environment at fmj_create turns it off); 0 for a
- * register tier whose builds do not carry the policy (today waves_per_simd = 4).
+ * register tier whose builds do not carry the policy (today waves_per_simd = 4).  *prio_policy (appended in the same way): which
+ * s_setprio the waves of such a launch execute at which point of a step, FMJ_DUAL_PRIO_PHASE of csrc/fmj_dual2.inc: 8 = the waves swap
+ * levels 1 / 0 at the top of every step and both run at level 2 from the factorisation rounds to the end of the step, 1 = the swap
+ * alone (the other ids are measurement variants; the id is chosen at compile time); 0 where *prio_enabled is 0.
  * Any pointer may be NULL. */
 enum { FMJ_DUAL_BUILD_NONE = 0, FMJ_DUAL_BUILD_GENERIC = 1, FMJ_DUAL_BUILD_RARE = 2, FMJ_DUAL_BUILD_LEAN = 3 };
-int fmj_dual_build_info(const fmj_ctx* ctx, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch, int32_t* prio_enabled);
+int fmj_dual_build_info(const fmj_ctx* ctx, int32_t* waves_per_simd, int32_t* lean_enabled, int32_t* last_launch, int32_t* prio_enabled,
+                        int32_t* prio_policy);
 
 /* ---- swimming links (SwimmingHandler.__init__, reference drag.pyx:333-387) ------------------
  * n_xfrc_rows: rows per env of the xfrc array (len(data.sensors.xfrc.names); the env stride of every xfrc row
