@@ -143,6 +143,7 @@ def build_id() -> str:
 
 
 _lib = None
+_bound = set()          # the names of SYMBOLS that load() found in the library
 ABI_VERSION = 6         # FMJ_ABI_VERSION of include/fmj.h
 
 
@@ -237,10 +238,31 @@ def load():
             raise
         fn.restype = res
         fn.argtypes = args
+        _bound.add(name)
     if lib.fmj_abi_version() != ABI_VERSION:
         raise FmjError('libfmj_hip.so ABI version mismatch; rebuild')
     _lib = lib
     return lib
+
+
+def has(name: str) -> bool:
+    """True when ``name`` is bound in the loaded library: every declared symbol, except the OPTIONAL_IN_AB_BASE ones that an A/B base
+    build (FMJ_SO) does not export."""
+    load()
+    return name in _bound
+
+
+def ints(fn, ctx):
+    """The int32 out-parameters of a query ``fn(ctx, &a, &b, ...)`` (fmj_kernel_info and its like), as a list."""
+    out = [ctypes.c_int32() for _ in fn.argtypes[1:]]
+    check(fn(ctx, *map(ctypes.byref, out)))
+    return [v.value for v in out]
+
+
+def stream_ptr(device):
+    """The current stream of ``device``, as the ``hip_stream`` argument of a C-ABI call."""
+    import torch      # (here and not at the top: loading the library needs neither torch nor a GPU)
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def check(rc: int):

@@ -4,11 +4,15 @@ The reference's ExperimentTask calls ``controller.step/positions/torques/springr
 ``controller.joints_names[ControlType.*]`` every control step (reference task.py:229-252,292-346).
 Here the same interface returns batched device tensors instead of per-joint dicts.
 """
+import ctypes
 import enum
 import math
 
 import numpy as np
 import torch
+
+from . import _lib
+from .model import wave_controller_params
 
 
 class ControlType(enum.IntEnum):
@@ -51,7 +55,6 @@ class WaveController(AnimatController):
 
     def __init__(self, model, env_phase, frequency=1.0, amplitude=0.3, n_wave=1.0, device='cuda:0', *, amplitude_env=None,
                  phase_lag_env=None):
-        from .model import wave_controller_params
         names = [model.joint_names[model.actuator_jntid[a]] for a in range(model.nu)
                  if model.actuator_tags[a] == 'position']
         super().__init__({ControlType.POSITION: names, ControlType.VELOCITY: [], ControlType.TORQUE: []})
@@ -121,7 +124,6 @@ class OscillatorNetwork:
 
     def as_c(self, struct):
         """Fill a ctypes mirror of fmj_cpg_desc (``struct`` = its class); arrays stay owned by self."""
-        import ctypes
         I, D = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
         d = struct()
         d.n_osc, d.n_conn, d.nu = self.n_osc, self.n_conn, self.nu
@@ -197,7 +199,6 @@ class NetworkController(AnimatController):
                       out_offset='nu')
 
     def __init__(self, model, network, n_envs, env_phase=None, drive=None, device='cuda:0', timestep=None, env_params=None):
-        from . import _lib
         names = [model.joint_names[model.actuator_jntid[a]] for a in range(model.nu)
                  if model.actuator_tags[a] == 'position']
         super().__init__({ControlType.POSITION: names, ControlType.VELOCITY: [], ControlType.TORQUE: []})
@@ -208,7 +209,6 @@ class NetworkController(AnimatController):
         self.timestep = float(model.timestep if timestep is None else timestep)
         self._timestep_given = timestep is not None      # ExperimentTask.initialize_control sets / validates it against task.timestep
         self._lib = _lib.load()
-        import ctypes
         self._ctx = ctypes.c_void_p()
         self._desc = network.as_c(_lib.CCpgDesc)
         _lib.check(self._lib.fmj_cpg_create(ctypes.byref(self._desc), self.device.index or 0, ctypes.byref(self._ctx)))
@@ -257,12 +257,10 @@ class NetworkController(AnimatController):
 
     def ctrl_tape(self, n_steps):
         """Advance the network ``n_steps`` and return ctrl[n_steps, n_envs, nu] (device)."""
-        import ctypes
-        from . import _lib
         if self._tape is None or self._tape.shape[0] < n_steps:
             self._tape = torch.empty(n_steps, self.n_envs, self.nu, dtype=torch.float32, device=self.device)
         tape = self._tape[:n_steps]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _lib.stream_ptr(self.device)
         drive = None if self.drive is None else self.drive.data_ptr()
         if not self.env_params:
             _lib.check(self._lib.fmj_cpg_tape(self._ctx, self.n_envs, n_steps, self.timestep, self.phase.data_ptr(),

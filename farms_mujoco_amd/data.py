@@ -68,6 +68,11 @@ class SensorArray:
         return self._base[0] + index*self._base[1]
 
 
+def c_rows(index, links=None, joints=None, xfrc=None, contacts=None):
+    """fmj_rows of ring index ``index``: each field points at that row of the SensorArray given for it, or is NULL."""
+    return _lib.CRows(*[None if s is None else s.row_ptr(index) for s in (links, joints, xfrc, contacts)])
+
+
 class AnimatData:
     def __init__(self, timestep, buffer_size, n_envs, links, joints, xfrc=None, contacts=(), device='cuda:0'):
         self.timestep = timestep

@@ -26,13 +26,10 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 class _MjData(SimpleNamespace):
     """``physics.data``: rebinding a field (``data.qpos = tensor``) is seen by the cached pointer struct of the per-step host path;
     in-place writes (``data.qpos[:] = ...``) never move a tensor."""
+    _cdata_cache = None
 
     def __setattr__(self, name, value):
         object.__setattr__(self, '_cdata_cache', None)
@@ -60,13 +57,13 @@ class BatchedPhysics:
             _lib.check(self._lib.fmj_create(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
                                             ctypes.byref(ctx)))
         else:
-            if not (hasattr(self._lib, 'fmj_create_ex') and self._lib.fmj_create_ex.argtypes):      # an A/B base build (FMJ_SO)
+            if not _lib.has('fmj_create_ex'):      # an A/B base build (FMJ_SO)
                 raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex: precision=%r needs a current build' % precision)
             opts = _lib.CCreateOptions(ctypes.sizeof(_lib.CCreateOptions), _lib.PRECISIONS[precision])
             _lib.check(self._lib.fmj_create_ex(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
                                                ctypes.byref(opts), ctypes.byref(ctx)))
         self._ctx = ctx
-        code = self._lib.fmj_precision(self._ctx) if hasattr(self._lib, 'fmj_precision') and self._lib.fmj_precision.argtypes else 0
+        code = self._lib.fmj_precision(self._ctx) if _lib.has('fmj_precision') else 0
         self.precision = {v: k for k, v in _lib.PRECISIONS.items()}[code]      # what the context reports
         lay = _lib.CSensorLayout()
         _lib.check(self._lib.fmj_get_sensor_layout(self._ctx, ctypes.byref(lay)))
@@ -87,12 +84,10 @@ class BatchedPhysics:
         self.data.xquat[:, :, 0] = 1.0
         self.data.qpos_spring[:] = torch.as_tensor(m.qpos_spring, dtype=torch.float32)
         # the solver that actually runs (fmj_solver_info): fmj_create swaps a primal solver for the dual one on near-frictionless contacts
-        rq, ef, it = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        if hasattr(self._lib, 'fmj_solver_info') and self._lib.fmj_solver_info.argtypes:     # absent only from an A/B base build (FMJ_SO)
-            _lib.check(self._lib.fmj_solver_info(self._ctx, ctypes.byref(rq), ctypes.byref(ef), ctypes.byref(it)))
+        rq, ef, it = _lib.ints(self._lib.fmj_solver_info, self._ctx) if _lib.has('fmj_solver_info') else (0, 0, 0)     # absent only from an A/B base build (FMJ_SO)
         names = {0: 'PGS', 1: 'CG', 2: 'Newton'}
-        self.solver_requested, self.solver_effective, self.solver_budget = names[rq.value], names[ef.value], it.value
-        if rq.value != ef.value:
+        self.solver_requested, self.solver_effective, self.solver_budget = names[rq], names[ef], it
+        if rq != ef:
             import warnings
             why = ('the noslip post-pass works on the dual matrices, which a primal solver never forms' if int(getattr(model, 'noslip_iterations', 0)) > 0 else
                    'explicit pairs under the elliptic cone have the dual block update only' if (int(getattr(model, 'cone', 0)) == 1 and int(getattr(model, 'npair', 0)) > 0) else
@@ -110,32 +105,15 @@ class BatchedPhysics:
             self._ctx = None
 
     # ---- marshalling ----------------------------------------------------------------------------
-    def _cdata(self, ctrl: Optional[torch.Tensor] = None, use_xfrc: bool = True) -> _lib.CData:
+    def _cdata(self, ctrl: Optional[torch.Tensor] = None) -> _lib.CData:
+        """fmj_data of ``physics.data`` (``ctrl``: a ctrl tape in the place of ``data.ctrl``): built once per binding of the fields
+        (_MjData), and handed out as a private copy - callers edit single fields."""
         d = self.data
-        cached = getattr(d, '_cdata_cache', None)
-        if cached is not None:                  # a private copy: callers edit single fields (ctrl tapes)
-            c = _lib.CData.from_buffer_copy(cached)
-            if ctrl is not None:
-                c.ctrl = ctrl.data_ptr()
-            if not use_xfrc:
-                c.xfrc_applied = None
-            return c
-        c = self._cdata_build()
-        object.__setattr__(d, '_cdata_cache', _lib.CData.from_buffer_copy(c))
-        return self._cdata(ctrl, use_xfrc)
-
-    def _cdata_build(self) -> _lib.CData:
-        d = self.data
-        ctrl, use_xfrc = None, True
-        c = _lib.CData()
-        c.qpos, c.qvel = d.qpos.data_ptr(), d.qvel.data_ptr()
-        c.ctrl = (d.ctrl if ctrl is None else ctrl).data_ptr()
-        c.qpos_spring = d.qpos_spring.data_ptr()
-        c.xfrc_applied = d.xfrc_applied.data_ptr() if use_xfrc else None
-        c.xpos, c.xquat, c.xipos = d.xpos.data_ptr(), d.xquat.data_ptr(), d.xipos.data_ptr()
-        c.sensordata, c.qacc, c.time, c.status = (d.sensordata.data_ptr(), d.qacc.data_ptr(), d.time.data_ptr(),
-                                                  d.status.data_ptr())
-        c.qacc_warmstart, c.contact, c.ncon = d.qacc_warmstart.data_ptr(), d.contact.data_ptr(), d.ncon.data_ptr()
+        if d._cdata_cache is None:
+            object.__setattr__(d, '_cdata_cache', _lib.CData(*[getattr(d, name).data_ptr() for name, _ in _lib.CData._fields_]))
+        c = _lib.CData.from_buffer_copy(d._cdata_cache)
+        if ctrl is not None:
+            c.ctrl = ctrl.data_ptr()
         return c
 
     # ---- dm_control Physics surface -----------------------------------------------------------------
@@ -150,31 +128,37 @@ class BatchedPhysics:
         self.forward(disable_actuation=True)
 
     def forward(self, disable_actuation: bool = False):
-        c = self._cdata()
-        _lib.check(self._lib.fmj_forward(self._ctx, ctypes.byref(c), int(disable_actuation), _stream_ptr(self.device)))
+        _lib.check(self._lib.fmj_forward(self._ctx, ctypes.byref(self._cdata()), int(disable_actuation), _lib.stream_ptr(self.device)))
 
     def step(self, nstep: int = 1, ctrl_tape: Optional[torch.Tensor] = None):
         """mujoco.mj_step x nstep for every env (reference simulation.py:156 via Physics.step).
         ``ctrl_tape`` [nstep, n_envs, nu] supplies a different ctrl row per step."""
         if ctrl_tape is not None:
             assert ctrl_tape.shape == (nstep, self.n_envs, self.model.nu) and ctrl_tape.is_contiguous()
-            c = self._cdata(ctrl=ctrl_tape)
-            stride = self.n_envs*self.model.nu
-        else:
-            c = self._cdata()
-            stride = 0
-        _lib.check(self._lib.fmj_step(self._ctx, ctypes.byref(c), int(nstep), stride, _stream_ptr(self.device)))
+        stride = 0 if ctrl_tape is None else self.n_envs*self.model.nu
+        _lib.check(self._lib.fmj_step(self._ctx, ctypes.byref(self._cdata(ctrl_tape)), int(nstep), stride, _lib.stream_ptr(self.device)))
 
     def step_debug(self, want_pgs: bool = True):
         """One mj_step through ``fmj_step_debug``: returns ``(efc_rows [n_envs, maxefc, 8], pgs_improvement [n_envs,
         solver_iterations] or None)`` next to the usual state update (tests of the constraint solve; not the product path)."""
-        me, mc, it = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(self._lib.fmj_constraint_info(self._ctx, ctypes.byref(me), ctypes.byref(mc), ctypes.byref(it)))
-        rows = torch.zeros(self.n_envs, max(me.value, 1), 8, device=self.device)
-        imp = torch.full((self.n_envs, max(it.value, 1)), float('nan'), device=self.device) if want_pgs else None
-        c = self._cdata()
-        _lib.check(self._lib.fmj_step_debug(self._ctx, ctypes.byref(c), _ptr(rows), _ptr(imp), _stream_ptr(self.device)))
+        maxefc, _, iterations = _lib.ints(self._lib.fmj_constraint_info, self._ctx)
+        rows = torch.zeros(self.n_envs, max(maxefc, 1), 8, device=self.device)
+        imp = torch.full((self.n_envs, max(iterations, 1)), float('nan'), device=self.device) if want_pgs else None
+        _lib.check(self._lib.fmj_step_debug(self._ctx, ctypes.byref(self._cdata()), _ptr(rows), _ptr(imp), _lib.stream_ptr(self.device)))
         return rows, imp
+
+    def forward_debug(self, disable_actuation: bool = False):
+        """mj_forward through ``fmj_forward_debug``: returns ``(H [n_envs, nv, row_stride], qfrc_smooth [n_envs, nv])`` next to the
+        usual derived fields - the packed rows of H = M + diag(armature + h damping) as the step assembles them (include/fmj.h; tests
+        of the stages, not the product path).  The library names its row stride in the call that fills the rows, so they land in a
+        buffer of the longest row any build has (64, _lib.build) and H is the view of its packed head: ``H._base`` is the whole
+        buffer, zero past the rows."""
+        n, nv, rs = self.n_envs, self.model.nv, ctypes.c_int32()
+        buf = torch.zeros(n*nv*64, device=self.device)
+        qfrc = torch.zeros(n, nv, device=self.device)
+        _lib.check(self._lib.fmj_forward_debug(self._ctx, ctypes.byref(self._cdata()), int(disable_actuation), _ptr(buf), ctypes.byref(rs),
+                                               _ptr(qfrc), _lib.stream_ptr(self.device)))
+        return buf[:n*nv*rs.value].view(n, nv, rs.value), qfrc
 
     # ---- checkpoint / resume (SURVEY section 5) ---------------------------------------------------------
     STATE_FIELDS = ('qpos', 'qvel', 'ctrl', 'qpos_spring', 'xfrc_applied', 'xpos', 'xquat', 'xipos', 'sensordata', 'qacc',
@@ -241,19 +225,15 @@ class BatchedPhysics:
                                                   pr.ctypes.data_as(I) if len(pr) else None))
 
     def kernel_info(self):
-        lds, thr = ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(self._lib.fmj_kernel_info(self._ctx, ctypes.byref(lds), ctypes.byref(thr)))
-        info = dict(lds_bytes_per_env=lds.value, threads_per_env=thr.value)
-        if hasattr(self._lib, 'fmj_dual_build_info') and self._lib.fmj_dual_build_info.argtypes:     # absent only from an A/B base build (FMJ_SO)
+        lds, thr = _lib.ints(self._lib.fmj_kernel_info, self._ctx)
+        info = dict(lds_bytes_per_env=lds, threads_per_env=thr)
+        if _lib.has('fmj_dual_build_info'):     # absent only from an A/B base build (FMJ_SO)
             # the two-env step kernel's build (include/fmj.h: fmj_dual_build_info): register tier, whether fused launches of the
             # flagship shape run the lean build, what the last step launch ran, and whether fused launches alternate the issue
             # priority of the waves of a SIMD and by which policy (csrc/fmj_dual2.inc, FMJ_DUAL_PRIO_PHASE; 0 = none).  An A/B base build
             # from before either argument leaves it at 0
-            wps, lean, last, prio, pol = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-            _lib.check(self._lib.fmj_dual_build_info(self._ctx, ctypes.byref(wps), ctypes.byref(lean), ctypes.byref(last), ctypes.byref(prio),
-                                                     ctypes.byref(pol)))
-            if wps.value:
-                info.update(dual_wps=wps.value, dual_build='lean' if lean.value else 'generic',
-                            dual_last_launch=(None, 'generic', 'rare', 'lean')[last.value], dual_prio=bool(prio.value),
-                            dual_prio_policy=pol.value)
+            wps, lean, last, prio, pol = _lib.ints(self._lib.fmj_dual_build_info, self._ctx)
+            if wps:
+                info.update(dual_wps=wps, dual_build='lean' if lean else 'generic', dual_last_launch=(None, 'generic', 'rare', 'lean')[last],
+                            dual_prio=bool(prio), dual_prio_policy=pol)
         return info

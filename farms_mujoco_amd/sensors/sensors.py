@@ -1,9 +1,8 @@
 """Contact sensors - HIP counterpart of reference farms_mujoco/sensors/sensors.pyx (contacts part)."""
 import ctypes
 
-import torch
-
 from .. import _lib
+from ..data import c_rows
 
 
 def cycontacts2data(physics, iteration, data, geompair2data, meters, newtons):
@@ -13,12 +12,10 @@ def cycontacts2data(physics, iteration, data, geompair2data, meters, newtons):
     ``get_physics2data_maps`` and already uploaded with ``physics.set_contact_maps`` (kept for signature
     compatibility).  The row of ring index ``iteration`` is overwritten (the reference accumulates with ``+=``
     into a fresh row)."""
-    rows = _lib.CRows()
-    rows.contacts = data.array[iteration].data_ptr()
+    rows = c_rows(iteration, contacts=data)
     u = _lib.CUnits(meters, newtons, 1.0, 1.0, 1.0, 1.0)
-    c = physics._cdata()
-    _lib.check(physics._lib.fmj_contacts2data(physics._ctx, ctypes.byref(c), ctypes.byref(rows), ctypes.byref(u),
-                                              ctypes.c_void_p(torch.cuda.current_stream(physics.device).cuda_stream)))
+    _lib.check(physics._lib.fmj_contacts2data(physics._ctx, ctypes.byref(physics._cdata()), ctypes.byref(rows), ctypes.byref(u),
+                                              _lib.stream_ptr(physics.device)))
 
 
 def cymusclesensors2data(*args, **kwargs):

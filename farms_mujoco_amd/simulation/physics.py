@@ -2,9 +2,9 @@
 import ctypes
 
 import numpy as np
-import torch
 
 from .. import _lib
+from ..data import c_rows
 from ..model import JNT_FREE
 
 
@@ -78,23 +78,16 @@ def physics2data(physics, iteration, data, maps, units, links_only=False, swimmi
     rows, the contact rows of ``cycontacts2data`` when the data has contact sensors, and - ``swimming`` = the SwimmingHandler of a
     swimming callback that comes first among the task's callbacks - its drag on the links row just written (reference
     task.py:176-182: sensors, then the callbacks in order)."""
-    rows = _lib.CRows()
-    rows.links = data.sensors.links.row_ptr(iteration)
-    rows.joints = data.sensors.joints.row_ptr(iteration)
-    flags = _lib.BEFORE_ROWS | (_lib.BEFORE_LINKS_ONLY if links_only else 0)
-    if not links_only and data.sensors.contacts.names:
-        rows.contacts = data.sensors.contacts.row_ptr(iteration)
-        flags |= _lib.BEFORE_CONTACTS
+    sensors = data.sensors
+    contacts = sensors.contacts if not links_only and sensors.contacts.names else None
+    drag = swimming is not None and swimming.drag
+    rows = c_rows(iteration, sensors.links, sensors.joints, swimming.xfrc if drag else None, contacts)
+    flags = _lib.BEFORE_ROWS | (_lib.BEFORE_LINKS_ONLY if links_only else 0) | (_lib.BEFORE_CONTACTS if contacts else 0)
     water, xa = None, None
-    if swimming is not None and swimming.drag:
-        rows.xfrc = swimming.xfrc.row_ptr(iteration)
+    if drag:
         cwater = swimming.water.as_c(use_buoyancy=swimming.buoyancy)      # (kept alive until the call returns)
         water = ctypes.byref(cwater)
         xa = physics.data.xfrc_applied.data_ptr()
         flags |= _lib.BEFORE_DRAG
-    c = physics._cdata()
-    u = getattr(units, '_c_cache', None)
-    if u is None:
-        u = units._c_cache = units.as_c()       # (SimulationUnitScaling is a set of constants for the life of a task)
-    _lib.check(physics._lib.fmj_before_step(physics._ctx, ctypes.byref(c), ctypes.byref(rows), water, ctypes.byref(u), flags,
-                                            ctypes.c_void_p(xa), ctypes.c_void_p(torch.cuda.current_stream(physics.device).cuda_stream)))
+    _lib.check(physics._lib.fmj_before_step(physics._ctx, ctypes.byref(physics._cdata()), ctypes.byref(rows), water, ctypes.byref(units.as_c()), flags,
+                                            ctypes.c_void_p(xa), _lib.stream_ptr(physics.device)))

@@ -50,13 +50,45 @@ def _wave_args(a, c, n_envs, nu):
     return ext if per_env else None
 
 
+def _fused_args(task, phys, n_steps, rows=True, a=None):
+    """The ``(CData, CFusedArgs, ext)`` of a fused launch of ``n_steps`` iterations, as far as a chunk (Simulation.step_fused) and the
+    one-step launch of the per-iteration path (Simulation._step_with_controller) agree: ring, sub-steps and units, with ``rows`` the
+    rows, their strides and the swimming callback's drag and water, and the device controller - a ctrl tape in CData.ctrl, or the
+    wave controller with its per-env ``ext`` (None: a plain fmj_step_fused).  ``a``: the struct an earlier call with the same
+    ``n_steps`` returned, filled again (the per-step host path: no new struct, no tensor view); a call without ``rows`` switches off
+    what one with them left there (do_readout = do_drag = 0), and the water is read at every call (set_water_velocity)."""
+    if a is None:
+        a = _lib.CFusedArgs()
+        a.n_steps, a.buffer_size, a.substeps, a.units = n_steps, task.buffer_size, task.substeps, task.units.as_c()
+    a.do_readout = a.do_drag = 0
+    if rows:
+        sens, base = task.data.sensors, a.rows_base
+        a.do_readout = 1
+        base.links, base.joints, base.xfrc = sens.links.row_ptr(0), sens.joints.row_ptr(0), sens.xfrc.row_ptr(0)
+        a.row_stride_links, a.row_stride_joints, a.row_stride_xfrc = sens.links.array.stride(0), sens.joints.array.stride(0), sens.xfrc.array.stride(0)
+        swim, handler = task.swimming()
+        if swim is not None:
+            a.do_drag = int(handler.drag)
+            a.water = handler.water.as_c(use_buoyancy=handler.buoyancy)
+    c, cd, ext = task._controller, phys._cdata(), None
+    if getattr(c, 'tape', False):        # device controller that hands over a ctrl tape
+        tape = c.ctrl_tape(n_steps)
+        a.controller, a.ctrl_step_stride = 0, tape.stride(0)
+        cd.ctrl = tape.data_ptr()
+    elif c is not None:
+        a.controller = 1
+        ext = _wave_args(a, c, phys.n_envs, phys.model.nu)
+        a.ctrl_out = phys.data.ctrl.data_ptr()       # callbacks reading physics.data.ctrl see the last step's command
+    return cd, a, ext
+
+
 def _launch_fused(phys, cd, a, ext):
     """fmj_step_fused, or fmj_step_fused_ex when the controller has a per-env field (include/fmj.h)."""
-    stream = ctypes.c_void_p(torch.cuda.current_stream(phys.device).cuda_stream)
+    stream = _lib.stream_ptr(phys.device)
     if ext is None:
         _lib.check(phys._lib.fmj_step_fused(phys._ctx, ctypes.byref(cd), ctypes.byref(a), stream))
     else:
-        if not (hasattr(phys._lib, 'fmj_step_fused_ex') and phys._lib.fmj_step_fused_ex.argtypes):      # an A/B base build (FMJ_SO)
+        if not _lib.has('fmj_step_fused_ex'):      # an A/B base build (FMJ_SO)
             raise _lib.FmjError('this libfmj_hip.so has no fmj_step_fused_ex: per-env wave parameters need a current build')
         _lib.check(phys._lib.fmj_step_fused_ex(phys._ctx, ctypes.byref(cd), ctypes.byref(a), ctypes.byref(ext), stream))
 
@@ -71,6 +103,12 @@ class Simulation:
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here
     advances exactly ``n_iterations * substeps`` physics steps after an explicit :meth:`reset`.
     """
+
+    # the stepping state an object starts from, also one made without the constructor (the host-logic tests); reset() sets the first two again
+    _ahead_ok = None       # whether a step's launch may write the next iteration's rows: None = decide at the next step (_env_step)
+    _rows_for = -1         # the sim_iteration whose rows the previous launch wrote already
+    _step_args = None      # the fmj_fused_args of _step_with_controller, one struct for all its launches
+    _env_order = None      # keeps the env order of the last fused launch alive
 
     def __init__(self, mjcf_model: Model, base_link: str, simulation_options: SimulationOptions,
                  legacy_step: bool = False, **kwargs):
@@ -115,7 +153,7 @@ class Simulation:
         callbacks = kwargs.pop('callbacks', [])
         water = getattr(arena_options, 'water', None)
         if water is not None and water.height is not None and (water.drag or water.sph) \
-                and not any(isinstance(cb, SwimmingCallback) for cb in callbacks):
+                and SwimmingCallback.first(callbacks)[0] is None:
             callbacks = [SwimmingCallback(animat_options, arena_options)] + list(callbacks)
         if save_mjcf or show_mjcf:                   # reference mjcf.py:1503-1509
             from .mjcf import model2mjcf_xml
@@ -140,9 +178,9 @@ class Simulation:
         and xfrc_applied - fmj_fused_args::rows_ahead - so before_step finds them done) and two otherwise (fmj_before_step, then the
         step, which also evaluates a device controller); round 4 took four and a handful of torch kernels for the ctrl write."""
         task, phys = self.task, self.physics
-        if getattr(self, '_ahead_ok', None) is None:
+        if self._ahead_ok is None:
             self._ahead_ok = task.rows_ahead_ok(phys)
-        have_rows = getattr(self, '_rows_for', -1) == task.sim_iteration       # the previous launch wrote this iteration's rows
+        have_rows = self._rows_for == task.sim_iteration       # the previous launch wrote this iteration's rows
         task.before_step(None, phys, rows_written=have_rows)
         if task.controller_in_step() and task.sim_iteration % task.substeps == 0:
             # rows ahead: only when this iteration's own rows are in place (the first iteration gets them from before_step) and another
@@ -159,36 +197,10 @@ class Simulation:
         """One mj_step whose launch evaluates the device controller first (fmj_step_fused of one step).  Without ``rows_ahead`` no rows
         and no drag: before_step wrote them, xfrc_applied and qpos_spring are read from physics.data as fmj_step does.  With it the
         launch also writes what before_step would write for the NEXT iteration."""
-        task, phys = self.task, self.physics
-        a = getattr(self, '_step_args', None)
-        if a is None:
-            a = self._step_args = _lib.CFusedArgs()
-            a.n_steps, a.buffer_size, a.substeps = 1, task.buffer_size, 1
-            a.units = task.units.as_c()
-        a.iteration0 = task.iteration
-        a.rows_ahead = int(rows_ahead)
-        a.do_readout = a.do_drag = 0
-        if rows_ahead:
-            sens = task.data.sensors
-            a.do_readout = 1
-            a.rows_base.links, a.rows_base.joints, a.rows_base.xfrc = sens.links.array.data_ptr(), sens.joints.array.data_ptr(), sens.xfrc.array.data_ptr()
-            a.row_stride_links, a.row_stride_joints, a.row_stride_xfrc = sens.links.array.stride(0), sens.joints.array.stride(0), sens.xfrc.array.stride(0)
-            swim = [cb for cb in task._callbacks if isinstance(cb, SwimmingCallback)]
-            a.do_drag = int(bool(swim) and swim[0].handler.drag)
-            if swim:
-                a.water = swim[0].handler.water.as_c(use_buoyancy=swim[0].handler.buoyancy)
-        c = task._controller
-        cd = phys._cdata()
-        ext = None
-        if getattr(c, 'tape', False):
-            tape = c.ctrl_tape(1)
-            a.controller, a.ctrl_step_stride = 0, tape.stride(0)
-            cd.ctrl = tape.data_ptr()
-        else:
-            a.controller = 1
-            ext = _wave_args(a, c, phys.n_envs, phys.model.nu)
-            a.ctrl_out = phys.data.ctrl.data_ptr()
-        _launch_fused(phys, cd, a, ext)
+        cd, a, ext = _fused_args(self.task, self.physics, 1, rows=rows_ahead, a=self._step_args)
+        self._step_args = a
+        a.iteration0, a.rows_ahead = self.task.iteration, int(rows_ahead)
+        _launch_fused(self.physics, cd, a, ext)
 
     def step_fused(self, n_steps: int):
         """Run ``n_steps`` full iterations (``substeps`` physics steps each) inside ONE launch (fmj_step_fused): ring-buffer
@@ -199,39 +211,12 @@ class Simulation:
         n_steps = min(n_steps, task.n_iterations - task.sim_iteration//task.substeps)
         if n_steps <= 0:
             return 0
-        a = _lib.CFusedArgs()
-        a.n_steps, a.iteration0, a.buffer_size = n_steps, task.sim_iteration//task.substeps, task.buffer_size
-        a.substeps, a.substep_links = task.substeps, int(task.substeps_links)
+        cd, a, ext = _fused_args(task, phys, n_steps)
+        a.iteration0, a.substep_links = task.sim_iteration//task.substeps, int(task.substeps_links)
         a.n_iterations = task.n_iterations if task.n_iterations < (1 << 30) else 0
-        a.do_readout = 1
-        sens = task.data.sensors
-        a.rows_base.links = sens.links.array.data_ptr()
-        a.rows_base.joints = sens.joints.array.data_ptr()
-        a.rows_base.xfrc = sens.xfrc.array.data_ptr()
-        a.row_stride_links = sens.links.array.stride(0)
-        a.row_stride_joints = sens.joints.array.stride(0)
-        a.row_stride_xfrc = sens.xfrc.array.stride(0)
-        if sens.contacts.names:
-            a.rows_base.contacts = sens.contacts.array.data_ptr()
-            a.row_stride_contacts = sens.contacts.array.stride(0)
-        swim = [cb for cb in task._callbacks if isinstance(cb, SwimmingCallback)]
-        a.do_drag = int(bool(swim) and swim[0].handler.drag)
-        if swim:
-            h = swim[0].handler
-            a.water = h.water.as_c(use_buoyancy=h.buoyancy)
-        a.units = task.units.as_c()
-        c = task._controller
-        cd = phys._cdata()
-        ext = None
-        if c is not None and getattr(c, 'tape', False):        # device controller that hands over a ctrl tape
-            tape = c.ctrl_tape(n_steps)
-            a.controller = 0
-            a.ctrl_step_stride = tape.stride(0)
-            cd.ctrl = tape.data_ptr()
-        elif c is not None:
-            a.controller = 1
-            ext = _wave_args(a, c, phys.n_envs, phys.model.nu)
-            a.ctrl_out = phys.data.ctrl.data_ptr()       # callbacks reading physics.data.ctrl see the last step's command
+        contacts = task.data.sensors.contacts
+        if contacts.names:
+            a.rows_base.contacts, a.row_stride_contacts = contacts.row_ptr(0), contacts.array.stride(0)
         if phys.has_constraints and self.order_by_contacts:
             # envs with the most contacts (the slowest to step) are launched first instead of wherever they sit; the two-env constraint
             # kernel steps entries 2b and 2b + 1 of the order in one wave: neighbours have similar row counts (one PGS sweep length

@@ -54,6 +54,14 @@ class SwimmingCallback(TaskCallback):
     def before_step(self, task, action, physics):
         self.handler.step(task.iteration % task.buffer_size)
 
+    @classmethod
+    def first(cls, callbacks):
+        """``(callback, handler)`` of the first swimming callback among ``callbacks`` (no handler before initialize_episode), or two None."""
+        for cb in callbacks:
+            if isinstance(cb, cls):
+                return cb, cb.handler
+        return None, None
+
 
 class ExperimentTask:
     """FARMS experiment (reference task.py:37-412)."""
@@ -78,6 +86,7 @@ class ExperimentTask:
         self.sim_iteration = 0
         self.sim_iterations = self.n_iterations*self.substeps
         self.sim_timestep = self.timestep/self.substeps
+        self.host_step_only = False      # Simulation sets it: the controller is evaluated on the host path and no launch is fused
         self.maps: Dict = {'sensors': {}, 'ctrl': {}, 'xpos': {}, 'qpos': {}, 'geoms': {}, 'links': {},
                            'joints': {}, 'contacts': {}, 'xfrc': {}, 'muscles': {}}
         assert not kwargs, kwargs
@@ -175,15 +184,18 @@ class ExperimentTask:
             return False
         if any(getattr(cb, 'writes_state', False) for cb in self._callbacks) or self.data.sensors.contacts.names:
             return False
-        swims = [i for i, cb in enumerate(self._callbacks) if isinstance(cb, SwimmingCallback)]
-        return swims in ([], [0])
+        return self.swimming(self._callbacks[1:])[0] is None      # no swimming callback, or only in the first place
+
+    def swimming(self, callbacks=None):
+        """SwimmingCallback.first of the task's callbacks, or of ``callbacks``, a part of them."""
+        return SwimmingCallback.first(self._callbacks if callbacks is None else callbacks)
 
     def controller_in_step(self):
         """True when the controller is evaluated by the step launch itself (Simulation._env_step -> fmj_step_fused of one step):
         a device controller (``fusable``) in a run without sub-steps whose host callbacks do not write ``physics.data.ctrl``
         (``TaskCallback.writes_ctrl``).  Same semantics as the fused path: actuators the controller does not drive get ctrl 0."""
         c = self._controller
-        return (c is not None and getattr(c, 'fusable', False) and self.substeps == 1 and not getattr(self, 'host_step_only', False)
+        return (c is not None and getattr(c, 'fusable', False) and self.substeps == 1 and not self.host_step_only
                 and not any(getattr(cb, 'writes_ctrl', False) for cb in self._callbacks))
 
     def before_step(self, action, physics, rows_written=False):
@@ -200,9 +212,11 @@ class ExperimentTask:
         callbacks = [cb for cb in self._callbacks if full_step or (cb.substep and in_run)]
         sensors = (full_step or self.substeps_links) and in_run
         # a swimming callback that comes first has its drag computed by the sensors' own launch (fmj_before_step)
-        swim = callbacks[0] if sensors and callbacks and isinstance(callbacks[0], SwimmingCallback) and callbacks[0].handler is not None else None
+        swim, handler = self.swimming(callbacks[:1])
+        if not sensors or handler is None:
+            swim = None
         if sensors and not rows_written:
-            self.update_sensors(physics=physics, links_only=not full_step, swimming=None if swim is None else swim.handler)
+            self.update_sensors(physics=physics, links_only=not full_step, swimming=None if swim is None else handler)
         for callback in callbacks:
             if callback is not swim:
                 callback.before_step(task=self, action=action, physics=physics)
@@ -290,4 +304,4 @@ class ExperimentTask:
         sub-steps, links-only rows and the iteration counter as before_step / after_step do (include/fmj.h)."""
         cbs_ok = all(getattr(cb, 'fusable', False) for cb in self._callbacks)
         ctl_ok = self._controller is None or getattr(self._controller, 'fusable', False)
-        return cbs_ok and ctl_ok and not getattr(self, 'host_step_only', False)
+        return cbs_ok and ctl_ok and not self.host_step_only

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..data import c_rows
 
 
 class WaterProperties:
@@ -81,14 +82,11 @@ class SwimmingHandler:
         if not (self.drag or self.sph) or not self.drag:
             return
         phys = self.physics
-        rows = _lib.CRows()
-        rows.links = self.links.array[iteration].data_ptr()
-        rows.xfrc = self.xfrc.array[iteration].data_ptr()
+        rows = c_rows(iteration, links=self.links, xfrc=self.xfrc)
         water = self.water.as_c(use_buoyancy=self.buoyancy)
-        units = self.units.as_c()
         xa = phys.data.xfrc_applied.data_ptr() if write_xfrc_applied else None
-        _lib.check(phys._lib.fmj_drag(phys._ctx, ctypes.byref(rows), ctypes.byref(water), ctypes.byref(units),
-                                      ctypes.c_void_p(xa), ctypes.c_void_p(torch.cuda.current_stream(phys.device).cuda_stream)))
+        _lib.check(phys._lib.fmj_drag(phys._ctx, ctypes.byref(rows), ctypes.byref(water), ctypes.byref(self.units.as_c()),
+                                      ctypes.c_void_p(xa), _lib.stream_ptr(phys.device)))
 
     def set_water_velocity(self, velocity):
         self.water.set_velocity(vx=velocity[0], vy=velocity[1], vz=velocity[2])
@@ -118,5 +116,5 @@ def drag_forces(iteration, data_links, links_index, data_xfrc, xfrc_index, coeff
     _lib.check(lib.fmj_drag_link(n_envs, links.device.index or 0, lrow.data_ptr(), links.stride(1), xrow.data_ptr(),
                                  xfrc.stride(1), co.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(mass),
                                  float(height), float(density), ctypes.byref(w), hydro.data_ptr(),
-                                 ctypes.c_void_p(torch.cuda.current_stream(links.device).cuda_stream)))
+                                 _lib.stream_ptr(links.device)))
     return hydro.bool()

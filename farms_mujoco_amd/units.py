@@ -7,6 +7,7 @@ class SimulationUnitScaling:
         self.meters = float(meters)
         self.seconds = float(seconds)
         self.kilograms = float(kilograms)
+        self._c = None      # (base units, fmj_units) of the last as_c()
 
     @property
     def hertz(self): return 1.0/self.seconds
@@ -28,8 +29,12 @@ class SimulationUnitScaling:
     def angular_damping(self): return self.torques/self.angular_velocity
 
     def as_c(self):
-        from ._lib import CUnits
-        return CUnits(self.meters, self.newtons, self.torques, self.velocity, self.angular_velocity, self.kilograms)
+        """fmj_units, rebuilt only when a base unit changed (the per-step host path asks for it every step)."""
+        key = (self.meters, self.seconds, self.kilograms)
+        if self._c is None or self._c[0] != key:
+            from ._lib import CUnits
+            self._c = (key, CUnits(self.meters, self.newtons, self.torques, self.velocity, self.angular_velocity, self.kilograms))
+        return self._c[1]
 
     def as_array(self):
         """(meters, newtons, torques, velocity, angular_velocity) — order used by the oracle wrapper."""

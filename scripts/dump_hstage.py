@@ -2,7 +2,6 @@
 for the same fp32-rounded state, into gpurun_out/hstage_<model>.npz: the input of the error budget of DESIGN section 2
 (which part of the single-step qacc error is the entries of H, which the right-hand side, which the fp32 solve).
 GPU box: python scripts/dump_hstage.py"""
-import ctypes
 import os
 import sys
 
@@ -16,7 +15,6 @@ def main():
     import torch
     import farms_mujoco_amd.model as mm
     from farms_mujoco_amd.physics import BatchedPhysics
-    from farms_mujoco_amd import _lib
     from oracle import oracle
     oracle.build()
     os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
@@ -31,13 +29,9 @@ def main():
         d = phys.data
         d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
         q32 = d.qpos.cpu().numpy().astype(np.float64); v32 = d.qvel.cpu().numpy().astype(np.float64)
-        rs = ctypes.c_int32()
-        H = torch.zeros(n, m.nv, 32, device='cuda'); qf = torch.zeros(n, m.nv, device='cuda')
-        c = phys._cdata()
-        _lib.check(phys._lib.fmj_forward_debug(phys._ctx, ctypes.byref(c), 0, H.data_ptr(), ctypes.byref(rs), qf.data_ptr(), None))
+        H, qf = phys.forward_debug()
         torch.cuda.synchronize()
-        rs = rs.value
-        Hrows = H.cpu().numpy().ravel()[:n*m.nv*rs].reshape(n, m.nv, rs)
+        Hrows = H.cpu().numpy()
         xpos = d.xpos.cpu().numpy(); xquat = d.xquat.cpu().numpy(); xipos = d.xipos.cpu().numpy()
         phys.step(1)
         torch.cuda.synchronize()

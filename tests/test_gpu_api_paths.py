@@ -373,7 +373,6 @@ def test_mass_matrix_and_bias_stage(oracle, maker):
     import torch
     import farms_mujoco_amd.model as mm
     from farms_mujoco_amd.physics import BatchedPhysics
-    from farms_mujoco_amd import _lib
     m = getattr(mm, maker)()
     n = 8
     rng = np.random.default_rng(5)
@@ -384,13 +383,9 @@ def test_mass_matrix_and_bias_stage(oracle, maker):
     d = phys.data
     d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
     q32, v32 = _f64(d.qpos), _f64(d.qvel)
-    rs = ctypes.c_int32()
-    H = torch.zeros(n, m.nv, 32, device='cuda'); qf = torch.zeros(n, m.nv, device='cuda')
-    c = phys._cdata()
-    _lib.check(phys._lib.fmj_forward_debug(phys._ctx, ctypes.byref(c), 1, H.data_ptr(), ctypes.byref(rs), qf.data_ptr(), None))
+    H, qf = phys.forward_debug(disable_actuation=True)
     torch.cuda.synchronize()
-    rs = rs.value
-    Hrows = H.cpu().numpy().ravel()[:n*m.nv*rs].reshape(n, m.nv, rs)            # packed [n_envs, nv, rs]
+    Hrows = H.cpu().numpy()                                                     # packed [n_envs, nv, rs]
     depth = np.zeros(m.nv, int)
     for i in range(m.nv):
         depth[i] = 0 if m.dof_parentid[i] < 0 else depth[m.dof_parentid[i]] + 1
@@ -529,6 +524,7 @@ def test_before_step_operator_equals_the_three_operators(oracle):
     xfrc_applied) and walking (rows + contact rows), full rows and links-only rows."""
     import torch
     from farms_mujoco_amd import _lib
+    from farms_mujoco_amd.data import c_rows
     from farms_mujoco_amd.simulation.physics import physics2data
     from farms_mujoco_amd.sensors.sensors import cycontacts2data
     # swimming
@@ -539,10 +535,10 @@ def test_before_step_operator_equals_the_three_operators(oracle):
     s = task.data.sensors
 
     def three(index, links_only):
-        rows = _lib.CRows(); rows.links = s.links.array[index].data_ptr(); rows.joints = s.joints.array[index].data_ptr()
+        rows = c_rows(index, s.links, s.joints)
         c = phys._cdata(); u = task.units.as_c()
         _lib.check(phys._lib.fmj_physics2data(phys._ctx, ctypes.byref(c), ctypes.byref(rows), ctypes.byref(u), int(links_only),
-                                              ctypes.c_void_p(torch.cuda.current_stream(phys.device).cuda_stream)))
+                                              _lib.stream_ptr(phys.device)))
         h.step(index)
     for links_only in (False, True):
         for arr in (s.links.array, s.joints.array, s.xfrc.array):
@@ -570,10 +566,10 @@ def test_before_step_operator_equals_the_three_operators(oracle):
     simw.reset()
     simw.physics.step(30)
     sw = data.sensors
-    rows = _lib.CRows(); rows.links = sw.links.array[2].data_ptr(); rows.joints = sw.joints.array[2].data_ptr()
+    rows = c_rows(2, sw.links, sw.joints)
     c = simw.physics._cdata(); u = simw.task.units.as_c()
     _lib.check(simw.physics._lib.fmj_physics2data(simw.physics._ctx, ctypes.byref(c), ctypes.byref(rows), ctypes.byref(u), 0,
-                                                  ctypes.c_void_p(torch.cuda.current_stream(simw.physics.device).cuda_stream)))
+                                                  _lib.stream_ptr(simw.physics.device)))
     cycontacts2data(physics=simw.physics, iteration=2, data=sw.contacts, geompair2data=simw.task.maps['sensors']['geompair2data'],
                     meters=simw.task.units.meters, newtons=simw.task.units.newtons)
     want = [a[2].clone() for a in (sw.links.array, sw.joints.array, sw.contacts.array)]

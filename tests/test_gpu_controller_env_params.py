@@ -122,7 +122,7 @@ def _launch_through(mode, record=None):
 
     def launch(phys, cd, a, ext):
         assert ext is None
-        stream = ctypes.c_void_p(torch.cuda.current_stream(phys.device).cuda_stream)
+        stream = _lib.stream_ptr(phys.device)
         if mode == 'fmj_step_fused':
             rc = phys._lib.fmj_step_fused(phys._ctx, ctypes.byref(cd), ctypes.byref(a), stream)
         elif mode == 'ext_null':

@@ -127,21 +127,17 @@ def test_stage_outputs_to_the_ulp(oracle, name):
     """fmj_forward_debug: the rows of H = M + diag(armature + h damping) and qfrc_smooth against oracle.forward_debug (the fp32
     kernels' yardstick for this stage is 1e-5 absolute).  Groups: the entries of H of one env; qfrc_smooth of one env."""
     import torch
-    from farms_mujoco_amd import _lib
     m = _make(name)
     n = 4
     qpos, qvel, ctrl, xf, qs = _inputs(m, n, MODELS.index(name))
     phys, ins = _phys(m, n, qpos, qvel, ctrl, xf, qs)
-    rs = ctypes.c_int32()
-    H = torch.zeros(n, m.nv, 64, device='cuda'); qf = torch.zeros(n, m.nv, device='cuda')
-    c = phys._cdata()
-    _lib.check(phys._lib.fmj_forward_debug(phys._ctx, ctypes.byref(c), 0, H.data_ptr(), ctypes.byref(rs), qf.data_ptr(), None))
+    H, qf = phys.forward_debug()
     torch.cuda.synchronize()
-    rs = rs.value
+    rs = H.shape[2]
     depth = dof_depth(m)
     assert rs == (int(depth.max()) + 4)//4*4
-    Hrows = H.cpu().numpy().ravel()[:n*m.nv*rs].reshape(n, m.nv, rs)
-    assert np.all(H.cpu().numpy().ravel()[n*m.nv*rs:] == 0.0)
+    Hrows = H.cpu().numpy()
+    assert H.shape == (n, m.nv, rs) and np.all(H._base.cpu().numpy()[n*m.nv*rs:] == 0.0)
     Href = np.zeros_like(Hrows, dtype=np.float64); qref = np.zeros((n, m.nv))
     for e in range(n):
         o = oracle.forward_debug(m, ins['qpos'][e], ins['qvel'][e], ctrl=ins['ctrl'][e] if m.nu else None, qpos_spring=ins['qpos_spring'][e],

@@ -4,7 +4,6 @@ all three actuator kinds with ctrl and force ranges, external forces) and under 
 yardsticks the project already uses: the fixed bounds of test_random_tree_vs_oracle, 6x the fp32-storage floor per component
 (oracle.fp32_storage, parity_metrics.group_relerr) and the per-stage bounds of test_mass_matrix_and_bias_stage.  What the trees cover
 is checked without a GPU in test_wide_tree_coverage.py."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -123,20 +122,16 @@ def test_wide_mass_matrix_and_bias_stage(oracle, seed, monkeypatch):
     passive - bias + the external forces within 2e-5 of its largest entry (the bounds of test_mass_matrix_and_bias_stage).  Localises a K / C / S / M-phase error to its
     stage: the solve and the rollout amplify it."""
     import torch
-    from farms_mujoco_amd import _lib
     m = shape_tree(seed)
     n = 4
     qpos, qvel, ctrl, xf, qs = _inputs(m, n, seed)
     phys, ins = _wide_phys(m, n, monkeypatch, qpos, qvel, ctrl, xf, qs)
-    rs = ctypes.c_int32()
-    H = torch.zeros(n, m.nv, 64, device='cuda'); qf = torch.zeros(n, m.nv, device='cuda')
-    c = phys._cdata()
-    _lib.check(phys._lib.fmj_forward_debug(phys._ctx, ctypes.byref(c), 1, H.data_ptr(), ctypes.byref(rs), qf.data_ptr(), None))
+    H, qf = phys.forward_debug(disable_actuation=True)
     torch.cuda.synchronize()
-    rs = rs.value
+    rs = H.shape[2]
     assert rs == tree_properties(m)['rs'], (seed, rs)
-    Hrows = H.cpu().numpy().ravel()[:n*m.nv*rs].reshape(n, m.nv, rs)
-    assert np.all(H.cpu().numpy().ravel()[n*m.nv*rs:] == 0.0)                 # nothing written past the packed rows
+    Hrows = H.cpu().numpy()
+    assert H.shape == (n, m.nv, rs) and np.all(H._base.cpu().numpy()[n*m.nv*rs:] == 0.0)      # nothing written past the packed rows
     depth = dof_depth(m)
     worst_M = worst_b = 0.0
     for e in range(n):

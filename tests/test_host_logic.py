@@ -1,9 +1,12 @@
 """ExperimentTask / Simulation sequencing logic (no GPU): iteration counters, ring index, sub-step quirk,
 kwargs strictness — mirrored from reference farms_mujoco/simulation/task.py."""
+import ctypes
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
-from farms_mujoco_amd.simulation.task import ExperimentTask, TaskCallback, duration2nit
+from farms_mujoco_amd.simulation.task import ExperimentTask, SwimmingCallback, TaskCallback, duration2nit
 
 
 class _FakePhysics:
@@ -223,3 +226,99 @@ def test_task_spec_hooks_and_restart_flag():
     assert closed == [1]                                                  # task.py:358-364: the app is closed at the end
     with pytest.raises(AssertionError):
         ExperimentTask(base_link='b', n_iterations=1, timestep=1e-3, restart=True).initialize_episode(_FakePhysics())
+
+
+# ---- what a fused launch is told ----------------------------------------------------------------------------------------------
+
+def _fields(s):
+    """A ctypes struct as a dict: nested structs as dicts, arrays as lists, pointers as integers or None."""
+    get = lambda v: _fields(v) if isinstance(v, ctypes.Structure) else list(v) if isinstance(v, ctypes.Array) else v
+    return {name: get(getattr(s, name)) for name, _ in s._fields_}
+
+
+def _launch_sim(monkeypatch, substeps, controller, callbacks):
+    """A Simulation over stand-ins (constructor bypassed; AnimatData on the CPU, only data_ptr() and stride() are read) whose launches
+    are recorded instead of made: ``(sim, launches)``, a launch = the fields of (CData, CFusedArgs, ext) as _launch_fused got them."""
+    import torch
+    from farms_mujoco_amd import _lib
+    from farms_mujoco_amd.data import AnimatData
+    from farms_mujoco_amd.simulation import simulation
+    from farms_mujoco_amd.swimming.drag import WaterProperties
+    from farms_mujoco_amd.units import SimulationUnitScaling
+    n_envs, nu = 3, 4
+    data = AnimatData(1e-3, 5, n_envs, ['a', 'b', 'c'], ['j0', 'j1'], contacts=[('a', '')] if substeps > 1 else (), device='cpu')
+    swim = SwimmingCallback(None, None)
+    swim.handler = SimpleNamespace(drag=True, buoyancy=False, water=WaterProperties(0.25, 1000.0, [0.5, -1.0, 2.0], 1.5))
+    task = ExperimentTask(base_link='a', n_iterations=7, timestep=1e-3, data=data, controller=controller, callbacks=[swim] + callbacks,
+                          substeps=substeps, buffer_size=5, units=SimulationUnitScaling(meters=2.0, seconds=0.5, kilograms=3.0))
+    phys = SimpleNamespace(n_envs=n_envs, model=SimpleNamespace(nu=nu), device='cpu', precision='fp32', has_constraints=substeps > 1,
+                           data=SimpleNamespace(ctrl=torch.zeros(n_envs, nu), ncon=torch.tensor([1, 4, 4], dtype=torch.int32)),
+                           _cdata=lambda: _lib.CData(*range(101, 116)))
+    sim = simulation.Simulation.__new__(simulation.Simulation)
+    sim.task, sim.physics, sim.order_by_contacts = task, phys, True
+    launches = []
+    monkeypatch.setattr(simulation, '_launch_fused',
+                        lambda phys, cd, a, ext: launches.append((_fields(cd), _fields(a), None if ext is None else _fields(ext))))
+    return sim, launches
+
+
+def test_fused_launch_descriptions(monkeypatch):
+    """Every field of what Simulation.step_fused and Simulation._step_with_controller hand to _launch_fused (simulation._fused_args
+    and what each adds to it), against values written out here from the stand-ins' tensors as the two methods filled them before
+    they shared that function - the fields that stay zero included.  The one-step launches alternate on their one struct: a launch
+    without rows switches off (do_readout = do_drag = rows_ahead = 0) what the launch with rows before it left there, and the water
+    is read again at every launch with rows."""
+    import torch
+    from farms_mujoco_amd import _lib
+    f32 = lambda x: float(np.float32(x))
+    zero = _fields(_lib.CFusedArgs())
+    assert zero['rows_base'] == dict(links=None, joints=None, xfrc=None, contacts=None) and zero['n_iterations'] == 0
+    cdata = _fields(_lib.CData(*range(101, 116)))
+    units = dict(meters=2.0, newtons=24.0, torques=48.0, velocity=4.0, angular_velocity=2.0, kilograms=3.0)
+    water = lambda vel: dict(surface=0.25, density=1000.0, viscosity=1.5, velocity=[f32(v) for v in vel], gravity=f32(-9.81), use_buoyancy=0)
+
+    # a chunk: sub-steps, a sub-step callback, a contact sensor, a swimming callback, a controller that hands over a ctrl tape
+    class Sub(TaskCallback):
+        fusable = True
+    tape = torch.zeros(8, 3, 4)
+    sim, launches = _launch_sim(monkeypatch, 2, SimpleNamespace(fusable=True, tape=True, ctrl_tape=lambda n: tape[:n]), [Sub(substep=True)])
+    s, task = sim.task.data.sensors, sim.task
+    task.sim_iteration, task.iteration = 8, 4
+    assert sim.step_fused(5) == 3 and (task.sim_iteration, task.iteration, sim._rows_for) == (14, 7, -1)      # 7 iterations in all
+    assert sim._env_order.tolist() == [1, 2, 0] and sim._env_order.dtype == torch.int32
+    (cd, a, ext), = launches
+    assert ext is None and cd == dict(cdata, ctrl=tape.data_ptr())
+    assert a == dict(zero, n_steps=3, iteration0=4, buffer_size=5, do_readout=1, do_drag=1, controller=0, ctrl_step_stride=12,
+                     row_stride_links=s.links.array.stride(0), row_stride_joints=s.joints.array.stride(0),
+                     row_stride_xfrc=s.xfrc.array.stride(0), row_stride_contacts=s.contacts.array.stride(0),
+                     rows_base=dict(links=s.links.array.data_ptr(), joints=s.joints.array.data_ptr(), xfrc=s.xfrc.array.data_ptr(),
+                                    contacts=s.contacts.array.data_ptr()),
+                     water=water([0.5, -1.0, 2.0]), units=units, env_order=sim._env_order.data_ptr(), substeps=2, substep_links=1,
+                     n_iterations=7)
+    assert (a['row_stride_links'], a['row_stride_contacts']) == (3*3*s.links.array.shape[3], 3*1*s.contacts.array.shape[3])
+
+    # one step with the wave controller (per-env phase lags: an ext), without and with the next iteration's rows
+    wave = SimpleNamespace(fusable=True, frequency=1.5, amplitude=torch.zeros(4), phase_lag=torch.zeros(3, 4), env_phase=torch.zeros(3))
+    sim, launches = _launch_sim(monkeypatch, 1, wave, [_Recorder()])
+    s, task, h = sim.task.data.sensors, sim.task, sim.task._callbacks[0].handler
+    task.sim_iteration = task.iteration = 3
+    want_ext = dict(size=ctypes.sizeof(_lib.CFusedExt), reserved=0, wave_frequency_env=None, wave_amplitude_env_stride=0,
+                    wave_phase_lag_env_stride=4)
+    plain = dict(zero, n_steps=1, iteration0=3, buffer_size=5, controller=1, units=units, substeps=1, ctrl_out=sim.physics.data.ctrl.data_ptr(),
+                 wave=dict(amplitude=wave.amplitude.data_ptr(), phase_lag=wave.phase_lag.data_ptr(), env_phase=wave.env_phase.data_ptr(),
+                           frequency=1.5))
+    rows = dict(row_stride_links=s.links.array.stride(0), row_stride_joints=s.joints.array.stride(0), row_stride_xfrc=s.xfrc.array.stride(0),
+                rows_base=dict(links=s.links.array.data_ptr(), joints=s.joints.array.data_ptr(), xfrc=s.xfrc.array.data_ptr(), contacts=None))
+    sim._step_with_controller(rows_ahead=False)
+    assert launches[-1] == (cdata, plain, want_ext)                        # a new struct: no rows, no strides, no water
+    sim._step_with_controller(rows_ahead=True)
+    ahead = dict(plain, do_readout=1, do_drag=1, rows_ahead=1, water=water([0.5, -1.0, 2.0]), **rows)
+    assert launches[-1] == (cdata, ahead, want_ext)
+    task.iteration = 4
+    h.water.set_velocity(0.0, 0.25, 0.0)
+    sim._step_with_controller(rows_ahead=False)                            # the rows and the water of the launch before: switched off
+    assert launches[-1] == (cdata, dict(ahead, iteration0=4, do_readout=0, do_drag=0, rows_ahead=0), want_ext)
+    h.drag = False
+    sim._step_with_controller(rows_ahead=True)
+    assert launches[-1] == (cdata, dict(ahead, iteration0=4, do_drag=0, water=water([0.0, 0.25, 0.0])), want_ext)
+    assert sim._step_args is not None and len(launches) == 4
