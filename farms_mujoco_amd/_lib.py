@@ -72,10 +72,11 @@ BEFORE_ROWS, BEFORE_LINKS_ONLY, BEFORE_CONTACTS, BEFORE_DRAG = 1, 2, 4, 8      #
 
 # every symbol include/fmj.h declares: name -> (restype, argtypes)
 class CCreateOptions(ctypes.Structure):
-    _fields_ = [('size', ctypes.c_int32), ('precision', ctypes.c_int32)]
+    _fields_ = [('size', ctypes.c_int32), ('precision', ctypes.c_int32), ('kernel_flags', ctypes.c_int32), ('dual_wps', ctypes.c_int32)]
 
 
 PRECISIONS = {'fp32': 0, 'fp64': 1}      # FMJ_PRECISION_* of include/fmj.h
+KERNEL_TWO_WAVE, KERNEL_ONE_ENV_PER_WAVE, KERNEL_NO_LEAN, KERNEL_NO_PRIO = 1, 2, 4, 8      # FMJ_KERNEL_* of include/fmj.h ("Kernel selection" at fmj_create_ex)
 
 
 class CCpgDesc(ctypes.Structure):

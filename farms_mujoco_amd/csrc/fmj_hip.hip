@@ -221,7 +221,7 @@ enum StepPath {
   PATH_ONE_ENV,         // one wave per env: the one-env kernel (fmj_ctx::variant)
   PATH_TWO_ENV,         // integrating steps: two envs per wave (fmj_dual2.inc); fmj_forward: the one-env kernel
   PATH_CONS2_ONE_ENV,   // integrating steps: the two-env constraint kernel (fmj_cons2.inc), then the one-env kernel for the envs it hands over
-  PATH_TWO_WAVE,        // one workgroup of two waves per env (fmj_wide.inc), fmj_forward included: nbody or nv above 64, or FMJ_WIDE=1
+  PATH_TWO_WAVE,        // one workgroup of two waves per env (fmj_wide.inc), fmj_forward included: nbody or nv above 64, or on request (fmj.h, "Kernel selection")
   PATH_F64,             // the fp64 step kernel (fmj_f64.inc), fmj_forward included: fmj_create_ex with FMJ_PRECISION_F64
 };
 
@@ -231,9 +231,9 @@ struct fmj_ctx {
   std::vector<void*> allocs;  // device memory of the context (fmj_destroy)
   StepPath path = PATH_ONE_ENV;
   StepVariant variant = SV_PLAIN;        // of the one-env kernel
-  int dual_wps = 4;           // waves per SIMD the dual2 build is registered for: 2, 3 or 4, the most the batch fills (FMJ_WPS overrides)
-  int dual_lean = 1;          // fused launches of the flagship shape run the LEAN dual2 build (FMJ_DUAL_LEAN=0: always the generic one)
-  int dual_prio = 1;          // fused dual2 launches let the waves of a SIMD take turns at issue priority (FMJ_DUAL_PRIO=0: priorities left alone)
+  int dual_wps = 4;           // waves per SIMD the dual2 build is registered for: 2, 3 or 4, the most the batch fills, or the tier asked for (fmj.h, "Kernel selection")
+  int dual_lean = 1;          // fused launches of the flagship shape run the LEAN dual2 build (0: always the generic one; as asked for)
+  int dual_prio = 1;          // fused dual2 launches let the waves of a SIMD take turns at issue priority (0: priorities left alone; as asked for)
   int dual_last = FMJ_DUAL_BUILD_NONE;      // FMJ_DUAL_BUILD_* of the last dual2 launch (fmj_dual_build_info)
   size_t lds_bytes = 0, lds_bytes_dual2 = 0, lds_bytes_cons2 = 0, lds_bytes_wide = 0;
   int* d_resume = nullptr;    // [n_envs] hand-over of the two-env constraint kernel to the one-env kernel
@@ -1913,10 +1913,39 @@ static int sync_tables(fmj_ctx* c) {
   return FMJ_OK;
 }
 
-// ---- fmj_create, stage 1: every check of the model (host only, before any device call) and the facts the later stages build on
+// ---- fmj_create, stage 0: what the caller asks of the kernel selection (fmj.h, "Kernel selection" at fmj_create_ex).  The stages
+// below apply each request where the model allows it and ignore it where it does not.
+struct KernelChoice {
+  bool two_wave = false;           // the two-wave kernel on a model that fits one wave
+  bool one_env_per_wave = false;   // one env per wave where two would fit
+  int wps = 0;                     // register tier of the two-env kernel: 2, 3 or 4; 0 = from the batch size
+  bool lean = true, prio = true;   // the LEAN build for fused launches of the flagship shape; the issue-priority policy
+};
+
+// The only reader of the environment in the library.  A caller who passes the kernel fields has said everything; the FMJ_* variables
+// speak for callers who pass none (fmj_create, opts == NULL, the 8-byte struct).
+static int resolve_kernel_choice(const fmj_create_options* opts, KernelChoice* K) {
+  if (opts && opts->size == (int32_t)sizeof(fmj_create_options)) {
+    const int32_t f = opts->kernel_flags, w = opts->dual_wps;
+    if (f & ~(int32_t)FMJ_KERNEL_ALL) return set_err(FMJ_ERR_ARG, "fmj_create_ex: unknown bits in fmj_create_options.kernel_flags");
+    if (w != 0 && w != 2 && w != 3 && w != 4) return set_err(FMJ_ERR_ARG, "fmj_create_ex: fmj_create_options.dual_wps must be 0, 2, 3 or 4");
+    K->two_wave = f & FMJ_KERNEL_TWO_WAVE; K->one_env_per_wave = f & FMJ_KERNEL_ONE_ENV_PER_WAVE; K->wps = w;
+    K->lean = !(f & FMJ_KERNEL_NO_LEAN); K->prio = !(f & FMJ_KERNEL_NO_PRIO);
+    return FMJ_OK;
+  }
+  const auto first = [](const char* name) { const char* v = getenv(name); return v ? v[0] : '\0'; };
+  K->two_wave = first("FMJ_WIDE") == '1'; K->one_env_per_wave = first("FMJ_DUAL") == '0';
+  const char w = first("FMJ_WPS");
+  K->wps = (w == '2' || w == '3' || w == '4') ? w - '0' : 0;
+  K->lean = first("FMJ_DUAL_LEAN") != '0'; K->prio = first("FMJ_DUAL_PRIO") != '0';
+  return FMJ_OK;
+}
+
+// ---- stage 1: every check of the model (host only, before any device call) and the facts the later stages build on
 struct ModelFacts {
+  KernelChoice kernel;        // set by fmj_create_ex before check_model
   int cons = 0, big = 0;      // limits, contacts or pairs (the constraint kernels); nbody or nv above 64 (past one wavefront)
-  int wide = 0;               // every step launch runs the two-wave kernel (fmj_wide.inc): big, or FMJ_WIDE=1
+  int wide = 0;               // every step launch runs the two-wave kernel (fmj_wide.inc): big, or kernel.two_wave
   int nplane = 0, n_hfield = 0, any_mesh = 0, any_box = 0, any_polypair = 0;     // nplane counts the ground geoms: planes and the heightfield
   bool dual_instead = false;  // Newton / CG requested, solved on the dual problem (PGS)
   std::vector<int> bdepth, subsize, ddepth, dsub;      // body / dof depth and subtree size
@@ -2058,9 +2087,8 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   while ((1 << F->jump_rounds) < max_bdepth) F->jump_rounds++;
   F->anc_stride = r4(F->jump_rounds > 4 ? F->jump_rounds : 4);
   F->rs = r4(max_ddepth + 1);
-  // FMJ_WIDE=1: the two-wave kernel on any unconstrained model (tests hold it against the one-wave kernel; scripts measure the second wave)
-  const char* wenv = getenv("FMJ_WIDE");
-  F->wide = precision == FMJ_PRECISION_F32 && (big || (!cons && m->integrator != FMJ_INT_RK4 && wenv && wenv[0] == '1'));
+  // on request, the two-wave kernel on any unconstrained model (tests hold it against the one-wave kernel; scripts measure the second wave)
+  F->wide = precision == FMJ_PRECISION_F32 && (big || (!cons && m->integrator != FMJ_INT_RK4 && F->kernel.two_wave));
   if (F->wide) F->rs = F->rs <= 32 ? 32 : 64;     // the row lengths the two-wave kernel is instantiated at
   F->max_contacts = cons ? (m->max_contacts > 0 ? m->max_contacts : 1) : 0;
   int nlimj = 0; for (int j = 0; j < nj; j++) nlimj += (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE);
@@ -2123,9 +2151,8 @@ static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) 
   D.maxdep1 = F.max_ddepth;
   // ---- two envs per wave: bodies and the dofs minus a free root's translational dofs must fit 32 lanes, and a row 32 floats
   const int t0 = D.root_free ? 3 : 0;
-  const char* envv = getenv("FMJ_DUAL");
   D.dual_t0 = t0;
-  const bool halves_ok = nb <= 32 && nv - t0 <= 32 && D.rs <= FMJ_MAXD && !(envv && envv[0] == '0');
+  const bool halves_ok = nb <= 32 && nv - t0 <= 32 && D.rs <= FMJ_MAXD && !F.kernel.one_env_per_wave;
   D.dual_ok = !cons && halves_ok && !c->rk4 && !F.wide;      // RK4: four forward launches of the one-env kernel per step, no fused launch
   // the two-env constraint kernel covers what BASELINE configs[3] needs: limits + ground contacts of sphere / capsule / box / cylinder
   // geoms on ONE ground geom, pyramidal cone, PGS; everything else (pairs, meshes, Newton / CG, the elliptic cone) keeps the one-env kernel
@@ -2473,12 +2500,9 @@ static int choose_path(fmj_ctx* c, const ModelFacts& F) {
     const int waves = (c->n_envs + 1) / 2;
     // the build registered for the waves per SIMD the batch can fill: 2 (256 registers: model constants resident), 3 (168) or 4 (128)
     c->dual_wps = waves <= 2 * 4 * n_cu ? 2 : (waves <= 3 * 4 * n_cu ? 3 : 4);
-    const char* w = getenv("FMJ_WPS");
-    if (w && (w[0] == '2' || w[0] == '3' || w[0] == '4')) c->dual_wps = w[0] - '0';
-    const char* l = getenv("FMJ_DUAL_LEAN");      // 0: every launch runs the generic build (tests and A/B runs compare the two)
-    if (l && l[0] == '0') c->dual_lean = 0;
-    const char* p = getenv("FMJ_DUAL_PRIO");      // 0: no s_setprio in any launch (tests and A/B runs compare the two)
-    if (p && p[0] == '0') c->dual_prio = 0;
+    if (F.kernel.wps) c->dual_wps = F.kernel.wps;
+    c->dual_lean = F.kernel.lean;      // off: every launch runs the generic build (tests and A/B runs compare the two)
+    c->dual_prio = F.kernel.prio;      // off: no s_setprio in any launch (tests and A/B runs compare the two)
   }
   c->path = F.wide ? PATH_TWO_WAVE : D.dual_ok ? PATH_TWO_ENV : D.cons2_ok ? PATH_CONS2_ONE_ENV : PATH_ONE_ENV;
   c->variant = one_env_variant(D);
@@ -2586,10 +2610,12 @@ int fmj_precision(const fmj_ctx* c) { return c ? c->precision : FMJ_PRECISION_F3
 int fmj_create_ex(const fmj_model* m, int32_t n_envs, int32_t device, const fmj_create_options* opts, fmj_ctx** out) {
   if (!m || !out || n_envs <= 0) return set_err(FMJ_ERR_ARG, "fmj_create: NULL model/out or n_envs <= 0");
   *out = nullptr;
-  if (opts && opts->size != (int32_t)sizeof(fmj_create_options)) return set_err(FMJ_ERR_ARG, "fmj_create_ex: fmj_create_options.size is not sizeof(fmj_create_options)");
+  if (opts && opts->size != 8 && opts->size != (int32_t)sizeof(fmj_create_options))
+    return set_err(FMJ_ERR_ARG, "fmj_create_ex: fmj_create_options.size is neither sizeof(fmj_create_options) nor 8 (the struct before the kernel fields)");
   const int precision = opts ? opts->precision : FMJ_PRECISION_F32;
   if (precision != FMJ_PRECISION_F32 && precision != FMJ_PRECISION_F64) return set_err(FMJ_ERR_ARG, "fmj_create_ex: precision must be FMJ_PRECISION_F32 or FMJ_PRECISION_F64");
   ModelFacts F;
+  if (int rc = resolve_kernel_choice(opts, &F.kernel)) return rc;
   if (int rc = check_model(m, &F, precision)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_err(FMJ_ERR_NODEVICE, "fmj_create: no HIP device visible");

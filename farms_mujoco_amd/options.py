@@ -42,6 +42,28 @@ class SimulationOptions:
                             for k, v in vars(self).items()}, f)
 
 
+class KernelOptions:
+    """Which step kernels a context runs, among those its model is eligible for (include/fmj.h, "Kernel selection" at fmj_create_ex).
+    The defaults are what the library chooses on its own; a setting that does not apply to the model is ignored, and
+    ``BatchedPhysics.kernel_info()`` reports what runs.  ``two_wave``: the two-wave kernel on a model that fits one wave.
+    ``two_env=False``: one environment per wave where two would fit.  ``wps``: register tier of the two-env kernel, 2, 3 or 4 waves
+    per SIMD (None: from the batch size).  ``lean=False``: fused launches always run the generic two-env build.  ``prio=False``: no
+    issue-priority policy."""
+
+    def __init__(self, **kwargs):
+        self.two_wave = bool(kwargs.pop('two_wave', False))
+        self.two_env = bool(kwargs.pop('two_env', True))
+        self.wps = kwargs.pop('wps', None)
+        self.lean = bool(kwargs.pop('lean', True))
+        self.prio = bool(kwargs.pop('prio', True))
+        assert not kwargs, kwargs
+        if self.wps not in (None, 2, 3, 4):
+            raise ValueError(f'wps must be None, 2, 3 or 4, not {self.wps!r}')
+
+    def __repr__(self):
+        return 'KernelOptions(%s)' % ', '.join(f'{k}={v!r}' for k, v in vars(self).items())
+
+
 class WaterOptions:
     """ArenaOptions.water (reference drag.pyx:338-350, mjcf.py:1208-1224)."""
 

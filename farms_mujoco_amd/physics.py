@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .model import Model, JNT_FREE
+from .options import KernelOptions
 
 
 class PhysicsError(RuntimeError):
@@ -39,11 +40,14 @@ class _MjData(SimpleNamespace):
 class BatchedPhysics:
     """Device-resident mjData for ``n_envs`` copies of one model + the HIP step context."""
 
-    def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32'):
+    def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None):
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
-        # tensors of physics.data stay fp32
+        # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
+        # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
         if precision not in _lib.PRECISIONS:
             raise ValueError(f'precision must be one of {sorted(_lib.PRECISIONS)}, not {precision!r}')
+        if kernel is not None and not isinstance(kernel, KernelOptions):
+            raise TypeError(f'kernel must be a KernelOptions or None, not {kernel!r}')
         if not torch.cuda.is_available():
             raise _lib.FmjError('BatchedPhysics needs a GPU (torch.cuda.is_available() is False); '
                                 'there is no CPU fallback for the product path.')
@@ -53,15 +57,22 @@ class BatchedPhysics:
         self._lib = _lib.load()
         self._cmodel = model.as_c()
         ctx = ctypes.c_void_p()
-        if precision == 'fp32':
+        if precision == 'fp32' and kernel is None:
             _lib.check(self._lib.fmj_create(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
                                             ctypes.byref(ctx)))
         else:
+            asked = f'precision={precision!r}' if kernel is None else f'kernel={kernel!r}'
             if not _lib.has('fmj_create_ex'):      # an A/B base build (FMJ_SO)
-                raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex: precision=%r needs a current build' % precision)
-            opts = _lib.CCreateOptions(ctypes.sizeof(_lib.CCreateOptions), _lib.PRECISIONS[precision])
-            _lib.check(self._lib.fmj_create_ex(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
-                                               ctypes.byref(opts), ctypes.byref(ctx)))
+                raise _lib.FmjError(f'this libfmj_hip.so has no fmj_create_ex: {asked} needs a current build')
+            k = kernel or KernelOptions()
+            flags = (k.two_wave * _lib.KERNEL_TWO_WAVE | (not k.two_env) * _lib.KERNEL_ONE_ENV_PER_WAVE |
+                     (not k.lean) * _lib.KERNEL_NO_LEAN | (not k.prio) * _lib.KERNEL_NO_PRIO)
+            opts = _lib.CCreateOptions(ctypes.sizeof(_lib.CCreateOptions), _lib.PRECISIONS[precision], flags, k.wps or 0)
+            rc = self._lib.fmj_create_ex(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
+                                         ctypes.byref(opts), ctypes.byref(ctx))
+            if rc and b'fmj_create_options.size' in self._lib.fmj_last_error():      # an A/B base build from before the kernel fields
+                raise _lib.FmjError(f'this libfmj_hip.so has no kernel fields in fmj_create_options: {asked} needs a current build')
+            _lib.check(rc)
         self._ctx = ctx
         code = self._lib.fmj_precision(self._ctx) if _lib.has('fmj_precision') else 0
         self.precision = {v: k for k, v in _lib.PRECISIONS.items()}[code]      # what the context reports

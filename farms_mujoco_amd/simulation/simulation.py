@@ -98,7 +98,8 @@ class Simulation:
 
     ``mjcf_model`` is a compiled :class:`~farms_mujoco_amd.model.Model` (the dm_control MJCF element tree is
     replaced).  Extra kwargs: ``n_envs``, ``device``, ``precision`` ('fp32' | 'fp64': the step kernel's arithmetic,
-    :class:`~farms_mujoco_amd.physics.BatchedPhysics`).  ``legacy_step`` is accepted for signature
+    :class:`~farms_mujoco_amd.physics.BatchedPhysics`), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
+    kernels this simulation's context runs).  ``legacy_step`` is accepted for signature
     compatibility; the step is always the full mj_step (legacy_step=False semantics, simulation.py:36-37).
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here
     advances exactly ``n_iterations * substeps`` physics steps after an explicit :meth:`reset`.
@@ -119,7 +120,7 @@ class Simulation:
         self.pause = not self.options.play
         n_envs = kwargs.pop('n_envs', 1)
         device = kwargs.pop('device', 'cuda:0')
-        self.physics = BatchedPhysics(mjcf_model, n_envs, device, precision=kwargs.pop('precision', 'fp32'))
+        self.physics = BatchedPhysics(mjcf_model, n_envs, device, precision=kwargs.pop('precision', 'fp32'), kernel=kwargs.pop('kernel', None))
         self.handle_exceptions = kwargs.pop('handle_exceptions', False)
         # dm_control raises PhysicsError inside the offending step; here the device freezes the offending env at that
         # step (include/fmj.h) and the host looks at the status words every `check_every` steps (one sync each)

@@ -291,8 +291,8 @@ typedef struct fmj_ctx fmj_ctx;   /* opaque */
  * builds the level / ancestor tables, uploads the fp32 device copy. `device` = HIP ordinal.
  * Model size: nbody <= 128 and nv <= 128, a dof chain of at most 64 (32 with limits / contacts).  A model past 64 bodies or dofs
  * steps on one workgroup of two wavefronts per environment and must have no limits, contacts or pairs and not use RK4; these
- * are FMJ_ERR_UNSUPPORTED with the limit named in fmj_last_error().  FMJ_WIDE=1 in the environment at fmj_create runs the
- * two-wave kernel on any unconstrained, non-RK4 model (to compare it with the one-wave kernels). */
+ * are FMJ_ERR_UNSUPPORTED with the limit named in fmj_last_error().  Which kernels a context runs within those limits
+ * can be chosen per context: "Kernel selection" at fmj_create_ex. */
 int fmj_create(const fmj_model* model, int32_t n_envs, int32_t device, fmj_ctx** out);
 /* fmj_create with options (additive: FMJ_ABI_VERSION stays 6).  opts == NULL is fmj_create: the same path, the same bits.
  * precision = FMJ_PRECISION_F64 selects the fp64 step kernel: every stage of the unconstrained step in double precision, from a second,
@@ -304,12 +304,27 @@ int fmj_create(const fmj_model* model, int32_t n_envs, int32_t device, fmj_ctx**
  * qfrc_smooth rounded to fp32 on store), with the Euler and implicitfast integrators.  Refused with FMJ_ERR_UNSUPPORTED and a message
  * containing "fp64": a model with limits, contacts or pairs, the RK4 integrator (both at fmj_create_ex, before the device lookup) and
  * fmj_step_fused (write the rows with fmj_before_step, as with RK4).  The standalone operators (fmj_before_step, fmj_physics2data,
- * fmj_drag, fmj_contacts2data) work unchanged, in fp32, from the fmj_data fields.  An unknown precision or a size other than
- * sizeof(fmj_create_options) is FMJ_ERR_ARG. */
+ * fmj_drag, fmj_contacts2data) work unchanged, in fp32, from the fmj_data fields.  An unknown precision is FMJ_ERR_ARG.
+ * size is sizeof(fmj_create_options), or 8 for the struct as it was before the kernel fields (size and precision only); any other
+ * size is FMJ_ERR_ARG.
+ * Kernel selection.  kernel_flags and dual_wps choose, for this context, among the step kernels the model is eligible for; zero in
+ * both is what fmj_create chooses.  FMJ_KERNEL_TWO_WAVE: the two-wave kernel on a model that fits one wave.  FMJ_KERNEL_ONE_ENV_PER_WAVE: one environment
+ * per wave where two would fit, with and without constraints (TWO_WAVE wins where both are set).  FMJ_KERNEL_NO_LEAN: fused launches
+ * always run the generic build of the two-env kernel.  FMJ_KERNEL_NO_PRIO: no issue-priority policy in the two-env kernel.  dual_wps:
+ * the register tier of the two-env kernel, 2, 3 or 4 waves per SIMD, 0 = from the batch size.  A request that does not apply to the
+ * model (TWO_WAVE with constraints, RK4 or fp64, say) is ignored; fmj_kernel_info and fmj_dual_build_info report what runs.  An
+ * unknown flag bit or another dual_wps is FMJ_ERR_ARG, decided before the device lookup.  A caller who passes these fields (opts
+ * non-NULL, size covering them) has said everything: the environment is not consulted for that context, not even for fields left 0.
+ * For callers who pass none - fmj_create, opts == NULL, size 8 - five variables in the process environment at the call say the
+ * same: FMJ_WIDE=1 (TWO_WAVE), FMJ_DUAL=0 (ONE_ENV_PER_WAVE), FMJ_DUAL_LEAN=0 (NO_LEAN), FMJ_DUAL_PRIO=0 (NO_PRIO), FMJ_WPS=2|3|4
+ * (dual_wps; any other value is ignored).  The library reads the environment nowhere else. */
 enum { FMJ_PRECISION_F32 = 0, FMJ_PRECISION_F64 = 1 };
+enum { FMJ_KERNEL_TWO_WAVE = 1, FMJ_KERNEL_ONE_ENV_PER_WAVE = 2, FMJ_KERNEL_NO_LEAN = 4, FMJ_KERNEL_NO_PRIO = 8, FMJ_KERNEL_ALL = 15 };
 typedef struct fmj_create_options {
-  int32_t size;        /* = sizeof(fmj_create_options), for later growth */
-  int32_t precision;   /* FMJ_PRECISION_* */
+  int32_t size;           /* = sizeof(fmj_create_options); 8 = precision only */
+  int32_t precision;      /* FMJ_PRECISION_* */
+  int32_t kernel_flags;   /* FMJ_KERNEL_*, or 0 */
+  int32_t dual_wps;       /* 0, 2, 3 or 4 */
 } fmj_create_options;
 int fmj_create_ex(const fmj_model* model, int32_t n_envs, int32_t device, const fmj_create_options* opts, fmj_ctx** out);
 int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
@@ -318,15 +333,15 @@ const char* fmj_last_error(void);
 int fmj_abi_version(void);
 int fmj_get_sensor_layout(const fmj_ctx* ctx, fmj_sensor_layout_t* out);
 /* LDS bytes / VGPR-independent facts the host needs for reporting; threads_per_env is 32 (two envs per wave), 64 (one wave) or
- * 128 (two waves: models past 64 bodies / dofs, or FMJ_WIDE=1; always for an fp64 context, whose LDS holds the rows of H as doubles) */
+ * 128 (two waves: models past 64 bodies / dofs, or on request: "Kernel selection" at fmj_create_ex; always for an fp64 context, whose LDS holds the rows of H as doubles) */
 int fmj_kernel_info(const fmj_ctx* ctx, int32_t* lds_bytes_per_env, int32_t* threads_per_env);
 /* The build of the two-env step kernel a context runs (all zero / NONE for a context on another kernel).  *waves_per_simd: the register
- * tier, 2, 3 or 4 (chosen from the batch size at fmj_create; FMJ_WPS=2|3|4 overrides).  *lean_enabled: 1 when fmj_step_fused launches of
+ * tier, 2, 3 or 4 (chosen from the batch size at fmj_create unless asked for: "Kernel selection" at fmj_create_ex).  *lean_enabled: 1 when fmj_step_fused launches of
  * the shape of a fused run - wave controller, readout and drag on, substeps = 1, no rows_ahead, no joint stiffness, Euler - run the
- * build with those options folded in at compile time (bitwise the same results; FMJ_DUAL_LEAN=0 in the environment at fmj_create turns
+ * build with those options folded in at compile time (bitwise the same results; FMJ_KERNEL_NO_LEAN turns
  * it off, for comparisons).  *last_launch: the FMJ_DUAL_BUILD_* the last step launch of the context ran.  *prio_enabled (appended; the
  * parameters in front of it are as before): 1 when the fused launches of the kernel let the waves that share a SIMD take turns at
- * issue priority (s_setprio; scheduling only, bitwise the same results; FMJ_DUAL_PRIO=0 in the environment at fmj_create turns it off); 0 for a
+ * issue priority (s_setprio; scheduling only, bitwise the same results; FMJ_KERNEL_NO_PRIO turns it off); 0 for a
  * register tier whose builds do not carry the policy (today waves_per_simd = 4).  *prio_policy (appended in the same way): which
  * s_setprio the waves of such a launch execute at which point of a step, FMJ_DUAL_PRIO_PHASE of csrc/fmj_dual2.inc: 8 = the waves swap
  * levels 1 / 0 at the top of every step and both run at level 2 from the factorisation rounds to the end of the step, 1 = the swap

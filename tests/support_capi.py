@@ -11,6 +11,10 @@ F32, F64 = 0, 1                                                   # FMJ_PRECISIO
 
 def lib():
     """The ctypes mirror module and the loaded library."""
+    try:
+        import torch  # noqa: F401  (before the library, as in the package: loaded after it, torch and the library each find no device once the other has looked)
+    except Exception:
+        pass
     from farms_mujoco_amd import _lib
     if not os.path.exists(_lib.SO_PATH):
         pytest.skip('libfmj_hip.so not built')
@@ -35,11 +39,11 @@ def create(m):
     return rc, so.fmj_last_error().decode()
 
 
-def create_ex(m, precision=F64, size=None):
+def create_ex(m, precision=F64, size=None, kernel_flags=0, dual_wps=0):
     """fmj_create_ex(m, 4 envs, options) and destroy: the return code, the message and the precision the context reports."""
     L, so = lib()
     c = m.as_c(); ctx = ctypes.c_void_p()
-    opts = L.CCreateOptions(ctypes.sizeof(L.CCreateOptions) if size is None else size, precision)
+    opts = L.CCreateOptions(ctypes.sizeof(L.CCreateOptions) if size is None else size, precision, kernel_flags, dual_wps)
     rc = so.fmj_create_ex(ctypes.byref(c), 4, 0, ctypes.byref(opts), ctypes.byref(ctx))
     prec = None
     if rc == 0:

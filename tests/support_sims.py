@@ -131,6 +131,33 @@ def outputs(sim, fields):
     return out
 
 
+def dual2_swim(n_envs, n_iterations, ring, kernel):
+    """The swimming workload of the two-env kernel's A/B tests, its context created with ``kernel`` (a KernelOptions)."""
+    return swim_sim(n_envs, n_iterations, ring, water_kwargs=dict(height=-0.11, velocity=[0.03, 0.0, -0.01]), kernel=kernel)[0]      # the surface cuts the animal, a current
+
+
+def dual2_finish(sim, fused=True):
+    """Run a dual2_swim simulation - one fused launch, or the per-iteration host path (one-step launches with rows_ahead: the generic
+    build, whose every launch sets the priority at its step 0).  Returns its outputs, the context's kernel_info after the run and, for
+    the host path, the build every single launch ran."""
+    launches = set()
+    if fused:
+        sim.run(fused=True)
+    else:
+        for _ in range(sim.options.n_iterations):
+            sim._env_step()
+            launches.add(sim.physics.kernel_info()['dual_last_launch'])
+        sim.physics.check_invalid_state()
+    out = outputs(sim, ('qpos', 'qvel', 'sensordata', 'xpos', 'xquat'))
+    assert {'links', 'joints', 'xfrc'} <= set(out)
+    assert int(sim.physics.data.status.abs().sum()) == 0
+    return out, sim.physics.kernel_info(), launches
+
+
+def dual2_run(n_envs, n_iterations, ring, kernel, fused=True):
+    return dual2_finish(dual2_swim(n_envs, n_iterations, ring, kernel), fused)
+
+
 def env_of(out, e):
     """Env ``e`` of an outputs() dict (the ring-buffer arrays carry the env in their second axis)."""
     return {k: (v[:, e] if k in ('links', 'joints', 'xfrc', 'contacts') else v[e]) for k, v in out.items()}
@@ -143,9 +170,9 @@ def assert_bitwise(a, b, what):
         assert np.array_equal(a[k], b[k]), (what, k)
 
 
-def check_random_tree_vs_oracle(oracle, seed, threads_per_env):
-    """The assertions of test_random_tree_vs_oracle on random_tree(seed), run in the kernel of ``threads_per_env`` lanes per env (the
-    environment variables read at fmj_create choose it)."""
+def check_random_tree_vs_oracle(oracle, seed, threads_per_env, kernel):
+    """The assertions of test_random_tree_vs_oracle on random_tree(seed), run in the kernel of ``threads_per_env`` lanes per env, which
+    ``kernel`` (a KernelOptions) chooses."""
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
     m = random_tree(seed)
@@ -161,7 +188,7 @@ def check_random_tree_vs_oracle(oracle, seed, threads_per_env):
     ctrl = rng.uniform(-0.6, 0.6, (n, max(m.nu, 1)))[:, :m.nu]
     xf = rng.normal(size=(n, m.nbody, 6))*0.05; xf[:, 0] = 0
     qs = np.tile(m.qpos_spring, (n, 1)) + rng.uniform(-0.1, 0.1, (n, m.nq))
-    phys = BatchedPhysics(m, n)
+    phys = BatchedPhysics(m, n, kernel=kernel)
     assert phys.kernel_info()['threads_per_env'] == threads_per_env
     d = phys.data
     f32 = lambda a: torch.as_tensor(a, dtype=torch.float32)

@@ -695,12 +695,13 @@ def test_mesh_on_heightfield_and_fused_rows(oracle):
     assert _relerr(d.qpos.cpu().numpy(), ref['qpos']) < 2e-3
 
 
-def test_two_env_kernel_modes_do_not_depend_on_the_partner(oracle, monkeypatch):
+def test_two_env_kernel_modes_do_not_depend_on_the_partner(oracle):
     """The two-env constraint kernel (fmj_cons2.inc, round 4): what an env computes depends neither on the mode its rows were solved
     in - PAIR (both envs of the wave have <= 32 rows: solved at once), SOLO (one has 33..64: one after the other) - nor on the env it
     shares its wave with; an env with more than 64 rows retires from the wave ALONE and is finished by the one-env kernel, bitwise
-    as if that kernel had stepped it from the start (FMJ_DUAL=0).  All of it within tolerance of the oracle."""
+    as if that kernel had stepped it from the start (KernelOptions(two_env=False)).  All of it within tolerance of the oracle."""
     import torch
+    from farms_mujoco_amd.options import KernelOptions
     from farms_mujoco_amd.physics import BatchedPhysics
     m = _walker()
     rng = np.random.default_rng(11)
@@ -719,11 +720,10 @@ def test_two_env_kernel_modes_do_not_depend_on_the_partner(oracle, monkeypatch):
     assert len(light) == 2 and len(medium) == 2 and len(heavy) == 1, nefc
     L, L2, Md, Md2, Hv = light[0], light[1], medium[0], medium[1], heavy[0]
     T = 25
-    import os
 
-    def run(qs):
-        phys = BatchedPhysics(m, len(qs))
-        assert phys.kernel_info()['threads_per_env'] == (32 if os.environ.get('FMJ_DUAL', '1') != '0' else 64)
+    def run(qs, two_env=True):
+        phys = BatchedPhysics(m, len(qs), kernel=KernelOptions(two_env=two_env))
+        assert phys.kernel_info()['threads_per_env'] == (32 if two_env else 64)
         q32, v32, _ = set_state(phys, np.array(qs), np.zeros((len(qs), m.nv)))
         phys.step(T)
         torch.cuda.synchronize()
@@ -738,8 +738,7 @@ def test_two_env_kernel_modes_do_not_depend_on_the_partner(oracle, monkeypatch):
     assert same(r_mm, 0, r_lm, 1) and same(r_mm, 0, r_mh, 0) and same(r_mm, 1, r_ml, 0), 'an env with 33..64 rows changed with its partner'
     r_hh = run([Hv, Hv])
     assert same(r_hh, 0, r_lh, 1) and same(r_hh, 0, r_mh, 1) and same(r_hh, 0, r_hh, 1)
-    monkeypatch.setenv('FMJ_DUAL', '0')            # the one-env kernel from the first step on: what a retired env must reproduce bitwise
-    r_one = run([Hv, L])
+    r_one = run([Hv, L], two_env=False)            # the one-env kernel from the first step on: what a retired env must reproduce bitwise
     assert same(r_one, 0, r_hh, 0), 'a retired env is not what the one-env kernel computes'
     # ... and the two kernels agree with each other and with the oracle to fp32 tolerance on the light env
     assert _relerr(r_one[0][1], r_ll[0][0]) < 2e-5
@@ -818,17 +817,15 @@ def test_thousand_steps_of_walking(oracle, solver):
 
 @pytest.mark.parametrize('dual', ['1', '0'], ids=['two_per_wave', 'one_per_wave'])
 @pytest.mark.parametrize('substeps', [2, 3])
-def test_fused_walk_with_substeps(oracle, monkeypatch, substeps, dual):
+def test_fused_walk_with_substeps(oracle, substeps, dual):
     """Walking with num_sub_steps > 1 (reference task.py:168-186,348-369: joint and contact rows once per iteration, at the full
     step; the model steps at timestep / S) through both constraint kernels: the fused launch equals the operator-by-operator path row
     for row, and both follow the oracle's restatement of the task's counters."""
-    import os
     import torch
     from farms_mujoco_amd.data import AnimatData
     from farms_mujoco_amd.model import salamander33
-    from farms_mujoco_amd.options import SimulationOptions
+    from farms_mujoco_amd.options import SimulationOptions, KernelOptions
     from farms_mujoco_amd.simulation.simulation import Simulation
-    monkeypatch.setenv('FMJ_DUAL', dual)
     S, h = substeps, 1e-3
     m = salamander33(contacts=True, limits=True, spawn_z=0.045, timestep=h/S)
     n, T = 6, 30
@@ -838,7 +835,8 @@ def test_fused_walk_with_substeps(oracle, monkeypatch, substeps, dual):
 
     def make():
         data = AnimatData(h, T, n, m.body_names[1:], m.hinge_joint_names(), contacts=pairs)
-        sim = Simulation(m, m.body_names[1], SimulationOptions(timestep=h, n_iterations=T, num_sub_steps=S), n_envs=n, data=data, buffer_size=T)
+        sim = Simulation(m, m.body_names[1], SimulationOptions(timestep=h, n_iterations=T, num_sub_steps=S), n_envs=n, data=data, buffer_size=T,
+                         kernel=KernelOptions(two_env=dual == '1'))
         sim.reset()
         sim.physics.data.qpos[:] = torch.as_tensor(q0, dtype=torch.float32)
         sim.physics.forward(disable_actuation=True)

@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from farms_mujoco_amd.options import KernelOptions
 from parity_metrics import relerr as _relerr
 from support_capi import FMJ_ERR_ARG
 from support_sims import load_batch, outputs, env_of as _env_of, assert_bitwise as _assert_bitwise
@@ -56,8 +57,8 @@ def _initial(m, n, kind, env_offset=0):
     return qpos, qvel, psi
 
 
-def _make_sim(kind, controller_of, n=N, n_iterations=T, ring=RING, substeps=1, env_offset=0, device='cuda:0'):
-    """A fused swimming (or walking) simulation whose controller is ``controller_of(m, psi)``."""
+def _make_sim(kind, controller_of, n=N, n_iterations=T, ring=RING, substeps=1, env_offset=0, device='cuda:0', kernel=None):
+    """A fused swimming (or walking) simulation whose controller is ``controller_of(m, psi)``; ``kernel``: its KernelOptions."""
     from farms_mujoco_amd.data import AnimatData
     from farms_mujoco_amd.options import SimulationOptions, ArenaOptions, AnimatOptions, WaterOptions
     from farms_mujoco_amd.simulation.simulation import Simulation
@@ -73,7 +74,7 @@ def _make_sim(kind, controller_of, n=N, n_iterations=T, ring=RING, substeps=1, e
         arena = ArenaOptions(water=WaterOptions(height=height, velocity=[0.03, 0.0, -0.01]))
     sim = Simulation.from_sdf(SimulationOptions(timestep=1e-3, n_iterations=n_iterations, num_sub_steps=substeps),
                               AnimatOptions.from_model(m), arena, model=m, n_envs=n, controller=controller_of(m, psi),
-                              buffer_size=ring, device=device, **kw)
+                              buffer_size=ring, device=device, kernel=kernel, **kw)
     load_batch(sim, qpos, qvel)
     return sim, m
 
@@ -182,18 +183,16 @@ def test_bad_ext_is_an_argument_error(monkeypatch):
 # ---- 2. uniform per-env rows are the shared parameters, in every register tier -------------------------------------------------
 
 @pytest.mark.parametrize('wps', ['2', '3', '4'])
-def test_uniform_rows_equal_shared_parameters_bitwise(wps, monkeypatch):
+def test_uniform_rows_equal_shared_parameters_bitwise(wps):
     from farms_mujoco_amd.control import WaveController
     from farms_mujoco_amd.model import wave_controller_params
-    monkeypatch.setenv('FMJ_WPS', wps)
-    monkeypatch.setenv('FMJ_DUAL_LEAN', '0')
-    shared_sim, m = _make_sim('salamander', lambda m, psi: WaveController(m, psi, frequency=1.25))
+    shared_sim, m = _make_sim('salamander', lambda m, psi: WaveController(m, psi, frequency=1.25), kernel=KernelOptions(wps=int(wps), lean=False))
     shared = _run(shared_sim)
     sinfo = shared_sim.physics.kernel_info()
     assert sinfo['dual_wps'] == int(wps) and sinfo['dual_build'] == 'generic' and sinfo['dual_last_launch'] == 'generic', sinfo
-    monkeypatch.delenv('FMJ_DUAL_LEAN')            # a context with the lean build enabled: the per-env launch must not take it
     amp, lag = wave_controller_params(m, 0.3, 1.0)
-    rows_sim, _ = _make_sim('salamander', _per_env(np.full(N, 1.25), np.tile(amp, (N, 1)), np.tile(lag, (N, 1))))
+    rows_sim, _ = _make_sim('salamander', _per_env(np.full(N, 1.25), np.tile(amp, (N, 1)), np.tile(lag, (N, 1))),
+                            kernel=KernelOptions(wps=int(wps)))      # a context with the lean build enabled: the per-env launch must not take it
     rows = _run(rows_sim)
     info = rows_sim.physics.kernel_info()
     assert info['dual_wps'] == int(wps) and info['dual_build'] == 'lean' and info['dual_last_launch'] == 'generic', info
@@ -202,10 +201,10 @@ def test_uniform_rows_equal_shared_parameters_bitwise(wps, monkeypatch):
 
 # ---- 3. an env owns its numbers ---------------------------------------------------------------------------------------------------
 
-CASES = {      # kind, threads per env of the step kernel, environment at fmj_create, sub-steps, fused
+CASES = {      # kind, threads per env of the step kernel, KernelOptions kwargs, sub-steps, fused
     'two_envs_per_wave': ('salamander', 32, {}, 1, True),
     'one_env_kernel': ('centipede', 64, {}, 1, True),
-    'two_waves_per_env': ('centipede', 128, {'FMJ_WIDE': '1'}, 1, True),
+    'two_waves_per_env': ('centipede', 128, {'two_wave': True}, 1, True),
     'two_waves_per_env_long': ('centipede_long', 128, {}, 1, True),
     'constraint_kernels': ('walker', 32, {}, 1, True),
     'substeps_3': ('salamander', 32, {}, 3, True),
@@ -214,17 +213,16 @@ CASES = {      # kind, threads per env of the step kernel, environment at fmj_cr
 
 
 @pytest.mark.parametrize('case', list(CASES))
-def test_env_equals_shared_batch_with_its_rows(case, monkeypatch):
+def test_env_equals_shared_batch_with_its_rows(case):
     """Env e of the per-env batch == env e of a batch in which EVERY env has e's frequency, amplitude row and lag row (today's
     shared controller), from the same initial states: bitwise, for every e - so neither the wave partner nor the per-env indexing
     shows in an env's numbers."""
-    kind, threads, env, substeps, fused = CASES[case]
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    kind, threads, kernel, substeps, fused = CASES[case]
+    kernel = KernelOptions(**kernel)
     n = 3 if kind == 'centipede_long' else N
     m = _model(kind, substeps)
     freq, amp, lag = _params(m, n)
-    sim, _ = _make_sim(kind, _per_env(freq, amp, lag), n=n, substeps=substeps)
+    sim, _ = _make_sim(kind, _per_env(freq, amp, lag), n=n, substeps=substeps, kernel=kernel)
     got = _run(sim, fused)
     info = sim.physics.kernel_info()
     assert info['threads_per_env'] == threads, info
@@ -237,7 +235,7 @@ def test_env_equals_shared_batch_with_its_rows(case, monkeypatch):
     # not vacuous: the envs are commanded differently, and differently from a shared batch
     assert np.abs(got['ctrl'][0] - got['ctrl'][1]).max() > 1e-2
     for e in range(n):
-        ref_sim, _ = _make_sim(kind, _shared(freq[e], amp[e], lag[e]), n=n, substeps=substeps)
+        ref_sim, _ = _make_sim(kind, _shared(freq[e], amp[e], lag[e]), n=n, substeps=substeps, kernel=kernel)
         ref = _run(ref_sim, fused)
         _assert_bitwise(_env_of(got, e), _env_of(ref, e), f'{case} env {e}')
         other = (e + 1) % n

@@ -306,18 +306,18 @@ def test_full_size_config2_properties(oracle, N):
     assert np.abs(q[:, 0] - qpos[:, 0]).mean() > 0.02
 
 
-@pytest.mark.parametrize('env', [dict(FMJ_WPS='3'), dict(FMJ_WPS='4'), dict(FMJ_DUAL='0')])
-def test_every_step_kernel_build_matches_oracle(oracle, env, monkeypatch):
-    """The kernel a context uses is picked at fmj_create (batch size, model, FMJ_* switches): the two-env kernel in its
+@pytest.mark.parametrize('kernel', [dict(wps=3), dict(wps=4), dict(two_env=False)], ids=['wps3', 'wps4', 'one_env_per_wave'])
+def test_every_step_kernel_build_matches_oracle(oracle, kernel):
+    """The kernel a context uses is picked at fmj_create (batch size, model, KernelOptions): the two-env kernel in its
     168- and 128-register builds and the one-env kernel all reproduce the oracle on the same fused
     workload (odd batch: the last wave of the two-env kernels has an idle half)."""
     import torch
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    from farms_mujoco_amd.options import KernelOptions
     n, T = 7, 120
-    sim, m, psi = _make_sim(n, T, buffer_size=40, water_kwargs=dict(height=-0.11, velocity=[0.03, 0.0, -0.01]))
+    sim, m, psi = _make_sim(n, T, buffer_size=40, water_kwargs=dict(height=-0.11, velocity=[0.03, 0.0, -0.01]), kernel=KernelOptions(**kernel))
     info = sim.physics.kernel_info()
-    assert info['threads_per_env'] == (64 if env.get('FMJ_DUAL') == '0' else 32)
+    assert info['threads_per_env'] == (32 if kernel.get('two_env', True) else 64)
+    assert info.get('dual_wps') == kernel.get('wps')      # the tier asked for; the one-env kernel has none
     st = _oracle_initial_state(oracle, sim, m)
     swim, water = _swim_water(sim)
     sim.run(fused=True)
@@ -332,7 +332,7 @@ def test_every_step_kernel_build_matches_oracle(oracle, env, monkeypatch):
     errs = dict(qpos=_relerr(d.qpos.cpu().numpy(), ref['qpos']), links=_relerr(sens.links.array.cpu().numpy(), ref['links']),
                 joints=_relerr(sens.joints.array.cpu().numpy(), ref['joints']), xfrc=_relerr(sens.xfrc.array.cpu().numpy(), ref['xfrc']),
                 sensordata=_relerr(d.sensordata.cpu().numpy(), ref['sensordata']))
-    print(env, errs)
+    print(kernel, errs)
     # link rows carry velocities: 0.8e-4 (two-env builds) to 1.1e-4 (one-env build) after 120 steps, fp32 rounding of
     # differently scheduled but identical arithmetic; the state itself is at 6e-6
     assert errs['qpos'] < 1e-4 and errs['links'] < 2e-4 and errs['joints'] < 1e-3 and errs['xfrc'] < 1e-3 and errs['sensordata'] < 2e-3, errs

@@ -41,10 +41,10 @@ def _state(m, n, seed, vscale=0.3):
     return qpos, qvel, ctrl
 
 
-def _run(m, qpos, qvel, ctrl, n_steps):
+def _run(m, qpos, qvel, ctrl, n_steps, kernel=None):
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
-    phys = BatchedPhysics(m, qpos.shape[0], 'cuda:0')
+    phys = BatchedPhysics(m, qpos.shape[0], 'cuda:0', kernel=kernel)
     d = phys.data
     d.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32); d.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
     d.ctrl[:] = torch.as_tensor(ctrl, dtype=torch.float32)
@@ -60,17 +60,18 @@ def _run(m, qpos, qvel, ctrl, n_steps):
 @pytest.mark.parametrize('kw,dual', [({}, '1'), ({}, '0'), (dict(contacts=True, limits=True, spawn_z=0.045), '1'), (dict(contacts=True, limits=True, spawn_z=0.045), '0'),
                                      (dict(contacts=True, limits=True, spawn_z=0.045, solver='newton'), '0')],
                          ids=['two_per_wave', 'one_per_wave', 'two_per_wave_constrained', 'one_per_wave_constrained', 'one_per_wave_newton'])
-def test_implicitfast_step_matches_oracle(oracle, monkeypatch, kw, dual, clamp):
+def test_implicitfast_step_matches_oracle(oracle, kw, dual, clamp):
     """One step and 200 steps from random states with random velocity-servo targets.  qvel is held to the same fp32-storage floor as
     the Euler step (tests/test_gpu_step_parity.py), and the test has teeth: the Euler result of the same inputs is further from the
     oracle's implicitfast than the bound allows."""
+    from farms_mujoco_amd.options import KernelOptions
     n, maker, tpe = 32, 'salamander33', 32 if dual == '1' else 64
-    monkeypatch.setenv('FMJ_DUAL', dual)                 # '0': the one-env kernels step the same model
+    kernel = KernelOptions(two_env=dual == '1')          # '0': the one-env kernels step the same model
     m = _servo_model(maker, 'implicitfast', clamp=clamp, **kw)
     # (the primal solvers are held to states of walking speed, as in tests/test_gpu_newton.py: from the violent ones an fp32 Newton
     # iteration and the fp64 one stop at different iterates - 4 % of qvel, under Euler as under implicitfast)
     qpos, qvel, ctrl = _state(m, n, 11, vscale=0.02 if kw.get('solver') else 0.3)
-    phys, (q32, v32, c32), q1, v1 = _run(m, qpos, qvel, ctrl, 1)
+    phys, (q32, v32, c32), q1, v1 = _run(m, qpos, qvel, ctrl, 1, kernel)
     assert phys.kernel_info()['threads_per_env'] == tpe
     ref = oracle.step(m, q32, v32, ctrl=c32)
     with oracle.fp32_storage():
@@ -88,10 +89,10 @@ def test_implicitfast_step_matches_oracle(oracle, monkeypatch, kw, dual, clamp):
     assert gap > 20*bound(fl), (gap, fl)             # implicitfast is not Euler on these inputs ...
     with oracle.fp32_storage():
         fle = group_relerr(oracle.step(me, q32, v32, ctrl=c32)['qvel'], eul['qvel'], groups)
-    _, _, _, ve = _run(me, qpos, qvel, ctrl, 1)
+    _, _, _, ve = _run(me, qpos, qvel, ctrl, 1, kernel)
     assert group_relerr(ve, eul['qvel'], groups) < bound(fle)     # ... and the device's Euler still is Euler
     # 200 steps (swimmers in free space / the walker settling on its feet)
-    _, (q32, v32, c32), q200, v200 = _run(m, qpos, qvel, ctrl, 200)
+    _, (q32, v32, c32), q200, v200 = _run(m, qpos, qvel, ctrl, 200, kernel)
     ref = oracle.step(m, q32, v32, ctrl=c32, n_steps=200)
     e = relerr(q200, ref['qpos'])
     print('qpos after 200 steps', e)

@@ -6,7 +6,7 @@ Procedure (the pattern of test_plane_box_contacts): create BatchedPhysics(model,
 convert the records with oracle.contacts_from_hip, compare env by env with ref_ground_contacts(model, q32[e]).  The envs of one batch are
 the poses of one model, batch sizes are odd and neighbouring envs hold different cases, so the two halves of a wave of the two-env kernel
 disagree about their contact counts.  Models the two-env constraint kernel accepts (one ground, at most 32 geoms, no mesh, PGS, pyramidal)
-run twice - default path and FMJ_DUAL=0 - and every run asserts kernel_info()['threads_per_env'], so it is known which kernel ran.
+run twice - default path and KernelOptions(two_env=False) - and every run asserts kernel_info()['threads_per_env'], so it is known which kernel ran.
 
 Per env: ncon equal; geom ids of every record equal, in the reference's order; positions within 2e-6 m and the nine frame entries within
 2e-5 (the bounds of test_heightfield_contacts_match_oracle, for every case); status 0, or exactly FMJ_WARN_CONTACTFULL where the case is a
@@ -31,19 +31,16 @@ POS_TOL, FRAME_TOL = 2e-6, 2e-5
 ONE_ENV_ONLY = ('two_grounds', 'chunk')          # two ground entries; more than 32 geoms
 
 
-def _run(oracle, monkeypatch, m, qpos, threads, label, exact=(), truncated=(), forces=True):
+def _run(oracle, m, qpos, threads, label, exact=(), truncated=(), forces=True):
     """One batch through the device and the reference; returns (worst position error, worst frame error, contacts compared)."""
     import torch
+    from farms_mujoco_amd.options import KernelOptions
     from farms_mujoco_amd.physics import BatchedPhysics
-    if threads == 64:
-        monkeypatch.setenv('FMJ_DUAL', '0')
-    else:
-        monkeypatch.delenv('FMJ_DUAL', raising=False)
     qpos = np.asarray(qpos, float)
     n = len(qpos)
     assert n % 2 == 1
     rng = np.random.default_rng(zlib.crc32(label.encode()))
-    phys = BatchedPhysics(m, n)
+    phys = BatchedPhysics(m, n, kernel=KernelOptions(two_env=threads == 32))
     assert phys.kernel_info()['threads_per_env'] == threads, (label, phys.kernel_info())
     q32, v32, _ = set_state(phys, qpos, 0.05*rng.normal(size=(n, m.nv)))
     phys.data.status.zero_()          # OR-accumulated: the constructor's reset ran a forward pass at qpos0, where the body lies in the ground
@@ -96,41 +93,41 @@ DIRECTED = [(key, t) for key in directed_batches() for t in ((64,) if key in ONE
 
 
 @pytest.mark.parametrize('key,threads', DIRECTED)
-def test_directed_cases(oracle, monkeypatch, key, threads):
+def test_directed_cases(oracle, key, threads):
     """The table of directed cases of support_narrow.py, one batch per model, on each kernel that accepts the model."""
     cases = directed_batches()[key]
     m = directed_model(key)
-    _, _, compared = _run(oracle, monkeypatch, m, [c.qpos for c in cases], threads, f'directed/{key}',
+    _, _, compared = _run(oracle, m, [c.qpos for c in cases], threads, f'directed/{key}',
                           exact={e for e, c in enumerate(cases) if c.exact}, truncated={e for e, c in enumerate(cases) if c.truncated})
     assert compared == sum(c.ncon for c in cases)
 
 
 @pytest.mark.parametrize('i', range(8))
-def test_seeded_scenes_two_grounds(oracle, monkeypatch, i):
+def test_seeded_scenes_two_grounds(oracle, i):
     """A four-shape body over a tilted plane plus a rotated heightfield: the loop over ground entries of the one-env kernel."""
     grounds, geoms, qs = seeded_scenes().two_grounds[i]
-    _run(oracle, monkeypatch, build_model(grounds, geoms, max_contacts=32), qs, 64, f'seeded/two_grounds/{i}')
+    _run(oracle, build_model(grounds, geoms, max_contacts=32), qs, 64, f'seeded/two_grounds/{i}')
 
 
 @pytest.mark.parametrize('i,threads', [(i, t) for i in range(8) for t in (32, 64)])
-def test_seeded_scenes_single_ground(oracle, monkeypatch, i, threads):
+def test_seeded_scenes_single_ground(oracle, i, threads):
     """The same bodies and poses over one of the two grounds (plane and heightfield alternating): these reach the two-env kernel."""
     grounds, geoms, qs = seeded_scenes().single[i]
-    _run(oracle, monkeypatch, build_model(grounds, geoms, max_contacts=32), qs, threads, f'seeded/single/{i}')
+    _run(oracle, build_model(grounds, geoms, max_contacts=32), qs, threads, f'seeded/single/{i}')
 
 
 @pytest.mark.parametrize('i', range(4))
-def test_seeded_scenes_with_a_convex_mesh(oracle, monkeypatch, i):
+def test_seeded_scenes_with_a_convex_mesh(oracle, i):
     """A cube given as 8 vertices / a hull of 20, over the tilted plane or the heightfield: the MESH build keeps the deepest four in order."""
     grounds, geoms, qs = seeded_scenes().mesh[i]
-    _, _, compared = _run(oracle, monkeypatch, build_model(grounds, geoms, max_contacts=32), qs, 64, f'seeded/mesh/{i}')
+    _, _, compared = _run(oracle, build_model(grounds, geoms, max_contacts=32), qs, 64, f'seeded/mesh/{i}')
     assert compared >= 1
 
 
 @pytest.mark.parametrize('solver,cone', [('newton', 'pyramidal'), ('cg', 'pyramidal'), ('newton', 'elliptic'), ('cg', 'elliptic')])
 @pytest.mark.parametrize('i', range(8))
-def test_seeded_scenes_other_solvers(oracle, monkeypatch, i, solver, cone):
+def test_seeded_scenes_other_solvers(oracle, i, solver, cone):
     """The Newton / CG and elliptic instantiations compile the narrow phase on their own: ncon, ids, positions and frames only."""
     grounds, geoms, qs = seeded_scenes().two_grounds[i]
     m = build_model(grounds, geoms, max_contacts=32, solver=solver, cone=cone)
-    _run(oracle, monkeypatch, m, qs, 64, f'seeded/{solver}-{cone}/{i}', forces=False)
+    _run(oracle, m, qs, 64, f'seeded/{solver}-{cone}/{i}', forces=False)

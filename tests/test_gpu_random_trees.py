@@ -4,29 +4,26 @@ with control / force limits, external forces) against the fp64 oracle."""
 import numpy as np
 import pytest
 
+from farms_mujoco_amd.options import KernelOptions
 from support_models import random_tree, FMJ_WARN_CONTACTFULL
 from support_sims import check_random_tree_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize('seed,two_per_wave', [(s, True) for s in range(20)] + [(s, False) for s in range(0, 20, 2)])
-def test_random_tree_vs_oracle(oracle, seed, two_per_wave, monkeypatch):
-    """Every tree here has <= 32 bodies, so it runs in the two-envs-per-wave kernel by default; FMJ_DUAL=0 (read at
-    fmj_create) sends the same tree through the one-env-per-wave kernel."""
-    if not two_per_wave:
-        monkeypatch.setenv('FMJ_DUAL', '0')
-    check_random_tree_vs_oracle(oracle, seed, 32 if two_per_wave else 64)
+def test_random_tree_vs_oracle(oracle, seed, two_per_wave):
+    """Every tree here has <= 32 bodies, so it runs in the two-envs-per-wave kernel by default; KernelOptions(two_env=False)
+    sends the same tree through the one-env-per-wave kernel."""
+    check_random_tree_vs_oracle(oracle, seed, 32 if two_per_wave else 64, KernelOptions(two_env=two_per_wave))
 
 
 @pytest.mark.parametrize('seed,two_per_wave', [(s, True) for s in range(100, 112)] + [(s, False) for s in range(100, 112, 2)])
-def test_random_tree_with_limits_and_contacts(oracle, seed, two_per_wave, monkeypatch):
+def test_random_tree_with_limits_and_contacts(oracle, seed, two_per_wave):
     """The constraint path on random trees: limited hinges, sphere / capsule / box / cylinder geoms over a plane that cuts
     through the tree; contact lists, constraint forces and the state after one and after 30 steps vs the oracle.  Every tree here has
-    <= 32 bodies: it runs in the two-env constraint kernel (fmj_cons2.inc) by default, FMJ_DUAL=0 sends it through the one-env kernel."""
+    <= 32 bodies: it runs in the two-env constraint kernel (fmj_cons2.inc) by default, KernelOptions(two_env=False) sends it through the one-env kernel."""
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
-    if not two_per_wave:
-        monkeypatch.setenv('FMJ_DUAL', '0')
     m = random_tree(seed, contacts=True)
     if m is None or m.nv == 0:
         pytest.skip('degenerate draw')
@@ -39,7 +36,7 @@ def test_random_tree_with_limits_and_contacts(oracle, seed, two_per_wave, monkey
             qpos[:, a+2] = rng.uniform(-0.05, 0.1, n)
     qvel = rng.normal(size=(n, m.nv))*0.2
     ctrl = rng.uniform(-0.4, 0.4, (n, max(m.nu, 1)))[:, :m.nu]
-    phys = BatchedPhysics(m, n)
+    phys = BatchedPhysics(m, n, kernel=KernelOptions(two_env=two_per_wave))
     assert phys.kernel_info()['threads_per_env'] == (32 if two_per_wave else 64)
     d = phys.data
     f32 = lambda a: torch.as_tensor(a, dtype=torch.float32)

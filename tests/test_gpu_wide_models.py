@@ -1,6 +1,6 @@
 """Models past one wavefront: the two-wave step kernel (csrc/fmj_wide.inc, one workgroup of 128 threads per env) on unconstrained
 models of up to 128 bodies / dofs, against the fp64 oracle with the fp32-storage-floor yardsticks of test_gpu_morphologies.py, against
-the one-wave kernels on the same model (FMJ_WIDE=1), and through the product path (fused swim, freeze, checkpoint)."""
+the one-wave kernels on the same model (KernelOptions(two_wave=True)), and through the product path (fused swim, freeze, checkpoint)."""
 import numpy as np
 import pytest
 
@@ -24,10 +24,10 @@ def _tape(m, n, T, psi):
     return amp[None, None, :]*np.sin(2*np.pi*1.5*t - lag[None, None, :] + psi[None, :, None])
 
 
-def _phys(m, qpos, qvel):
+def _phys(m, qpos, qvel, kernel=None):
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
-    phys = BatchedPhysics(m, qpos.shape[0])
+    phys = BatchedPhysics(m, qpos.shape[0], kernel=kernel)
     phys.data.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32)
     phys.data.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
     return phys
@@ -104,22 +104,21 @@ def test_fused_swim_of_a_wide_centipede(oracle):
 
 
 @pytest.mark.parametrize('maker', ['centipede', 'salamander33', 'eel58'])
-def test_forced_wide_kernel_matches_the_one_wave_kernel(oracle, monkeypatch, maker):
-    """FMJ_WIDE=1 runs the two-wave kernel on a model that fits one wave: after 1 and 100 steps it agrees with the model's own kernel
+def test_forced_wide_kernel_matches_the_one_wave_kernel(oracle, maker):
+    """KernelOptions(two_wave=True) runs the two-wave kernel on a model that fits one wave: after 1 and 100 steps it agrees with the model's own kernel
     per component within 6x the fp32-storage floor (two fp32 kernels with different reduction orders: not bitwise).  eel58: a dof
     chain of 64, the register row of the MAXD 64 instantiation."""
     import torch
     import farms_mujoco_amd.model as mm
+    from farms_mujoco_amd.options import KernelOptions
     m = mm.eel(n_joints=58) if maker == 'eel58' else getattr(mm, maker)()
     n = 8
     qpos, qvel, psi = mm.synthetic_batch(m, n, seed=4)
     T = 100
     tape_t = torch.as_tensor(_tape(m, n, T, psi), dtype=torch.float32, device='cuda').contiguous()
-    base = _phys(m, qpos, qvel)
+    base = _phys(m, qpos, qvel, KernelOptions())
     assert base.kernel_info()['threads_per_env'] in (32, 64)
-    monkeypatch.setenv('FMJ_WIDE', '1')
-    wide = _phys(m, qpos, qvel)
-    monkeypatch.delenv('FMJ_WIDE')
+    wide = _phys(m, qpos, qvel, KernelOptions(two_wave=True))
     assert wide.kernel_info()['threads_per_env'] == 128
     q32 = torch.as_tensor(qpos, dtype=torch.float32).numpy().astype(np.float64)
     ctrl = tape_t.cpu().numpy().astype(np.float64)

@@ -8,6 +8,7 @@ is checked without a GPU in test_wide_tree_coverage.py."""
 import numpy as np
 import pytest
 
+from farms_mujoco_amd.options import KernelOptions
 from parity_metrics import relerr, group_relerr, qpos_groups, qvel_groups, link_row_groups
 from wide_trees import WIDE_SHAPES, shape_tree, tree_properties, dof_depth
 from support_models import tree_inputs as _inputs, FMJ_WARN_BADQPOS
@@ -15,14 +16,12 @@ from support_sims import f64 as _f64, swim_sim, wave_at, oracle_initial_state, s
 
 pytestmark = pytest.mark.gpu
 
-def _wide_phys(m, n, monkeypatch, qpos, qvel, ctrl=None, xf=None, qs=None):
-    """BatchedPhysics of m in the two-wave kernel (FMJ_WIDE=1 is read at fmj_create; models past 64 take it anyway) with the inputs
+def _wide_phys(m, n, qpos, qvel, ctrl=None, xf=None, qs=None):
+    """BatchedPhysics of m in the two-wave kernel (KernelOptions(two_wave=True); models past 64 take it anyway) with the inputs
     stored in fp32; returns it and the inputs as the device holds them, in fp64."""
     import torch
     from farms_mujoco_amd.physics import BatchedPhysics
-    monkeypatch.setenv('FMJ_WIDE', '1')
-    phys = BatchedPhysics(m, n)
-    monkeypatch.delenv('FMJ_WIDE')
+    phys = BatchedPhysics(m, n, kernel=KernelOptions(two_wave=True))
     assert phys.kernel_info()['threads_per_env'] == 128
     d = phys.data
     f32 = lambda a: torch.as_tensor(a, dtype=torch.float32)
@@ -72,7 +71,7 @@ def _qvel_bound(name, got, ref, flo, m, seed):
 # ---- one step and a rollout per tree -----------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize('seed', [s[0] for s in WIDE_SHAPES])
-def test_wide_random_tree_vs_oracle(oracle, seed, monkeypatch):
+def test_wide_random_tree_vs_oracle(oracle, seed):
     """One step: poses, sensors and qpos to the bounds of test_random_tree_vs_oracle, qvel to 6x its per-component floor.  Then a
     100-step rollout with a ctrl tape (xfrc_applied and qpos_spring held): qpos within max(1e-4, 6x the floor's own rollout).  The
     trees named in QVEL_FLOOR_FACTOR / ROLLOUT_FLOOR_FACTOR use their measured factors instead of 6."""
@@ -80,7 +79,7 @@ def test_wide_random_tree_vs_oracle(oracle, seed, monkeypatch):
     m = shape_tree(seed)
     n, T = 6, 100
     qpos, qvel, ctrl, xf, qs = _inputs(m, n, seed)
-    phys, ins = _wide_phys(m, n, monkeypatch, qpos, qvel, ctrl, xf, qs)
+    phys, ins = _wide_phys(m, n, qpos, qvel, ctrl, xf, qs)
     d = phys.data
     rng = np.random.default_rng(4000 + seed)
     t = np.arange(T)[:, None, None]*m.timestep
@@ -116,7 +115,7 @@ def test_wide_random_tree_vs_oracle(oracle, seed, monkeypatch):
 # ---- the stage outputs: H and qfrc_smooth ------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize('seed', [s[0] for s in WIDE_SHAPES])
-def test_wide_mass_matrix_and_bias_stage(oracle, seed, monkeypatch):
+def test_wide_mass_matrix_and_bias_stage(oracle, seed):
     """fmj_forward_debug on the two-wave kernel (actuation off): the register row length is the 32 or 64 the dof chain asks for; every
     entry of H = M + diag(armature + h damping) within 1e-5 of sqrt(H_ii H_jj) (H_BOUND for the trees named there) and qfrc_smooth =
     passive - bias + the external forces within 2e-5 of its largest entry (the bounds of test_mass_matrix_and_bias_stage).  Localises a K / C / S / M-phase error to its
@@ -125,7 +124,7 @@ def test_wide_mass_matrix_and_bias_stage(oracle, seed, monkeypatch):
     m = shape_tree(seed)
     n = 4
     qpos, qvel, ctrl, xf, qs = _inputs(m, n, seed)
-    phys, ins = _wide_phys(m, n, monkeypatch, qpos, qvel, ctrl, xf, qs)
+    phys, ins = _wide_phys(m, n, qpos, qvel, ctrl, xf, qs)
     H, qf = phys.forward_debug(disable_actuation=True)
     torch.cuda.synchronize()
     rs = H.shape[2]
@@ -155,14 +154,14 @@ def test_wide_mass_matrix_and_bias_stage(oracle, seed, monkeypatch):
 # ---- fmj_forward -------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize('disable_actuation', [True, False])
-def test_wide_forward_matches_oracle(oracle, disable_actuation, monkeypatch):
+def test_wide_forward_matches_oracle(oracle, disable_actuation):
     """fmj_forward (what reset runs) on the nq = 129 tree: poses and sensors against oracle.forward_debug, with actuation off (the
     actuator forces are zero) and on; the state is left as it was."""
     import torch
     m = shape_tree(1)
     n = 4
     qpos, qvel, ctrl, xf, qs = _inputs(m, n, 1)
-    phys, ins = _wide_phys(m, n, monkeypatch, qpos, qvel, ctrl, xf, qs)
+    phys, ins = _wide_phys(m, n, qpos, qvel, ctrl, xf, qs)
     d = phys.data
     q0, v0 = d.qpos.clone(), d.qvel.clone()
     phys.forward(disable_actuation=disable_actuation)
@@ -191,11 +190,10 @@ def test_wide_forward_matches_oracle(oracle, disable_actuation, monkeypatch):
 # ---- the small random trees of test_gpu_random_trees.py, forced onto the two-wave kernel ------------------------------------------
 
 @pytest.mark.parametrize('seed', range(20))
-def test_small_random_tree_on_the_wide_kernel(oracle, seed, monkeypatch):
-    """FMJ_WIDE=1 on random_tree(0..19) (3..21 bodies): a second wave with no body and no dof, most lanes of the first idle; the
-    assertions of test_random_tree_vs_oracle."""
-    monkeypatch.setenv('FMJ_WIDE', '1')
-    check_random_tree_vs_oracle(oracle, seed, 128)
+def test_small_random_tree_on_the_wide_kernel(oracle, seed):
+    """KernelOptions(two_wave=True) on random_tree(0..19) (3..21 bodies): a second wave with no body and no dof, most lanes of the
+    first idle; the assertions of test_random_tree_vs_oracle."""
+    check_random_tree_vs_oracle(oracle, seed, 128, KernelOptions(two_wave=True))
 
 
 # ---- implicitfast ------------------------------------------------------------------------------------------------------------------
@@ -228,7 +226,7 @@ def _servo_inputs(m, n):
 
 
 @pytest.mark.parametrize('clamp', [False, True])
-def test_wide_implicitfast_step_matches_oracle(oracle, clamp, monkeypatch):
+def test_wide_implicitfast_step_matches_oracle(oracle, clamp):
     """The structure of test_implicitfast_step_matches_oracle on a 65-dof tree (nbody 66): one step's qvel per component within 6x the
     floor, and the Euler result of the same inputs is more than 20x the bound away (so the bound can tell the integrators apart); the
     device's Euler is Euler; 200 steps within max(1e-4, 6x the floor's own rollout)."""
@@ -239,7 +237,7 @@ def test_wide_implicitfast_step_matches_oracle(oracle, clamp, monkeypatch):
     groups = qvel_groups(m)
 
     def run(model, steps):
-        phys, ins = _wide_phys(model, n, monkeypatch, qpos, qvel, ctrl)
+        phys, ins = _wide_phys(model, n, qpos, qvel, ctrl)
         phys.step(steps)
         torch.cuda.synchronize()
         assert int(phys.data.status.abs().sum()) == 0
@@ -413,7 +411,7 @@ def test_wide_torque_control_springrefs_and_disabled_actuators(oracle):
 
 # ---- freeze from the far end of the state ------------------------------------------------------------------------------------------
 
-def test_nan_in_the_last_qpos_entry_freezes_a_wide_env(monkeypatch):
+def test_nan_in_the_last_qpos_entry_freezes_a_wide_env():
     """nq = 129: qpos[128] is the entry lane 0 loads on its second pass.  A NaN there freezes that env with FMJ_WARN_BADQPOS and keeps
     its pre-launch qpos; every other env is bitwise what a clean run gives."""
     import torch
@@ -421,9 +419,9 @@ def test_nan_in_the_last_qpos_entry_freezes_a_wide_env(monkeypatch):
     assert m.nq == 129
     n, T, bad = 5, 20, 3
     qpos, qvel, ctrl, xf, qs = _inputs(m, n, 1)
-    clean, _ = _wide_phys(m, n, monkeypatch, qpos, qvel, ctrl, xf, qs)
+    clean, _ = _wide_phys(m, n, qpos, qvel, ctrl, xf, qs)
     clean.step(T)
-    phys, _ = _wide_phys(m, n, monkeypatch, qpos, qvel, ctrl, xf, qs)
+    phys, _ = _wide_phys(m, n, qpos, qvel, ctrl, xf, qs)
     d = phys.data
     d.qpos[bad, 128] = float('nan')
     q_before = d.qpos[bad].clone()

@@ -83,7 +83,7 @@ def test_wide_random_tree_draws_are_seeded():
 
 
 # sha1 of what random_tree(0..19) draws (tree structure, joint kinds, frames, axes, actuators, gravity), taken before the wide generator
-# was added: test_random_tree_vs_oracle and its FMJ_WIDE=1 run in test_gpu_wide_random_trees.py must keep stepping these trees
+# was added: test_random_tree_vs_oracle and its two-wave run in test_gpu_wide_random_trees.py must keep stepping these trees
 RANDOM_TREE_DIGEST = '00dcf40a493afc37f913a6f2610ae325581e73e4'
 
 
