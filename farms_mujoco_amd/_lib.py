@@ -123,6 +123,7 @@ SYMBOLS = {
     'fmj_contacts2data': (ctypes.c_int, [_VP, ctypes.POINTER(CData), ctypes.POINTER(CRows), ctypes.POINTER(CUnits), _VP]),
     'fmj_step_fused': (ctypes.c_int, [_VP, ctypes.POINTER(CData), ctypes.POINTER(CFusedArgs), _VP]),
     'fmj_step_fused_ex': (ctypes.c_int, [_VP, ctypes.POINTER(CData), ctypes.POINTER(CFusedArgs), ctypes.POINTER(CFusedExt), _VP]),
+    'fmj_step_fused_f64': (ctypes.c_int, [_VP, ctypes.POINTER(CData), ctypes.POINTER(CFusedArgs), ctypes.POINTER(CFusedExt), _VP]),
     'fmj_sc': (ctypes.c_int, [ctypes.c_char_p]),
     'fmj_cpg_create': (ctypes.c_int, [ctypes.POINTER(CCpgDesc), ctypes.c_int32, ctypes.POINTER(_VP)]),
     'fmj_cpg_destroy': (None, [_VP]),
@@ -217,7 +218,8 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
 
 
 # queries, and entries only per-env controller parameters call (physics.py / simulation.py tolerate their absence under FMJ_SO)
-OPTIONAL_IN_AB_BASE = ('fmj_solver_info', 'fmj_create_ex', 'fmj_precision', 'fmj_dual_build_info', 'fmj_step_fused_ex', 'fmj_cpg_tape_ex')
+OPTIONAL_IN_AB_BASE = ('fmj_solver_info', 'fmj_create_ex', 'fmj_precision', 'fmj_dual_build_info', 'fmj_step_fused_ex', 'fmj_cpg_tape_ex',
+                       'fmj_step_fused_f64')
 
 
 def load():

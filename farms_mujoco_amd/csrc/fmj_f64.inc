@@ -16,12 +16,20 @@
 //   X       x_i /= D_i, then the root-first sweep a tree level at a time (one barrier per level)
 //   freeze  decided for the workgroup (wg_or) before any lane commits a store; every barrier is reached by all 128 threads
 // No private array is indexed at run time (nothing lives in scratch), no fast reciprocal / rsqrt, no fp32 intermediate.
+//
+// fmj_step_f64_kernel<true> is the fused loop of fmj_step_fused_f64 (include/fmj.h): what fmj_step_wide_kernel<true, ..> does around
+// its steps (fmj_stage_carry_in / step_head / q / f .inc, emit_links_and_drag), in double.  Lane = dof writes the joints row of a full
+// step and evaluates the controller (ctrl tape row of the iteration, or the wave controller with sin); after the forward pass of a
+// step that is not the launch's last, lane = body writes the links row of the next before_step and computes its drag, whose
+// world-frame wrench stays in registers as doubles for the next step's F.  Rows are rounded to fp32 at their store, the state where
+// the launch ends.  Units and water come widened in F64Fused; the fused loop needs no LDS of its own.
 
 #define FMJ_F64_LANES 128
 #define F64_BD 28      // doubles per body: pos(3) mass, quat(4), ipos(3) subtree mass, iquat(4), inertia(3) -, axis(3) qpos0, jnt_pos(3) stiffness
-#define F64_BI 8       // ints per body: parent, joint type (-1 none), qpos address, dof address, subtree size
-#define F64_DI 8       // ints per dof: body, depth, qpos address (-1: a free joint's dof), first actuator, actuator count, joint-sensor slot
+#define F64_BI 8       // ints per body: parent, joint type (-1 none), qpos address, dof address, subtree size, links row (-1 none), swimming slot (-1 none)
+#define F64_DI 8       // ints per dof: body, depth, qpos address (-1: a free joint's dof), first actuator, actuator count, joint-sensor slot, joints row (-1 none)
 #define F64_AD 8       // doubles per actuator (sorted by dof): gain, bias(3), ctrlrange(2), forcerange(2) (infinite where not limited)
+#define F64_SW 10      // doubles per swimming slot: drag coefficients (3 force, 3 torque), mass, height, density, xfrc row
 
 struct F64Model {
   int nbody, nv, nq, nu, rs, jump_rounds, anc_stride, root_free, any_stiffness, implicitfast, nsensordata, njs, maxdep, nround;
@@ -35,6 +43,15 @@ struct F64Model {
   const uint8_t* b_anc;         // [nbody][anc_stride] ancestor body at distance 2^r (DevModel's table)
   const uint8_t* danc;          // [nv][rs] ancestor dof at each depth below the dof's own
   const struct WideRoundW* rounds;   // [nround] elimination rounds, deepest level first
+};
+
+// What only the fused loop reads (a third kernel argument: F64Model and StepArgs keep their places in the kernarg segment).  Units and
+// water arrive as fp32 in the C-ABI and are widened once, on the host; the reciprocals are double divisions.
+struct F64Fused {
+  double inv_meters, inv_velocity, inv_angvel, inv_torques, newtons, torques;
+  double surface, viscosity, wvx, wvy, wvz, wgravity;
+  const double* sw;             // [ns][F64_SW]
+  int n_links, n_joints, n_xfrc;      // rows per env of the three ring tensors
 };
 
 // LDS map, in doubles (ints at the end)
@@ -124,7 +141,55 @@ __device__ __forceinline__ d6 dget6(const double* p) { d6 v = {dmk(p[0], p[1], p
 __device__ __forceinline__ void dput10(double* p, const di10& i) { p[0] = i.i0; p[1] = i.i1; p[2] = i.i2; p[3] = i.i3; p[4] = i.i4; p[5] = i.i5; p[6] = i.i6; p[7] = i.i7; p[8] = i.i8; p[9] = i.i9; }
 __device__ __forceinline__ di10 dget10(const double* p) { di10 i = {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9]}; return i; }
 
-__global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Model FM, const StepArgs A) {
+// emit_links_and_drag (fmj_hip.hip) in double, for lane = body: the links row of iteration `it` (reference physics.py:449-466,435-446)
+// and the drag of a swimming link (drag.pyx:152-268 with com2urdf = identity: physics.py:455-466 fills both quaternions from xquat),
+// its xfrc row and the body's world-frame wrench (xf0..2 force, xf3..5 torque).  The rows are rounded to fp32 at the store.
+__device__ __forceinline__ void f64_emit_links_and_drag(const F64Fused& U, const StepArgs& A, int env, int it, bool isb, int link_row, int swim_slot,
+                                                        d3 xpos, dq xquat, d3 xipos, d3 linvel, d3 angvel,
+                                                        double& xf0, double& xf1, double& xf2, double& xf3, double& xf4, double& xf5) {
+  const int index = it % A.buffer_size;
+  const d3 r_com = dscl(xipos, U.inv_meters), r_urdf = dscl(xpos, U.inv_meters);
+  const d3 r_lin = dscl(linvel, U.inv_velocity), r_ang = dscl(angvel, U.inv_angvel);
+  if (A.do_readout && isb && link_row >= 0) {
+    float* row = A.links + ((size_t)index * A.row_stride_links + (size_t)env * U.n_links * FMJ_LINK_SIZE) + link_row * FMJ_LINK_SIZE;
+    const float qx = (float)xquat.x, qy = (float)xquat.y, qz = (float)xquat.z, qw = (float)xquat.w;      // wxyz -> xyzw (physics.py:458)
+    row[0] = (float)r_com.x; row[1] = (float)r_com.y; row[2] = (float)r_com.z; row[3] = qx; row[4] = qy; row[5] = qz; row[6] = qw;
+    row[7] = (float)r_urdf.x; row[8] = (float)r_urdf.y; row[9] = (float)r_urdf.z; row[10] = qx; row[11] = qy; row[12] = qz; row[13] = qw;
+    row[14] = (float)r_lin.x; row[15] = (float)r_lin.y; row[16] = (float)r_lin.z;
+    row[17] = (float)r_ang.x; row[18] = (float)r_ang.y; row[19] = (float)r_ang.z;
+  }
+  if (!A.do_drag) return;
+  xf0 = xf1 = xf2 = xf3 = xf4 = xf5 = 0.0;
+  if (!isb || swim_slot < 0) return;
+  if (r_com.z > U.surface) return;                                    // drag.pyx:192-194: above the surface, no force and no row
+  const double* sw = U.sw + (size_t)swim_slot * F64_SW;
+  const dm33 R = dq2m(xquat);                                         // link -> world; world -> link is its transpose (drag.pyx:50-63, 235-244)
+  d3 lin = dmk(R.a0 * r_lin.x + R.a3 * r_lin.y + R.a6 * r_lin.z, R.a1 * r_lin.x + R.a4 * r_lin.y + R.a7 * r_lin.z, R.a2 * r_lin.x + R.a5 * r_lin.y + R.a8 * r_lin.z);
+  const d3 ang = dmk(R.a0 * r_ang.x + R.a3 * r_ang.y + R.a6 * r_ang.z, R.a1 * r_ang.x + R.a4 * r_ang.y + R.a7 * r_ang.z, R.a2 * r_ang.x + R.a5 * r_ang.y + R.a8 * r_ang.z);
+  d3 buoy = dmk(0.0, 0.0, 0.0);
+  const double mass = sw[6], height = sw[7], density = sw[8];
+  if (A.use_buoyancy && mass > 0.0 && r_com.z < U.surface) {         // drag.pyx:139-146
+    const double fz = -1000.0 * mass * U.wgravity / density * fmin(fmax(U.surface - r_com.z, 0.0) / height, 1.0);
+    buoy = dmk(R.a6 * fz, R.a7 * fz, R.a8 * fz);
+  }
+  lin = dsub(lin, dmk(R.a0 * U.wvx + R.a3 * U.wvy + R.a6 * U.wvz, R.a1 * U.wvx + R.a4 * U.wvy + R.a7 * U.wvz, R.a2 * U.wvx + R.a5 * U.wvy + R.a8 * U.wvz));
+  d3 f = dmk(fabs(lin.x) * lin.x * (U.viscosity * sw[0]) + buoy.x, fabs(lin.y) * lin.y * (U.viscosity * sw[1]) + buoy.y,
+                   fabs(lin.z) * lin.z * (U.viscosity * sw[2]) + buoy.z);                                  // sign(v) v^2 c visc + buoyancy (drag.pyx:83-88)
+  d3 t = dmk(fabs(ang.x) * ang.x * sw[3], fabs(ang.y) * ang.y * sw[4], fabs(ang.z) * ang.z * sw[5]);   // :104-108
+  // drag.pyx:261-262 rotates both by urdf2com = conj(conj(q) q), a sandwich that multiplies by |q|^4: the identity for a unit quaternion.
+  // Inside a launch |q| is 1 to the last bit of a double; the poses of fmj_data behind the iteration0 row are fp32, |q|^2 is 1 only to
+  // 1e-7 there, and the reference's arithmetic carries that factor into the row (two ulps of the fp32 store)
+  const double qq = xquat.w * xquat.w + xquat.x * xquat.x + xquat.y * xquat.y + xquat.z * xquat.z;
+  f = dscl(f, qq * qq); t = dscl(t, qq * qq);
+  float* xr = A.xfrc + ((size_t)index * A.row_stride_xfrc + (size_t)env * U.n_xfrc * FMJ_XFRC_SIZE) + (int)sw[9] * FMJ_XFRC_SIZE;
+  xr[0] = (float)f.x; xr[1] = (float)f.y; xr[2] = (float)f.z; xr[3] = (float)t.x; xr[4] = (float)t.y; xr[5] = (float)t.z;
+  const d3 fw = dmrot(R, f), tw = dmrot(R, t);
+  xf0 = fw.x * U.newtons; xf1 = fw.y * U.newtons; xf2 = fw.z * U.newtons;
+  xf3 = tw.x * U.torques; xf4 = tw.y * U.torques; xf5 = tw.z * U.torques;
+}
+
+template <bool FUSED>
+__global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Model FM, const StepArgs A, const F64Fused U) {
   extern __shared__ __align__(16) double ldsd[];
   const int env = blockIdx.x;
   const int lane = threadIdx.x;
@@ -160,20 +225,52 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
     for (int i = lane; i < nv; i += FMJ_F64_LANES) { const float v = gv[i]; QV[i] = (double)v; XA[i] = 0.0; if (!(fabsf(v) <= 1e10f)) warn |= FMJ_WARN_BADQVEL; }   // mj_checkVel
   }
   double xf0 = 0.0, xf1 = 0.0, xf2 = 0.0, xf3 = 0.0, xf4 = 0.0, xf5 = 0.0;     // world-frame external force / torque on this body
-  if (A.xfrc_applied && isb) {
+  if (!(FUSED && A.do_drag) && A.xfrc_applied && isb) {      // (the fused drag writes the wrench itself)
     const float* x = A.xfrc_applied + (size_t)env * nb * 6 + bl * 6;
     xf0 = x[0]; xf1 = x[1]; xf2 = x[2]; xf3 = x[3]; xf4 = x[4]; xf5 = x[5];
+  }
+  // fused: what the previous launch left for this one - the motor torque of the joints row (physics.py:510-524)
+  double cy_actsum = 0.0;
+  const int link_row = FUSED ? bip[5] : -1, swim_slot = FUSED ? bip[6] : -1, joint_row = FUSED ? dip[6] : -1;
+  if (FUSED && d_scalar) {
+    const float* sa = A.sensordata + (size_t)env * FM.nsensordata + 6 * (nb - 1) + 3 * FM.njs;
+    for (int a = 0; a < nact; a++) cy_actsum += (double)sa[FM.asrc[act0 + a]] * U.inv_torques;
   }
   // frozen (include/fmj.h): decided for the whole workgroup
   bool frozen = (A.status[env] & FMJ_WARN_FREEZE) != 0;
   frozen = wg_or(warn & FMJ_WARN_FREEZE, FLG + 0) != 0 || frozen;
   int steps_done = 0;
+  if (FUSED && !frozen && A.n_steps > 0) {      // the links row and the drag of iteration0, from the poses and sensors fmj_data holds
+    const int cl = lane < nb ? lane : 0;
+    const float* p = A.xpos + (size_t)env * nb * 3 + cl * 3;
+    const float* q = A.xquat + (size_t)env * nb * 4 + cl * 4;
+    const float* ip = A.xipos + (size_t)env * nb * 3 + cl * 3;
+    const float* sd = A.sensordata + (size_t)env * FM.nsensordata + 6 * (isb ? lane - 1 : 0);
+    const dq cq = {(double)q[0], (double)q[1], (double)q[2], (double)q[3]};
+    f64_emit_links_and_drag(U, A, env, A.iteration0, isb, link_row, swim_slot, dmk(p[0], p[1], p[2]), cq, dmk(ip[0], ip[1], ip[2]),
+                            dmk(sd[0], sd[1], sd[2]), dmk(sd[3], sd[4], sd[5]), xf0, xf1, xf2, xf3, xf4, xf5);
+  }
   __syncthreads();
 
+  int sub = 0, itm = 0;      // fused: the sub-step inside the iteration, iterations completed in this launch
 #pragma unroll 1
   for (int step = 0; step < A.n_steps; step++) {
     if (frozen) break;                          // uniform: every freeze decision is a workgroup OR
     const bool last = step == A.n_steps - 1;
+    // fused: the counters of fmj_stage_step_head.inc: n_steps = iterations x substeps physics steps
+    const int it = A.iteration0 + itm;
+    const int S_sub = FUSED ? A.substeps : 1;
+    const bool full = sub == 0;
+    const int nsub = sub + 1 >= S_sub ? 0 : sub + 1;           // the next physics step: its sub index, whether it is a full step,
+    const bool nfull = nsub == 0;                               // and task.iteration as its before_step will see it: the reference
+    const int nit = (nfull ? it + 1 : it) + ((nsub >= 1 && nsub >= S_sub - 1) ? 1 : 0);   // advances it after sub-step S - 2 (task.py:352-355)
+    // ---- before_step of a full step: the joints row (physics.py:500-524)
+    if (FUSED && A.do_readout && full && d_scalar && joint_row >= 0) {
+      float* row = A.joints + ((size_t)(it % A.buffer_size) * A.row_stride_joints + (size_t)env * U.n_joints * FMJ_JOINT_SIZE) + joint_row * FMJ_JOINT_SIZE;
+      row[0] = (float)QP[d_qadr]; row[1] = (float)(QV[lane] * U.inv_angvel);
+      row[2] = row[3] = row[4] = row[5] = row[6] = row[7] = 0.f;
+      row[8] = (float)cy_actsum; row[9] = row[10] = row[11] = 0.f;
+    }
     // ---- K: local transforms, composed along the chains by pointer jumping through LDS (buffer r & 1)
     const d3 axis = dmk(bdp[20], bdp[21], bdp[22]);
     const d3 jpos = dmk(bdp[24], bdp[25], bdp[26]);
@@ -286,6 +383,12 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
       f.l = dsub(f.l, fw);
       if (lane < nb) { if (!isb) { f.r = f.l = dmk(0.0, 0.0, 0.0); } dput6(CF + lane * 6, f); }
     }
+    // ---- fused: the next before_step's links row and drag from this forward pass (this step's F consumed the wrench above); a
+    // sub-step that writes no row (substep_links off, or task.iteration at the run's n_iterations) keeps the drag force it has
+    if (FUSED && !last && (nfull || (A.sub_links && !(A.n_it_total > 0 && nit >= A.n_it_total)))) {
+      const d3 linvel = dsub(cv.l, dcross(dsub(xi, com), cv.r));
+      f64_emit_links_and_drag(U, A, env, nit, isb, link_row, swim_slot, xp, xq, xi, linvel, cv.r, xf0, xf1, xf2, xf3, xf4, xf5);
+    }
     // ---- sensors and poses of this (pre-integration) state
     if (last && lane < nb) {
       float* p = A.xpos + (size_t)env * nb * 3 + lane * 3; p[0] = (float)xp.x; p[1] = (float)xp.y; p[2] = (float)xp.z;
@@ -326,10 +429,27 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
           const double kst = FM.bd[(size_t)d_body * F64_BD + 27];
           if (kst != 0.0) passive += -kst * (qj - (double)A.qpos_spring[(size_t)env * nq + d_qadr]);
         }
+        // fused: the wave controller (task.py:288-346), amp sin(2 pi frac(f t) + env_phase - lag) with t = iteration x the timestep of an
+        // iteration (task.py:290); every step of an iteration evaluates it at the iteration's own time, so a sub-step holds the full step's ctrl
+        const bool wave = FUSED && A.controller == 1;
+        double cbase = 0.0;
+        const float* w_amp = A.w_amp; const float* w_lag = A.w_lag;
+        if (wave) {
+          w_amp += (size_t)env * A.w_amp_stride; w_lag += (size_t)env * A.w_lag_stride;      // the env's rows (stride 0: the shared row)
+          const double wfreq = A.w_freq_env ? (double)A.w_freq_env[env] : (double)A.w_freq;
+          double cyc = wfreq * ((double)it * (h * (double)S_sub));
+          cyc -= floor(cyc);
+          cbase = 6.283185307179586 * cyc + (double)A.w_env[env];
+        }
         for (int a = 0; a < nact; a++) {              // mj_fwdActuation, joint transmission
           const double* ap = FM.ad + (size_t)(act0 + a) * F64_AD;
           const int src = FM.asrc[act0 + a];
-          double c = A.ctrl ? (double)A.ctrl[(size_t)step * A.ctrl_step_stride + (size_t)env * nu + src] : 0.0;
+          double c;
+          if (wave) {
+            const double amp = (double)w_amp[src];
+            c = amp != 0.0 ? amp * sin(cbase - (double)w_lag[src]) : 0.0;
+            if (last && A.ctrl_out) A.ctrl_out[(size_t)env * nu + src] = (float)c;      // what task.py:288-346 leaves in physics.data.ctrl
+          } else c = A.ctrl ? (double)A.ctrl[(size_t)(FUSED ? itm : step) * A.ctrl_step_stride + (size_t)env * nu + src] : 0.0;   // fused: one ctrl row per iteration
           c = fmin(fmax(c, ap[4]), ap[5]);
           double f = ap[0] * c + ap[1] + ap[2] * qj + ap[3] * qd;
           f = fmin(fmax(f, ap[6]), ap[7]);
@@ -338,6 +458,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
           if (last) A.sensordata[(size_t)env * FM.nsensordata + 6 * (nb - 1) + 3 * FM.njs + src] = (float)f;   // actuatorfrc
           asum += f;
         }
+        if (FUSED) cy_actsum = asum * U.inv_torques;
       }
       qfrc = passive - d6dot(cd, dget6(CS + d_body * 6)) + asum;
     }
@@ -430,6 +551,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
       }
     }
     if (wg_or(warn & FMJ_WARN_BADQPOS, FLG + 4) != 0) frozen = true;   // (its barrier also orders the root update before the next step)
+    if (FUSED) { sub = nsub; itm += nfull ? 1 : 0; }
   }
 
   // ---- store the state: rounded once.  An env that completed no step keeps its buffers as they are.
@@ -447,5 +569,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
   if (w != 0 && lane == 0) A.status[env] |= w;
 }
 
-extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64(void) { return (void*)fmj_step_f64_kernel; }
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64(int fused) {
+  return fused ? (void*)fmj_step_f64_kernel<true> : (void*)fmj_step_f64_kernel<false>;
+}
 #endif  // FMJ_TU_F64

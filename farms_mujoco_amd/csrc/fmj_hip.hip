@@ -1835,7 +1835,7 @@ void* fmj_tu_kernel_20(int, int); void* fmj_tu_kernel_24(int, int); void* fmj_tu
 void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu_kernel_44(int, int); void* fmj_tu_kernel_48(int, int);
 void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
-void* fmj_tu_f64(void);
+void* fmj_tu_f64(int);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -1855,15 +1855,28 @@ struct F64Host {
   size_t lds_bytes = 0;
   std::vector<double> h_ad;      // actuator table mirror (fmj_set_actuator_forcerange)
   std::vector<int> h_asrc;
+  std::vector<int> h_bi, h_di;   // body / dof table mirrors: the rows and swimming slots of the fused loop (fmj_set_readout_maps, fmj_set_swimming)
+  const double* d_sw = nullptr;  // [nbody][F64_SW] the swimming slots in double: allocated once (a body has at most one slot), filled by fmj_set_swimming
 };
+typedef void (*f64_kernel_t)(const F64Model, const StepArgs, const F64Fused);
 
-static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream) {
+// the rows and swimming slots of fmj_ctx's tables (h_b_info2, h_d_info) into the fp64 body / dof tables
+static int sync_f64_maps(fmj_ctx* c) {
+  F64Host& H = *c->f64;
+  for (int b = 0; b < c->nbody; b++) { H.h_bi[(size_t)b * F64_BI + 5] = c->h_b_info2[4 * b + 2]; H.h_bi[(size_t)b * F64_BI + 6] = c->h_b_info2[4 * b + 3]; }
+  for (int d = 0; d < c->nv; d++) H.h_di[(size_t)d * F64_DI + 6] = c->h_d_info[4 * d + 3];
+  HIP_TRY(hipMemcpy((void*)H.fm.bi, H.h_bi.data(), H.h_bi.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy((void*)H.fm.di, H.h_di.data(), H.h_di.size() * sizeof(int), hipMemcpyHostToDevice));
+  return FMJ_OK;
+}
+
+static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream, const F64Fused* f64_fused = nullptr) {
   const DevModel& D = c->dm;
   const int pairs = (c->n_envs + 1) / 2;
   if (c->path == PATH_F64) {
-    if (fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: an fp64 context steps through fmj_step; write the rows with fmj_before_step");
-    typedef void (*f64_kernel_t)(const F64Model, const StepArgs);
-    hipLaunchKernelGGL((f64_kernel_t)fmj_tu_f64(), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream, c->f64->fm, A);
+    if (fused && !f64_fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: an fp64 context steps through fmj_step; write the rows with fmj_before_step");
+    const F64Fused U = f64_fused ? *f64_fused : F64Fused{};      // (the plain step reads none of it)
+    hipLaunchKernelGGL((f64_kernel_t)fmj_tu_f64(fused), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream, c->f64->fm, A, U);
     if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string("fp64 step kernel launch: ") + hipGetErrorString(e));
     return FMJ_OK;
   }
@@ -2576,18 +2589,20 @@ static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
   const std::vector<LaneMask> anc = ancestor_masks(m, 0);
   for (const DepthRound& g : depth_rounds(F.ddepth, 0, 6)) if (g.depth > 0) rw.push_back(round6<WideRoundW>(g, anc));      // a root dof has no ancestor to update
   M.nround = (int)rw.size();
-  H.h_ad = ad; H.h_asrc = asrc;
+  H.h_ad = ad; H.h_asrc = asrc; H.h_bi = bi; H.h_di = di;
   int rc;
+  if ((rc = upload_f64(c, std::vector<double>((size_t)nb * F64_SW, 0.0), &H.d_sw))) return rc;
   if ((rc = upload_f64(c, bd, &M.bd)) || (rc = upload_f64(c, bi, &M.bi)) || (rc = upload_f64(c, dd, &M.dd)) || (rc = upload_f64(c, di, &M.di)) ||
       (rc = upload_f64(c, ad, &M.ad)) || (rc = upload_f64(c, asrc, &M.asrc)) || (rc = upload_f64(c, danc, &M.danc)) || (rc = upload_f64(c, rw, &M.rounds)))
     return rc;
   M.b_anc = D.b_anc;
   H.lds_bytes = (size_t)ldsd_layout(nb, nv, m->nq, M.rs).total_bytes;
   if (H.lds_bytes > 160 * 1024) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: fp64 step kernel LDS above 160 KB");     // (cannot happen within the size limits)
-  if (hipFuncSetAttribute((const void*)fmj_tu_f64(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
-    return set_err(FMJ_ERR_HIP, "fmj_create_ex: LDS request of the fp64 step kernel too large");
+  for (int fused = 0; fused < 2; fused++)
+    if (hipFuncSetAttribute((const void*)fmj_tu_f64(fused), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
+      return set_err(FMJ_ERR_HIP, "fmj_create_ex: LDS request of the fp64 step kernel too large");
   c->path = PATH_F64;
-  return FMJ_OK;
+  return sync_f64_maps(c);      // the default rows; no swimming slots yet
 }
 
 extern "C" {
@@ -2688,6 +2703,17 @@ int fmj_set_swimming(fmj_ctx* c, int32_t ns, int32_t n_xfrc_rows, const int32_t*
   if ((rc = sync_tables(c))) return rc;
   c->dm.ns = ns;
   c->dm.n_xfrc = n_xfrc_rows;       // env stride of the xfrc rows = rows the caller's tensor holds per env
+  if (c->f64) {      // the fused fp64 loop's slots, from the unrounded values
+    if (ns > c->nbody) return set_err(FMJ_ERR_ARG, "fmj_set_swimming: more swimming links than bodies");
+    std::vector<double> sw((size_t)ns * F64_SW, 0.0);
+    for (int s = 0; s < ns; s++) {
+      double* t = &sw[(size_t)s * F64_SW];
+      for (int k = 0; k < 6; k++) t[k] = coefficients[6 * s + k];
+      t[6] = masses[s]; t[7] = heights[s]; t[8] = densities[s]; t[9] = xfrc_index[s];
+    }
+    if (ns) HIP_TRY(hipMemcpy((void*)c->f64->d_sw, sw.data(), sw.size() * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = sync_f64_maps(c))) return rc;
+  }
   return FMJ_OK;
 }
 
@@ -2735,6 +2761,7 @@ int fmj_set_readout_maps(fmj_ctx* c, int32_t n_links, const int32_t* links_body,
   { int rc2 = sync_tables(c); if (rc2) return rc2; }
   c->dm.n_links = n_links; c->dm.n_joints = n_joints;
   { int rc3 = sync_readout_maps(c); if (rc3) return rc3; }
+  if (c->f64) return sync_f64_maps(c);
   return FMJ_OK;
 }
 
@@ -2840,12 +2867,18 @@ int fmj_step_debug(fmj_ctx* c, const fmj_data* d, float* efc_rows, float* pgs_im
 
 int fmj_step_fused(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, void* stream) { return fmj_step_fused_ex(c, d, a, nullptr, stream); }
 
-int fmj_step_fused_ex(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, const fmj_fused_ext* ext, void* stream) {
+// The argument checks of a fused launch and its StepArgs, for fmj_step_fused_ex (precision = FMJ_PRECISION_F32) and fmj_step_fused_f64
+// (FMJ_PRECISION_F64): everything but the contact rows, rows_ahead and the env order, which the two treat differently.
+static int fused_step_args(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, const fmj_fused_ext* ext, int precision, StepArgs* out) {
   if (!c || !a) return set_err(FMJ_ERR_ARG, "fmj_step_fused: NULL argument");
-  StepArgs A; int rc = fill_data(c, d, &A, true); if (rc) return rc;
+  StepArgs& A = *out;
+  int rc = fill_data(c, d, &A, true); if (rc) return rc;
   if (a->n_steps < 0 || a->buffer_size < 1) return set_err(FMJ_ERR_ARG, "fmj_step_fused: bad n_steps/buffer_size");
   if (c->rk4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: the RK4 integrator steps through fmj_step (four forward launches per step); write the rows with fmj_before_step");
-  if (c->precision == FMJ_PRECISION_F64) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: an fp64 context steps through fmj_step (the fp64 step kernel has no fused loop); write the rows with fmj_before_step");
+  if (c->precision != precision)
+    return set_err(FMJ_ERR_UNSUPPORTED, precision == FMJ_PRECISION_F64
+      ? "fmj_step_fused_f64: the context is not an fp64 context (fmj_create_ex with FMJ_PRECISION_F64); an fp32 context fuses through fmj_step_fused"
+      : "fmj_step_fused: an fp64 context steps through fmj_step (the fp64 step kernel has no fused loop); write the rows with fmj_before_step");
   if (c->dm.any_stiffness && !d->qpos_spring) return set_err(FMJ_ERR_ARG, "fmj_step_fused: qpos_spring required");
   if (a->do_readout && (!a->rows_base.links || !a->rows_base.joints)) return set_err(FMJ_ERR_ARG, "fmj_step_fused: readout needs links and joints rows");
   if (a->do_drag && (!a->rows_base.xfrc || c->dm.ns == 0)) return set_err(FMJ_ERR_ARG, "fmj_step_fused: drag needs xfrc rows and fmj_set_swimming");
@@ -2865,15 +2898,20 @@ int fmj_step_fused_ex(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, co
   A.do_drag = a->do_drag; A.controller = a->controller; A.ctrl_step_stride = a->ctrl_step_stride;
   A.row_stride_links = a->row_stride_links; A.row_stride_joints = a->row_stride_joints; A.row_stride_xfrc = a->row_stride_xfrc;
   A.links = a->rows_base.links; A.joints = a->rows_base.joints; A.xfrc = a->rows_base.xfrc;
+  fill_units(&A, &a->units); fill_water(&A, &a->water);
+  A.w_amp = a->wave.amplitude; A.w_lag = a->wave.phase_lag; A.w_env = a->wave.env_phase; A.w_freq = a->wave.frequency;
+  if (ext) { A.w_freq_env = ext->wave_frequency_env; A.w_amp_stride = ext->wave_amplitude_env_stride; A.w_lag_stride = ext->wave_phase_lag_env_stride; }
+  A.ctrl_out = a->controller == 1 ? a->ctrl_out : nullptr;
+  return FMJ_OK;
+}
+
+int fmj_step_fused_ex(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, const fmj_fused_ext* ext, void* stream) {
+  StepArgs A; int rc = fused_step_args(c, d, a, ext, FMJ_PRECISION_F32, &A); if (rc) return rc;
   if (a->rows_base.contacts && a->do_readout) {
     if (!c->dm.cons || !c->d_geom_sensor) return set_err(FMJ_ERR_ARG, "fmj_step_fused: contact rows need a model with collision geoms and fmj_set_contact_maps");
     A.contacts_rows = a->rows_base.contacts; A.row_stride_contacts = a->row_stride_contacts;
     A.n_contact_rows = c->n_contact_rows; A.n_pairs = c->n_pairs; A.geom_sensor = c->d_geom_sensor; A.pairs = c->d_pairs;
   }
-  fill_units(&A, &a->units); fill_water(&A, &a->water);
-  A.w_amp = a->wave.amplitude; A.w_lag = a->wave.phase_lag; A.w_env = a->wave.env_phase; A.w_freq = a->wave.frequency;
-  if (ext) { A.w_freq_env = ext->wave_frequency_env; A.w_amp_stride = ext->wave_amplitude_env_stride; A.w_lag_stride = ext->wave_phase_lag_env_stride; }
-  A.ctrl_out = a->controller == 1 ? a->ctrl_out : nullptr;
   if (a->rows_ahead) {
     if (c->path != PATH_TWO_ENV || A.substeps != 1) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: rows_ahead needs the two-env unconstrained step kernel and substeps = 1 (write the rows with fmj_before_step instead)");
     A.rows_ahead = 1; A.xfrc_applied_out = (float*)d->xfrc_applied;
@@ -2881,6 +2919,21 @@ int fmj_step_fused_ex(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, co
   A.env_order = c->path == PATH_TWO_ENV ? nullptr : a->env_order;      // the two-env constraint kernel pairs neighbours of the order: similar row counts
   HIP_TRY(hipSetDevice(c->device));
   return launch_step(c, true, A, stream);
+}
+
+int fmj_step_fused_f64(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, const fmj_fused_ext* ext, void* stream) {
+  StepArgs A; int rc = fused_step_args(c, d, a, ext, FMJ_PRECISION_F64, &A); if (rc) return rc;
+  if (a->rows_base.contacts) return set_err(FMJ_ERR_ARG, "fmj_step_fused_f64: contact rows: an fp64 model has no collision geoms");
+  if (a->rows_ahead) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused_f64: rows_ahead is not built for the fp64 step kernel (write the rows with fmj_before_step instead)");
+  // units and water, widened once: the reciprocals are double divisions of the widened values
+  F64Fused U = {};
+  const fmj_units& u = a->units; const fmj_water& w = a->water;
+  U.inv_meters = 1.0 / (double)u.meters; U.inv_velocity = 1.0 / (double)u.velocity; U.inv_angvel = 1.0 / (double)u.angular_velocity;
+  U.inv_torques = 1.0 / (double)u.torques; U.newtons = u.newtons; U.torques = u.torques;
+  U.surface = w.surface; U.viscosity = w.viscosity; U.wvx = w.velocity[0]; U.wvy = w.velocity[1]; U.wvz = w.velocity[2]; U.wgravity = w.gravity;
+  U.sw = c->f64->d_sw; U.n_links = c->dm.n_links; U.n_joints = c->dm.n_joints; U.n_xfrc = c->dm.n_xfrc;
+  HIP_TRY(hipSetDevice(c->device));
+  return launch_step(c, true, A, stream, &U);
 }
 
 int fmj_drag(fmj_ctx* c, const fmj_rows* rows, const fmj_water* water, const fmj_units* units, float* xfrc_applied, void* stream) {

@@ -40,12 +40,17 @@ class _MjData(SimpleNamespace):
 class BatchedPhysics:
     """Device-resident mjData for ``n_envs`` copies of one model + the HIP step context."""
 
-    def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None):
+    def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None, fp64_fused: bool = False):
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
         # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
         # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
+        # fp64_fused: fused launches of an fp64 context go through fmj_step_fused_f64 (opt-in: rows and drag in double, the state
+        # rounded to fp32 only where a launch ends, so results differ from the per-iteration fp64 path's; include/fmj.h).
         if precision not in _lib.PRECISIONS:
             raise ValueError(f'precision must be one of {sorted(_lib.PRECISIONS)}, not {precision!r}')
+        if fp64_fused and precision != 'fp64':
+            raise ValueError(f"fp64_fused=True needs precision='fp64', not {precision!r}: an fp32 context fuses through fmj_step_fused")
+        self.fp64_fused = bool(fp64_fused)
         if kernel is not None and not isinstance(kernel, KernelOptions):
             raise TypeError(f'kernel must be a KernelOptions or None, not {kernel!r}')
         if not torch.cuda.is_available():

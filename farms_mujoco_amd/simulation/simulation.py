@@ -83,9 +83,14 @@ def _fused_args(task, phys, n_steps, rows=True, a=None):
 
 
 def _launch_fused(phys, cd, a, ext):
-    """fmj_step_fused, or fmj_step_fused_ex when the controller has a per-env field (include/fmj.h)."""
+    """fmj_step_fused, or fmj_step_fused_ex when the controller has a per-env field, or fmj_step_fused_f64 for a physics made with
+    ``fp64_fused=True`` (include/fmj.h)."""
     stream = _lib.stream_ptr(phys.device)
-    if ext is None:
+    if getattr(phys, 'fp64_fused', False):
+        if not _lib.has('fmj_step_fused_f64'):      # an A/B base build (FMJ_SO)
+            raise _lib.FmjError('this libfmj_hip.so has no fmj_step_fused_f64: fp64_fused=True needs a current build')
+        _lib.check(phys._lib.fmj_step_fused_f64(phys._ctx, ctypes.byref(cd), ctypes.byref(a), None if ext is None else ctypes.byref(ext), stream))
+    elif ext is None:
         _lib.check(phys._lib.fmj_step_fused(phys._ctx, ctypes.byref(cd), ctypes.byref(a), stream))
     else:
         if not _lib.has('fmj_step_fused_ex'):      # an A/B base build (FMJ_SO)
@@ -98,7 +103,8 @@ class Simulation:
 
     ``mjcf_model`` is a compiled :class:`~farms_mujoco_amd.model.Model` (the dm_control MJCF element tree is
     replaced).  Extra kwargs: ``n_envs``, ``device``, ``precision`` ('fp32' | 'fp64': the step kernel's arithmetic,
-    :class:`~farms_mujoco_amd.physics.BatchedPhysics`), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
+    :class:`~farms_mujoco_amd.physics.BatchedPhysics`), ``fp64_fused`` (with 'fp64': fused launches through fmj_step_fused_f64 - rows and
+    drag in double, the state rounded to fp32 where a launch ends, not every iteration, so results differ from the default's), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
     kernels this simulation's context runs).  ``legacy_step`` is accepted for signature
     compatibility; the step is always the full mj_step (legacy_step=False semantics, simulation.py:36-37).
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here
@@ -120,7 +126,8 @@ class Simulation:
         self.pause = not self.options.play
         n_envs = kwargs.pop('n_envs', 1)
         device = kwargs.pop('device', 'cuda:0')
-        self.physics = BatchedPhysics(mjcf_model, n_envs, device, precision=kwargs.pop('precision', 'fp32'), kernel=kwargs.pop('kernel', None))
+        self.physics = BatchedPhysics(mjcf_model, n_envs, device, precision=kwargs.pop('precision', 'fp32'), kernel=kwargs.pop('kernel', None),
+                                      fp64_fused=kwargs.pop('fp64_fused', False))
         self.handle_exceptions = kwargs.pop('handle_exceptions', False)
         # dm_control raises PhysicsError inside the offending step; here the device freezes the offending env at that
         # step (include/fmj.h) and the host looks at the status words every `check_every` steps (one sync each)
@@ -130,9 +137,9 @@ class Simulation:
         self.task = ExperimentTask(base_link=base_link, n_iterations=self.options.n_iterations,
                                    timestep=self.options.timestep, units=self.options.units,
                                    substeps=self.options.num_sub_steps, **kwargs)
-        # RK4 (four forward launches per step, fmj_step) and the fp64 step kernel: no fused launch, the controller is evaluated on the
-        # host path (task.step_control)
-        self.task.host_step_only = self.physics.rk4 or self.physics.precision == 'fp64'
+        # RK4 (four forward launches per step, fmj_step) and the fp64 step kernel without fp64_fused: no fused launch, the controller is
+        # evaluated on the host path (task.step_control)
+        self.task.host_step_only = self.physics.rk4 or (self.physics.precision == 'fp64' and not self.physics.fp64_fused)
         self._needs_reset = True
 
     @property

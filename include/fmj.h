@@ -303,7 +303,8 @@ int fmj_create(const fmj_model* model, int32_t n_envs, int32_t device, fmj_ctx**
  * An fp64 context covers fmj_step (any n_steps, ctrl tape), fmj_forward (disable_actuation included) and fmj_forward_debug (H_rows /
  * qfrc_smooth rounded to fp32 on store), with the Euler and implicitfast integrators.  Refused with FMJ_ERR_UNSUPPORTED and a message
  * containing "fp64": a model with limits, contacts or pairs, the RK4 integrator (both at fmj_create_ex, before the device lookup) and
- * fmj_step_fused (write the rows with fmj_before_step, as with RK4).  The standalone operators (fmj_before_step, fmj_physics2data,
+ * fmj_step_fused / fmj_step_fused_ex (write the rows with fmj_before_step, as with RK4, or opt in to the fused fp64 loop through its own
+ * entry point, fmj_step_fused_f64, whose results differ from the per-iteration ones).  The standalone operators (fmj_before_step, fmj_physics2data,
  * fmj_drag, fmj_contacts2data) work unchanged, in fp32, from the fmj_data fields.  An unknown precision is FMJ_ERR_ARG.
  * size is sizeof(fmj_create_options), or 8 for the struct as it was before the kernel fields (size and precision only); any other
  * size is FMJ_ERR_ARG.
@@ -540,6 +541,23 @@ typedef struct fmj_fused_ext {
   int64_t wave_phase_lag_env_stride;   /* the same for args->wave.phase_lag */
 } fmj_fused_ext;
 int fmj_step_fused_ex(fmj_ctx* ctx, const fmj_data* d, const fmj_fused_args* args, const fmj_fused_ext* ext, void* hip_stream);
+
+/* The fused loop of an fp64 context (opt-in and additive: FMJ_ABI_VERSION stays 6; fmj_step_fused / fmj_step_fused_ex keep refusing an
+ * fp64 context).  Same arguments and the same sequence as fmj_step_fused_ex - rows, drag, controller, sub-steps, the n_iterations end
+ * rule, freeze - with everything between the loads and the stores in double: the state stays in LDS as doubles for the whole launch;
+ * the links, joints and xfrc rows are computed from it in double and rounded to fp32 at their store; the drag (surface test,
+ * buoyancy, water velocity, force and torque laws, rotation to the world frame) is computed in double and its wrench handed to the
+ * next step as doubles; the wave controller is amplitude sin(2 pi frac(frequency t) + env_phase - phase_lag) with the double sin;
+ * units and water are widened once and the reciprocals of the units are double divisions.  qpos, qvel, the poses and sensordata are
+ * rounded to fp32 only where a launch ends.  Results therefore depend on where launches end (a run in chunks of 10 and one in chunks
+ * of 100 differ in the last bits; two runs with the same chunks agree bitwise), and a fused fp64 run is not bit-identical to the
+ * per-iteration one (fmj_before_step + fmj_step), which rounds the state every iteration and computes rows and drag in fp32 - which
+ * is why this is a separate entry point, not a new meaning of fmj_step_fused.  With do_readout = do_drag = 0 the launch reads
+ * fmj_data.xfrc_applied as fmj_step does (a one-step launch with the wave controller is the per-iteration host path's step).
+ * Refused: a context that is not fp64 and rows_ahead != 0 (FMJ_ERR_UNSUPPORTED), rows_base.contacts != NULL (FMJ_ERR_ARG: an fp64
+ * model has no collision geoms), NULL ctx / args (FMJ_ERR_ARG, before any device call) and whatever fmj_step_fused_ex refuses.
+ * env_order is ignored. */
+int fmj_step_fused_f64(fmj_ctx* ctx, const fmj_data* d, const fmj_fused_args* args, const fmj_fused_ext* ext /* may be NULL */, void* hip_stream);
 
 /* ---- on-device controller: a network of amplitude-controlled phase oscillators --------------------
  * The reference only defines the AnimatController interface (task.py:292-346: step/positions/torques/springrefs);

@@ -7,6 +7,8 @@
 # Flags are those of farms_mujoco_amd/_lib.py build() plus --cuda-device-only -S; the digest is taken over the listing without
 # its .file / .ident lines (they name the path and the compiler build) and with the hash in the __hip_cuid_<hash> symbol blanked
 # (hipcc derives it from the source path). MAX_JOBS caps the parallel compiles.
+# A change that adds a kernel to a unit moves that unit's digest; scripts/kernel_body_digest.py then compares the kernels that were
+# already there one by one, from the two listings in OUTDIR.
 set -euo pipefail
 tree=$(cd "${1:-$(dirname "$0")/..}" && pwd)
 out=${2:-$(mktemp -d /tmp/fmj_listing_XXXX)}
