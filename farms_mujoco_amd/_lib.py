@@ -86,6 +86,7 @@ class CCpgDesc(ctypes.Structure):
                 ('out_a', _I), ('out_b', _I), ('out_gain', _D), ('out_offset', _D)]
 
 
+CPG_MAX_OSC = 256      # FMJ_CPG_MAX_OSC of include/fmj.h: the largest oscillator network fmj_cpg_create accepts
 CPG_ENV_ARRAYS = ('drive', 'omega', 'rate', 'amplitude', 'conn_weight', 'conn_bias', 'out_gain', 'out_offset')
 
 

@@ -134,13 +134,10 @@ class OscillatorNetwork:
         return d
 
 
-def salamander_network(model, frequency=1.0, amplitude=0.15, n_wave=1.0, limb_amplitude=0.15, rate=20.0,
-                       weight=30.0):
-    """Double-chain salamander CPG on the axial joints (left/right oscillator per ``joint_body_*``: ascending and
-    descending nearest-neighbour couplings with the travelling-wave phase bias, antiphase contralateral couplings)
-    plus one oscillator pair per limb coupled to the axial oscillator at its girdle and to the diagonal limb.
-    Axial outputs drive the position actuators with r_L (1 + cos th_L) - r_R (1 + cos th_R); each limb drives the
-    position actuator of its ``_0`` joint.  Amplitude 0.15 gives a 0.3 rad joint swing."""
+def _chain_and_limbs_network(model, girdle_of, frequency, amplitude, n_wave, limb_amplitude, rate, weight):
+    """The double chain on the ``joint_body_*`` joints plus one oscillator pair per limb (the joints ``joint_leg_*`` that share a name
+    up to the last ``_k``), the pair's first oscillator coupled with bias pi to the axial oscillator, on the limb's side (``_L`` = 0,
+    ``_R`` = 1), of axial joint ``girdle_of(limb, n_axial)``."""
     axial = [j for j, n in enumerate(model.joint_names) if n.startswith('joint_body_')]
     na = len(axial)
     limbs = sorted({n.rsplit('_', 1)[0] for n in model.joint_names if n.startswith('joint_leg_')})
@@ -159,7 +156,7 @@ def salamander_network(model, frequency=1.0, amplitude=0.15, n_wave=1.0, limb_am
     for li, name in enumerate(limbs):
         a, b = 2*na + 2*li, 2*na + 2*li + 1
         con.append((a, b, weight, np.pi)); con.append((b, a, weight, np.pi))
-        girdle = 0 if 'front' in name else min(na - 1, na//2)
+        girdle = girdle_of(name, na)
         side = 0 if name.endswith('_L') else 1
         con.append((a, 2*girdle + side, weight, np.pi))                         # limb swings against its body side
     out = []
@@ -179,15 +176,41 @@ def salamander_network(model, frequency=1.0, amplitude=0.15, n_wave=1.0, limb_am
     for k in range(na):
         ph0[2*k] = -k*bias; ph0[2*k + 1] = -k*bias + np.pi
     for li, name in enumerate(limbs):
-        girdle = 0 if 'front' in name else min(na - 1, na//2)
+        girdle = girdle_of(name, na)
         side = 0 if name.endswith('_L') else 1
         ph0[2*na + 2*li] = ph0[2*girdle + side] + np.pi; ph0[2*na + 2*li + 1] = ph0[2*girdle + side]
     return OscillatorNetwork(freq, rt, amp, con, out, initial_phase=(ph0 + np.pi) % (2*np.pi) - np.pi)
 
 
+def salamander_network(model, frequency=1.0, amplitude=0.15, n_wave=1.0, limb_amplitude=0.15, rate=20.0,
+                       weight=30.0):
+    """Double-chain salamander CPG on the axial joints (left/right oscillator per ``joint_body_*``: ascending and
+    descending nearest-neighbour couplings with the travelling-wave phase bias, antiphase contralateral couplings)
+    plus one oscillator pair per limb coupled to the axial oscillator at its girdle and to the diagonal limb.
+    Axial outputs drive the position actuators with r_L (1 + cos th_L) - r_R (1 + cos th_R); each limb drives the
+    position actuator of its ``_0`` joint.  Amplitude 0.15 gives a 0.3 rad joint swing."""
+    return _chain_and_limbs_network(model, lambda name, na: 0 if 'front' in name else min(na - 1, na//2), frequency, amplitude, n_wave,
+                                    limb_amplitude, rate, weight)
+
+
+def axial_limb_network(model, frequency=1.0, amplitude=0.15, n_wave=1.0, limb_amplitude=0.15, rate=20.0, weight=30.0):
+    """``salamander_network``'s double chain for a body with any number of limbs (a centipede: forty legs; an eel: none): each limb's
+    pair couples to the axial oscillator of the joint that moves the segment the limb is mounted on - the parent body of the limb's
+    ``_0`` joint - where ``salamander_network`` knows two girdles only.  Limbs on the root segment, which no axial joint moves, follow
+    the first axial joint.  Two oscillators per axial joint and per limb: centipede() 70, eel(48) 96, centipede(20, 25) 130 (at most
+    ``_lib.CPG_MAX_OSC``).  Outputs and ``initial_phase`` as in ``salamander_network``."""
+    names = list(model.joint_names)
+    axial_of_body = {int(model.jnt_bodyid[j]): k for k, j in enumerate(j for j, n in enumerate(names) if n.startswith('joint_body_'))}
+
+    def girdle_of(limb, na):
+        segment = int(model.body_parentid[model.jnt_bodyid[names.index(limb + '_0')]])
+        return axial_of_body.get(segment, 0)
+    return _chain_and_limbs_network(model, girdle_of, frequency, amplitude, n_wave, limb_amplitude, rate, weight)
+
+
 class NetworkController(AnimatController):
     """AnimatController (reference task.py:292-346) whose joint position commands come from an OscillatorNetwork
-    integrated on the device by ``fmj_cpg_tape``.  ``fusable``: a chunk of the fused loop asks for its
+    of at most ``_lib.CPG_MAX_OSC`` oscillators, integrated on the device by ``fmj_cpg_tape``.  ``fusable``: a chunk of the fused loop asks for its
     ctrl tape up front (``ctrl_tape``), so no host work or host->device copy remains per step.  ``drive`` ([n_envs],
     optional) scales the intrinsic frequencies per env.  ``env_params`` gives every env its own numbers on the network's topology
     (``fmj_cpg_tape_ex``): a dict with any of ``frequency``, ``rate``, ``amplitude`` ([n_envs, n_osc]), ``conn_weight``,

@@ -3036,15 +3036,20 @@ struct fmj_cpg {
   float4* out;      // [nu] a (bits), b (bits), gain, offset
 };
 
-// the env's own parameters (fmj_cpg_env_params; DEVICE pointers by value): a NULL array is the shared table, decided per array for the whole wave
+// the env's own parameters (fmj_cpg_env_params; DEVICE pointers by value): a NULL array is the shared table, decided per array for the whole block
 struct CpgEnv { const float *drive, *omega, *rate, *amplitude, *conn_weight, *conn_bias, *out_gain, *out_offset; };
 
-__global__ void __launch_bounds__(64) fmj_cpg_kernel(const int n_osc, const int n_conn, const int nu, const float4* __restrict__ osc,
+// One env per workgroup of BLOCK = 64 ceil(n_osc / 64) threads, thread = oscillator (threads past n_osc own none and only take part in
+// the barriers and the output loop).  One text for BLOCK = 64, 128, 192, 256: what a thread computes for its oscillator does not
+// depend on BLOCK or on the thread's index, and a network of at most 64 oscillators runs the one-wave instantiation.
+extern "C++" template <int BLOCK>
+__global__ void __launch_bounds__(BLOCK) fmj_cpg_kernel(const int n_osc, const int n_conn, const int nu, const float4* __restrict__ osc,
                                                      const int* __restrict__ row, const float4* __restrict__ conn, const int* __restrict__ perm,
                                                      const float4* __restrict__ outp, const int n_envs, const int n_steps,
                                                      const float h, float* phase, float* amp, float* damp,
                                                      const CpgEnv E, float* tape) {
-  __shared__ float TH[64], RR[64];
+  static_assert(BLOCK % 64 == 0 && BLOCK >= 64 && BLOCK <= FMJ_CPG_MAX_OSC, "whole waves, at most one thread per oscillator of the largest network");
+  __shared__ float TH[BLOCK], RR[BLOCK];      // n_osc <= BLOCK: every index read below (a connection's source, an output's oscillator) is < n_osc
   const int env = blockIdx.x, lane = threadIdx.x;
   const bool iso = lane < n_osc;
   const int ol = iso ? lane : 0;
@@ -3060,7 +3065,7 @@ __global__ void __launch_bounds__(64) fmj_cpg_kernel(const int n_osc, const int 
     TH[lane] = th; RR[lane] = r;
     __syncthreads();
     float* t = tape + ((size_t)s * n_envs + env) * nu;
-    for (int u = lane; u < nu; u += 64) {
+    for (int u = lane; u < nu; u += BLOCK) {
       float4 q = outp[u];
       if (E.out_gain) q.z = E.out_gain[eu + u];
       if (E.out_offset) q.w = E.out_offset[eu + u];
@@ -3089,7 +3094,7 @@ __global__ void __launch_bounds__(64) fmj_cpg_kernel(const int n_osc, const int 
 }
 
 int fmj_cpg_create(const fmj_cpg_desc* d, int32_t device, fmj_cpg** out) {
-  if (!d || !out || d->n_osc < 1 || d->n_osc > 64 || d->n_conn < 0 || d->nu < 1) return set_err(FMJ_ERR_ARG, "fmj_cpg_create: need 1..64 oscillators, nu >= 1");
+  if (!d || !out || d->n_osc < 1 || d->n_osc > FMJ_CPG_MAX_OSC || d->n_conn < 0 || d->nu < 1) return set_err(FMJ_ERR_ARG, "fmj_cpg_create: need 1..256 oscillators, nu >= 1");
   if (!d->frequency || !d->rate || !d->amplitude || !d->out_a || !d->out_b || !d->out_gain || !d->out_offset ||
       (d->n_conn && (!d->conn_to || !d->conn_from || !d->conn_weight || !d->conn_bias))) return set_err(FMJ_ERR_ARG, "fmj_cpg_create: NULL array");
   for (int k = 0; k < d->n_conn; k++)
@@ -3147,8 +3152,15 @@ int fmj_cpg_tape_ex(fmj_cpg* c, int32_t n_envs, int32_t n_steps, double timestep
   CpgEnv E = {};
   if (p) E = CpgEnv{p->drive, p->omega, p->rate, p->amplitude, p->conn_weight, p->conn_bias, p->out_gain, p->out_offset};
   HIP_TRY(hipSetDevice(c->device));
-  hipLaunchKernelGGL(fmj_cpg_kernel, dim3(n_envs), dim3(64), 0, (hipStream_t)stream, c->n_osc, c->n_conn, c->nu, c->osc, c->row, c->conn, c->perm, c->out,
-                     n_envs, n_steps, (float)timestep, phase, amp, damp, E, ctrl_tape);
+#define FMJ_CPG_LAUNCH(BLOCK) hipLaunchKernelGGL(fmj_cpg_kernel<BLOCK>, dim3(n_envs), dim3(BLOCK), 0, (hipStream_t)stream, c->n_osc, c->n_conn, c->nu, c->osc, \
+                                                 c->row, c->conn, c->perm, c->out, n_envs, n_steps, (float)timestep, phase, amp, damp, E, ctrl_tape)
+  switch ((c->n_osc + 63) / 64) {      // fmj_cpg_create: 1 <= n_osc <= FMJ_CPG_MAX_OSC
+    case 1: FMJ_CPG_LAUNCH(64); break;
+    case 2: FMJ_CPG_LAUNCH(128); break;
+    case 3: FMJ_CPG_LAUNCH(192); break;
+    default: FMJ_CPG_LAUNCH(256); break;
+  }
+#undef FMJ_CPG_LAUNCH
   HIP_TRY(hipGetLastError());
   return FMJ_OK;
 }

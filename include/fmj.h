@@ -564,12 +564,17 @@ int fmj_step_fused_f64(fmj_ctx* ctx, const fmj_data* d, const fmj_fused_args* ar
  * the oscillator networks themselves live in its callers (farms_amphibious). This is the batched device counterpart:
  *   theta_i' = 2 pi f_i + sum_k r_j(k) w_k sin(theta_j(k) - theta_i - phi_k)      (connections k into i)
  *   r_i''    = a_i (a_i / 4 (R_i - r_i) - r_i')
- * integrated with explicit Euler at the physics timestep, one wave per env, lane = oscillator (n_osc <= 64).
+ * integrated with explicit Euler at the physics timestep, one workgroup of 64 ceil(n_osc / 64) threads per env, thread = oscillator
+ * (n_osc <= FMJ_CPG_MAX_OSC: two oscillators per dof at the model limit nv <= 128).  A network of at most 64 oscillators runs on one
+ * wave; a larger one on 2, 3 or 4 waves that exchange phases and amplitudes through LDS at two workgroup barriers per step.  What is
+ * computed for an oscillator (its incoming connections in the descriptor's order, the Euler update, the phase wrap) does not depend on
+ * the number of waves or on the oscillator's index: disconnected sub-networks integrate exactly as each would alone.
  * Output u of nu:  ctrl_u = gain_u (r_a (1 + cos theta_a) - r_b (1 + cos theta_b)) + offset_u   (b < 0: single-sided)
  * fmj_cpg_tape advances the network n_steps and writes ctrl_tape[s][env][u] of the state BEFORE each step, which is
  * exactly what fmj_step / fmj_step_fused consume as a ctrl tape (controller 0, ctrl_step_stride = n_envs * nu). */
+#define FMJ_CPG_MAX_OSC 256
 typedef struct fmj_cpg_desc {
-  int32_t n_osc, n_conn, nu;
+  int32_t n_osc, n_conn, nu;  /* 1 <= n_osc <= FMJ_CPG_MAX_OSC (FMJ_ERR_ARG otherwise, before any device call); n_conn >= 0, nu >= 1: no upper limit */
   const double* frequency;    /* [n_osc] Hz */
   const double* rate;         /* [n_osc] a_i */
   const double* amplitude;    /* [n_osc] R_i */
