@@ -75,6 +75,11 @@ class CCreateOptions(ctypes.Structure):
     _fields_ = [('size', ctypes.c_int32), ('precision', ctypes.c_int32), ('kernel_flags', ctypes.c_int32), ('dual_wps', ctypes.c_int32)]
 
 
+class CCreateExt(ctypes.Structure):      # fmj_create_ext (fmj_create_ex2)
+    _fields_ = [('size', ctypes.c_int32), ('flags', ctypes.c_int32)]
+
+
+CREATE_F64_LIMITS = 1      # FMJ_CREATE_F64_LIMITS of include/fmj.h
 PRECISIONS = {'fp32': 0, 'fp64': 1}      # FMJ_PRECISION_* of include/fmj.h
 KERNEL_TWO_WAVE, KERNEL_ONE_ENV_PER_WAVE, KERNEL_NO_LEAN, KERNEL_NO_PRIO = 1, 2, 4, 8      # FMJ_KERNEL_* of include/fmj.h ("Kernel selection" at fmj_create_ex)
 
@@ -97,6 +102,8 @@ class CCpgEnvParams(ctypes.Structure):      # fmj_cpg_env_params: per-env networ
 SYMBOLS = {
     'fmj_create': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_VP)]),
     'fmj_create_ex': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(CCreateOptions), ctypes.POINTER(_VP)]),
+    'fmj_create_ex2': (ctypes.c_int, [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(CCreateOptions), ctypes.POINTER(CCreateExt),
+                                      ctypes.POINTER(_VP)]),
     'fmj_precision': (ctypes.c_int, [_VP]),
     'fmj_destroy': (None, [_VP]),
     'fmj_last_error': (ctypes.c_char_p, []),
@@ -170,12 +177,13 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
         jobs = [(os.path.join(objdir, 'host.o'), [])] + [(os.path.join(objdir, f'k{n}.o'), [f'-DFMJ_TU_MAXD={n}'])
                                                          for n in range(4, 65, 4)]      # 36 .. 64: the unconstrained one-env kernel only
         jobs += [(os.path.join(objdir, f'kw{n}.o'), [f'-DFMJ_TU_WIDE={n}']) for n in (32, 64)]      # the two-wave kernel (csrc/fmj_wide.inc)
-        f64_job = (os.path.join(objdir, 'kf64.o'), ['-DFMJ_TU_F64'])      # the fp64 step kernel (csrc/fmj_f64.inc)
+        f64_jobs = [(os.path.join(objdir, 'kf64.o'), ['-DFMJ_TU_F64']),      # the fp64 step kernel (csrc/fmj_f64.inc)
+                    (os.path.join(objdir, 'kf64l.o'), ['-DFMJ_TU_F64=2'])]   # its instantiations with joint limits (fmj_create_ex2)
         if dev:
-            todo = [j for j in jobs if not j[1] or int(j[1][0].split('=')[1]) in dev or not os.path.exists(j[0])] + [f64_job]
-            jobs.append(f64_job)
+            todo = [j for j in jobs if not j[1] or int(j[1][0].split('=')[1]) in dev or not os.path.exists(j[0])] + f64_jobs
+            jobs += f64_jobs
         else:
-            jobs.append(f64_job)
+            jobs += f64_jobs
             todo = jobs
 
         def cc(job):
@@ -220,7 +228,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
 
 # queries, and entries only per-env controller parameters call (physics.py / simulation.py tolerate their absence under FMJ_SO)
 OPTIONAL_IN_AB_BASE = ('fmj_solver_info', 'fmj_create_ex', 'fmj_precision', 'fmj_dual_build_info', 'fmj_step_fused_ex', 'fmj_cpg_tape_ex',
-                       'fmj_step_fused_f64')
+                       'fmj_step_fused_f64', 'fmj_create_ex2')
 
 
 def load():

@@ -23,6 +23,21 @@
 // step that is not the launch's last, lane = body writes the links row of the next before_step and computes its drag, whose
 // world-frame wrench stays in registers as doubles for the next step's F.  Rows are rounded to fp32 at their store, the state where
 // the launch ends.  Units and water come widened in F64Fused; the fused loop needs no LDS of its own.
+//
+// fmj_step_f64_kernel<.., true> (fmj_create_ex2 with FMJ_CREATE_F64_LIMITS) adds joint limits, solved exactly.  Lane = dof owns the
+// up-to-two rows of its joint (oracle make_constraints, EFC_LIMIT: J = -side e_dof, so J M^-1 J' is never formed).  A step with no
+// candidate row (dist < margin nowhere in the env: one wg_or) is the step above, bit for bit.  Otherwise the step minimises
+//   0.5 (a - a_s)' M (a - a_s) + sum_e s_e(J_e a - aref_e),   s_e(x) = 0.5 x^2 / R_e for x < 0, else 0      (oracle solve_primal)
+// by Newton's method from a_s = M^-1 qfrc_smooth.  The Newton matrix M + sum_active e_d e_d' / R_e is M with a larger diagonal, so each
+// iteration refills the lane's row of HR from CR / CD (the M stage without h B, plus the lane's active 1 / R) and runs the L rounds and
+// the X sweep again: no second copy of H.  With p = -(M + D_S)^-1 g one has M p = -g - D_S p, and r = M (a - a_s) is carried along the
+// iterates: no product with M.  The line search is exact along the piecewise-quadratic cost (primal_linesearch: Newton on phi' from
+// alpha = 0 until it changes sign, then Newton safeguarded by the bracket); each lane evaluates its own rows and the sums go through
+// wg_sum4.  The loop ends when a step leaves the active set unchanged (the iterate is then the minimiser of the quadratic of that set),
+// at the oracle's gradient tolerance, or after solver_iterations iterations.  Then, as dual_finish and euler() do: f_e = -x_e / R_e on
+// the active rows, qfrc_constraint = J' f, and one more fill and factorisation of M + h B solved with qfrc_smooth + qfrc_constraint
+// (the constrained qacc itself when nothing is damped).  Every new branch is decided from a workgroup reduction: it is uniform, and every
+// barrier is reached by all 128 threads.
 
 #define FMJ_F64_LANES 128
 #define F64_BD 28      // doubles per body: pos(3) mass, quat(4), ipos(3) subtree mass, iquat(4), inertia(3) -, axis(3) qpos0, jnt_pos(3) stiffness
@@ -30,6 +45,7 @@
 #define F64_DI 8       // ints per dof: body, depth, qpos address (-1: a free joint's dof), first actuator, actuator count, joint-sensor slot, joints row (-1 none)
 #define F64_AD 8       // doubles per actuator (sorted by dof): gain, bias(3), ctrlrange(2), forcerange(2) (infinite where not limited)
 #define F64_SW 10      // doubles per swimming slot: drag coefficients (3 force, 3 torque), mass, height, density, xfrc row
+#define F64_LM 12      // doubles per dof of a limits context: limited (0 / 1), range(2), margin, solref(2), solimp(5), dof_invweight0
 
 struct F64Model {
   int nbody, nv, nq, nu, rs, jump_rounds, anc_stride, root_free, any_stiffness, implicitfast, nsensordata, njs, maxdep, nround;
@@ -54,6 +70,14 @@ struct F64Fused {
   int n_links, n_joints, n_xfrc;      // rows per env of the three ring tensors
 };
 
+// What only the LIMITS instantiations read (a fourth kernel argument, for the same reason).  The tolerances and the iteration budgets
+// are the model's (solver_tolerance, ls_tolerance, solver_iterations, ls_iterations); scale = 1 / (meaninertia max(1, nv)).
+struct F64Limits {
+  int solver_iterations, ls_iterations;
+  double tolerance, ls_tolerance, scale;
+  const double* lm;             // [nv][F64_LM]
+};
+
 // LDS map, in doubles (ints at the end)
 struct LdsLayoutD { int QP, QV, XA, XCH, CD, CI, CR, CF, CS, MX, HR, XW, FLG, total_bytes; };
 __host__ __device__ inline LdsLayoutD ldsd_layout(int nb, int nv, int nq, int rs) {
@@ -73,6 +97,12 @@ __host__ __device__ inline LdsLayoutD ldsd_layout(int nb, int nv, int nq, int rs
   L.FLG = o; o += 4;                          // wg_or slots (8 ints)
   L.total_bytes = o * 8;
   return L;
+}
+
+// What the LIMITS instantiations append to the map: two alternating buffers of 2 waves x 4 sums (wg_sum4) and 8 more wg_or ints
+#define F64_LIMITS_LDS_DOUBLES 20
+__host__ __device__ inline int ldsd_total_bytes(int nb, int nv, int nq, int rs, int limits) {
+  return ldsd_layout(nb, nv, nq, rs).total_bytes + (limits ? F64_LIMITS_LDS_DOUBLES * 8 : 0);
 }
 
 #ifdef FMJ_TU_F64
@@ -188,8 +218,53 @@ __device__ __forceinline__ void f64_emit_links_and_drag(const F64Fused& U, const
   xf3 = tw.x * U.torques; xf4 = tw.y * U.torques; xf5 = tw.z * U.torques;
 }
 
-template <bool FUSED>
-__global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Model FM, const StepArgs A, const F64Fused U) {
+// Sums of four doubles over the workgroup, on every lane and bitwise the same on every lane (a butterfly per wave, then wave 0 + wave 1).
+// buf: 8 doubles; consecutive calls alternate between two buffers, so one barrier per call is enough: a lane still reading buffer A
+// has not reached the barrier of the call that writes B, and A is rewritten only after that barrier.
+__device__ __forceinline__ void wg_sum4(double& s0, double& s1, double& s2, double& s3, double* buf) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o, 64); s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); s3 += __shfl_xor(s3, o, 64); }
+  if ((threadIdx.x & 63) == 0) { double* b = buf + (threadIdx.x >> 6) * 4; b[0] = s0; b[1] = s1; b[2] = s2; b[3] = s3; }
+  __syncthreads();
+  s0 = buf[0] + buf[4]; s1 = buf[1] + buf[5]; s2 = buf[2] + buf[6]; s3 = buf[3] + buf[7];
+}
+
+// One candidate limit row (oracle make_constraints: get_impedance, mj_makeImpedance, mj_referenceConstraint): D = 1 / R and aref from
+// the row's pos = dist, vel = J qvel.  lm: the dof's F64_LM doubles.
+#define F64_MINVAL 1e-15
+#define F64_MINIMP 0.0001
+#define F64_MAXIMP 0.9999
+__device__ __forceinline__ void f64_limit_row(const double* lm, double h, double pos, double vel, double& D, double& aref) {
+  const double margin = lm[3], sr0 = lm[4], sr1 = lm[5];
+  const double dmin = fmin(fmax(lm[6], F64_MINIMP), F64_MAXIMP), dmax = fmin(fmax(lm[7], F64_MINIMP), F64_MAXIMP);
+  const double width = fmax(0.0, lm[8]), mid = fmin(fmax(lm[9], F64_MINIMP), F64_MAXIMP), power = fmax(1.0, lm[10]);
+  double imp;
+  if (dmin == dmax || width <= F64_MINVAL) imp = 0.5 * (dmin + dmax);
+  else {
+    const double xx = fabs((pos - margin) / width);
+    double y;
+    if (xx >= 1.0) y = 1.0;
+    else if (xx <= 0.0) y = 0.0;
+    else if (power == 1.0) y = xx;
+    else if (xx <= mid) y = pow(xx, power) / pow(mid, power - 1.0);
+    else y = 1.0 - pow(1.0 - xx, power) / pow(1.0 - mid, power - 1.0);
+    imp = dmin + y * (dmax - dmin);
+  }
+  double K, B;
+  if (sr0 > 0.0) {
+    const double tc = fmax(sr0, 2.0 * h);
+    K = 1.0 / fmax(F64_MINVAL, dmax * dmax * tc * tc * sr1 * sr1);
+    B = 2.0 / fmax(F64_MINVAL, dmax * tc);
+  } else { K = -sr0 / fmax(F64_MINVAL, dmax * dmax); B = -sr1 / fmax(F64_MINVAL, dmax); }
+  D = 1.0 / fmax(F64_MINVAL, (1.0 - imp) * lm[11] / imp);
+  aref = -B * vel - K * imp * (pos - margin);
+}
+
+// A point of the line search (oracle ls_pt): the cost along the search line and its first two derivatives
+struct F64LsPt { double alpha, cost, d0, d1; };
+
+template <bool FUSED, bool LIMITS>
+__global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Model FM, const StepArgs A, const F64Fused U, const F64Limits LM) {
   extern __shared__ __align__(16) double ldsd[];
   const int env = blockIdx.x;
   const int lane = threadIdx.x;
@@ -200,6 +275,9 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
   double* CD = ldsd + L.CD; double* CI = ldsd + L.CI; double* CR = ldsd + L.CR; double* CF = ldsd + L.CF; double* CS = ldsd + L.CS;
   double* MX = ldsd + L.MX; double* HR = ldsd + L.HR; double* XW = ldsd + L.XW;
   int* FLG = (int*)(ldsd + L.FLG);
+  double* SUM = ldsd + L.total_bytes / 8; int* FLX = (int*)(SUM + 16);      // LIMITS only: past the map (ldsd_total_bytes)
+  int sumpar = 0;
+#define WG_SUM4(a_, b_, c_, d_) do { wg_sum4(a_, b_, c_, d_, SUM + sumpar * 8); sumpar ^= 1; } while (0)
 
   const bool isb = lane > 0 && lane < nb;
   const int bl = isb ? lane : 0;
@@ -215,6 +293,8 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
   const bool d_scalar = isd && d_qadr >= 0;
   const double d_arm = FM.dd[2 * dl], d_damp = FM.dd[2 * dl + 1];
   const double h = FM.h;
+  const double* lmp = LIMITS ? LM.lm + (size_t)dl * F64_LM : nullptr;
+  const bool lim_on = LIMITS && d_scalar && lmp[0] != 0.0;
 
   // ---- load the state: widened once
   int warn = 0;
@@ -236,6 +316,9 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
     const float* sa = A.sensordata + (size_t)env * FM.nsensordata + 6 * (nb - 1) + 3 * FM.njs;
     for (int a = 0; a < nact; a++) cy_actsum += (double)sa[FM.asrc[act0 + a]] * U.inv_torques;
   }
+  double cy_limfrc = 0.0;      // fused: the carried joint-limit force of the joints row (physics.py:484-487)
+  if (FUSED && LIMITS && lim_on) cy_limfrc = (double)A.sensordata[(size_t)env * FM.nsensordata + 6 * (nb - 1) + 3 * d_slot + 2] * U.inv_torques;
+  double ws_qacc = 0.0;        // limits: the constrained qacc of the launch's last step (the next warm start, as mj_step saves it)
   // frozen (include/fmj.h): decided for the whole workgroup
   bool frozen = (A.status[env] & FMJ_WARN_FREEZE) != 0;
   frozen = wg_or(warn & FMJ_WARN_FREEZE, FLG + 0) != 0 || frozen;
@@ -269,7 +352,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
       float* row = A.joints + ((size_t)(it % A.buffer_size) * A.row_stride_joints + (size_t)env * U.n_joints * FMJ_JOINT_SIZE) + joint_row * FMJ_JOINT_SIZE;
       row[0] = (float)QP[d_qadr]; row[1] = (float)(QV[lane] * U.inv_angvel);
       row[2] = row[3] = row[4] = row[5] = row[6] = row[7] = 0.f;
-      row[8] = (float)cy_actsum; row[9] = row[10] = row[11] = 0.f;
+      row[8] = (float)cy_actsum; row[9] = LIMITS ? (float)cy_limfrc : 0.f; row[10] = row[11] = 0.f;
     }
     // ---- K: local transforms, composed along the chains by pointer jumping through LDS (buffer r & 1)
     const d3 axis = dmk(bdp[20], bdp[21], bdp[22]);
@@ -462,22 +545,47 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
       }
       qfrc = passive - d6dot(cd, dget6(CS + d_body * 6)) + asum;
     }
+    // ---- limits: the candidate rows of the lane's joint (oracle make_constraints): lo is side -1 (J = +1), hi is side +1 (J = -1)
+    bool c_lo = false, c_hi = false;
+    double D_lo = 0.0, D_hi = 0.0, ar_lo = 0.0, ar_hi = 0.0;
+    int lflags = 0;      // workgroup: 1 = some row is a candidate, 2 = some dof is damped
+    if (LIMITS) {
+      if (lim_on) {
+        const double qj = QP[d_qadr], qd = QV[lane];
+        const double dist_lo = qj - lmp[1], dist_hi = lmp[2] - qj;
+        c_lo = dist_lo < lmp[3]; c_hi = dist_hi < lmp[3];
+        if (c_lo) f64_limit_row(lmp, h, dist_lo, qd, D_lo, ar_lo);
+        if (c_hi) f64_limit_row(lmp, h, dist_hi, -qd, D_hi, ar_hi);
+      }
+      lflags = wg_or(((c_lo || c_hi) ? 1 : 0) | ((isd && bdamp != 0.0) ? 2 : 0), FLX + 0);
+    }
+    // The solve below runs once in a step without candidate rows (phase 2: M + h B, qfrc_smooth).  With candidate rows it runs for
+    // a_s (phase 0: M), once per Newton iteration (phase 1: M + D_S, the gradient), and once more for the damped step (phase 2).
+    int phase = 2, nt_iter = 0;
+    double hb = bdamp, dadd = 0.0, rhs = isd ? qfrc : 0.0;
+    double nt_a = 0.0, nt_as = 0.0, nt_r = 0.0, nt_g = 0.0, nt_qfc = 0.0, lim_f = 0.0;      // a, a_s, M (a - a_s), gradient, J' f, the joint's limit force
+    bool act_lo = false, act_hi = false;
+    if (LIMITS && (lflags & 1) != 0) { phase = 0; hb = 0.0; }
+    const d6 buf = dinert_mul(dget10(CR + d_body * 10), cd);
+    double x;
+#pragma unroll 1
+    for (;;) {      // (the stages below keep the indentation they had before the loop was put around them)
     // ---- M: row i of H (mj_crb, then mj_Euler's M + h B), H[i][j] at column depth(j)
     {
-      const d6 buf = dinert_mul(dget10(CR + d_body * 10), cd);
       if (isd) {
         double* row = HR + lane * rs;
         const uint8_t* an = FM.danc + (size_t)lane * rs;
         for (int d = 0; d < ddepth; d++) row[d] = d6dot(dget6(CD + (int)an[d] * 6), buf);
-        row[ddepth] = (d_arm + d6dot(cd, buf)) + h * bdamp;
-        if (A.dbg_H) {
+        row[ddepth] = (d_arm + d6dot(cd, buf)) + h * hb;
+        if (LIMITS) row[ddepth] += dadd;
+        if (A.dbg_H && (!LIMITS || phase != 1)) {
           for (int d = 0; d < rs; d++) A.dbg_H[((size_t)env * nv + lane) * rs + d] = d <= ddepth ? (float)row[d] : 0.f;
           A.dbg_qfrc[(size_t)env * nv + lane] = (float)qfrc;
         }
       }
     }
     // ---- L: L'DL by rounds; the right-hand side is swept leaves-first in the same rounds
-    double x = isd ? qfrc : 0.0;
+    x = rhs;
     {
       typedef const WideRoundW __attribute__((address_space(4)))* wround_p;
       const wround_p RND = (wround_p)FM.rounds;
@@ -512,6 +620,88 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
       __syncthreads();
       if (isd && ddepth > lvl) x -= (HR[lane * rs + lvl] / Dm) * XW[FM.danc[(size_t)lane * rs + lvl]];
     }
+    if (!LIMITS || phase == 2) break;
+    // ---- limits: the Newton iteration on the primal problem (oracle solve_primal, unilateral rows); every branch below is uniform
+    bool stop;
+    if (phase == 0) {                       // x = a_s: the first iterate, where M (a - a_s) = 0
+      nt_as = nt_a = x; nt_r = 0.0;
+      phase = 1;
+      stop = LM.solver_iterations <= 0;     // (the forces of a_s, as primal_update leaves them)
+    } else {                                // x = (M + D_S)^-1 g: the search direction p = -x and M p = -g - D_S p
+      const double sp = -x, Mp = -nt_g - dadd * sp;
+      double s0 = sp * sp, s1 = sp * Mp, s2 = sp * nt_r, s3 = nt_r * (nt_a - nt_as);
+      WG_SUM4(s0, s1, s2, s3);
+      const double snorm = sqrt(s0), qg0 = 0.5 * s3, qg1 = s2, qg2 = 0.5 * s1;
+      const double gtol = LM.tolerance * LM.ls_tolerance * snorm / LM.scale;
+      const double j_lo = nt_a - ar_lo, j_hi = -nt_a - ar_hi;      // jar of the lane's rows at alpha = 0; Jv = +p, -p
+      const auto ls_eval = [&](double alpha) {
+        double c = 0.0, e0 = 0.0, e1 = 0.0, unused = 0.0;
+        const double x_lo = j_lo + alpha * sp, x_hi = j_hi - alpha * sp;
+        if (c_lo && x_lo < 0.0) { c += 0.5 * D_lo * x_lo * x_lo; e0 += D_lo * x_lo * sp; e1 += D_lo * sp * sp; }
+        if (c_hi && x_hi < 0.0) { c += 0.5 * D_hi * x_hi * x_hi; e0 -= D_hi * x_hi * sp; e1 += D_hi * sp * sp; }
+        WG_SUM4(c, e0, e1, unused);
+        F64LsPt pt;
+        pt.alpha = alpha; pt.cost = qg0 + alpha * (qg1 + alpha * qg2) + c; pt.d0 = qg1 + 2.0 * alpha * qg2 + e0;
+        pt.d1 = 2.0 * qg2 + e1; if (!(pt.d1 > F64_MINVAL)) pt.d1 = F64_MINVAL;
+        return pt;
+      };
+      double alpha = 0.0;
+      if (!(snorm < F64_MINVAL)) {          // primal_linesearch
+        const F64LsPt p0 = ls_eval(0.0);
+        F64LsPt p1 = ls_eval(-p0.d0 / p0.d1);
+        if (p0.cost < p1.cost) p1 = p0;
+        alpha = p1.alpha;
+        if (!(fabs(p1.d0) < gtol)) {
+          int it = 0;
+          bool done = false;
+          const double dir = p1.d0 < 0.0 ? 1.0 : -1.0;
+          F64LsPt p2 = p1;
+#pragma unroll 1
+          while (p1.d0 * dir <= -gtol && it < LM.ls_iterations) {      // one-sided Newton until phi' changes sign
+            p2 = p1; p1 = ls_eval(p1.alpha - p1.d0 / p1.d1); it++;
+            if (fabs(p1.d0) < gtol) { done = true; break; }
+          }
+          alpha = p1.alpha;
+          if (!done && !(it >= LM.ls_iterations || p1.d0 * dir <= 0.0)) {
+            F64LsPt lo = dir > 0.0 ? p2 : p1, hi = dir > 0.0 ? p1 : p2;      // phi'(lo) < 0 < phi'(hi): the minimiser is bracketed
+            F64LsPt best = fabs(lo.d0) < fabs(hi.d0) ? lo : hi;
+#pragma unroll 1
+            while (it < LM.ls_iterations) {
+              double an = best.alpha - best.d0 / best.d1;
+              if (!(an > lo.alpha && an < hi.alpha)) an = 0.5 * (lo.alpha + hi.alpha);
+              const F64LsPt pt = ls_eval(an); it++;
+              best = pt;
+              if (fabs(pt.d0) < gtol) { done = true; break; }
+              if (pt.d0 < 0.0) lo = pt; else hi = pt;
+              if (hi.alpha - lo.alpha <= 1e-16 * fabs(hi.alpha)) break;
+            }
+            alpha = (done || best.cost < p0.cost) ? best.alpha : 0.0;
+          }
+        }
+      }
+      nt_a += alpha * sp; nt_r += alpha * Mp;
+      nt_iter++;
+      stop = alpha == 0.0 || nt_iter >= LM.solver_iterations;
+    }
+    // the rows at the iterate (primal_update): active set, forces, J' f, gradient
+    const double j_lo = nt_a - ar_lo, j_hi = -nt_a - ar_hi;
+    const bool n_lo = c_lo && j_lo < 0.0, n_hi = c_hi && j_hi < 0.0;
+    const bool changed = n_lo != act_lo || n_hi != act_hi;
+    act_lo = n_lo; act_hi = n_hi;
+    const double f_lo = act_lo ? -D_lo * j_lo : 0.0, f_hi = act_hi ? -D_hi * j_hi : 0.0;
+    nt_qfc = f_lo - f_hi; lim_f = f_lo + f_hi;
+    nt_g = nt_r - nt_qfc;
+    {
+      double g2 = nt_g * nt_g, u1 = 0.0, u2 = 0.0, u3 = 0.0;
+      WG_SUM4(g2, u1, u2, u3);
+      // an unchanged active set: the iterate minimises the quadratic of that set (after a_s: no row is active, a_s is the minimiser)
+      if (wg_or(changed ? 1 : 0, FLX + 2) == 0 || LM.scale * sqrt(g2) < LM.tolerance) stop = true;
+    }
+    if (stop) {                             // dual_finish + euler(): M + h B with qfrc_smooth + qfrc_constraint, where anything is damped
+      if ((lflags & 2) == 0) { x = nt_a; break; }
+      phase = 2; hb = bdamp; dadd = 0.0; rhs = isd ? qfrc + nt_qfc : 0.0;
+    } else { dadd = (act_lo ? D_lo : 0.0) + (act_hi ? D_hi : 0.0); rhs = nt_g; }
+    }
     const double my_qacc = x;
     // ---- semi-implicit Euler; the freeze is decided for the workgroup before any lane commits
     const double hstep = A.integrate ? h : 0.0;
@@ -525,13 +715,14 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
     if (wg_or(warn & FMJ_WARN_FREEZE, FLG + 2) != 0) frozen = true;
     if (isd && !frozen) {
       XA[lane] = my_qacc;
+      if (LIMITS) { ws_qacc = (lflags & 1) != 0 ? nt_a : my_qacc; if (FUSED) cy_limfrc = lim_f * U.inv_torques; }
       QV[lane] = nvel;
       if (d_scalar) {
         const double pre_q = QP[d_qadr];
         QP[d_qadr] = pre_q + hstep * nvel;
         if (last) {
           float* s = A.sensordata + (size_t)env * FM.nsensordata + 6 * (nb - 1) + 3 * d_slot;   // jointpos, jointvel, jointlimitfrc
-          s[0] = (float)pre_q; s[1] = (float)pre_qd; s[2] = 0.f;
+          s[0] = (float)pre_q; s[1] = (float)pre_qd; s[2] = LIMITS ? (float)lim_f : 0.f;
         }
       }
     }
@@ -563,13 +754,22 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) fmj_step_f64_kernel(const F64Mo
       for (int i = lane; i < nv; i += FMJ_F64_LANES) ov[i] = (float)QV[i];
     }
     if (A.qacc) for (int i = lane; i < nv; i += FMJ_F64_LANES) A.qacc[(size_t)env * nv + i] = (float)XA[i];
+    if (LIMITS && A.qacc_warmstart && A.integrate && isd) A.qacc_warmstart[(size_t)env * nv + lane] = (float)ws_qacc;
     if (A.time && lane == 0 && A.integrate) A.time[env] = (float)((double)A.time[env] + h * steps_done);
   }
   const int w = wg_or(warn, FLG + 6);
   if (w != 0 && lane == 0) A.status[env] |= w;
 }
 
-extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64(int fused) {
-  return fused ? (void*)fmj_step_f64_kernel<true> : (void*)fmj_step_f64_kernel<false>;
+#undef WG_SUM4
+// -DFMJ_TU_F64: the two instantiations without limits; -DFMJ_TU_F64=2: the two LIMITS instantiations, a translation unit of their own
+#if FMJ_TU_F64 == 2
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_limits(int fused) {
+  return fused ? (void*)fmj_step_f64_kernel<true, true> : (void*)fmj_step_f64_kernel<false, true>;
 }
+#else
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64(int fused) {
+  return fused ? (void*)fmj_step_f64_kernel<true, false> : (void*)fmj_step_f64_kernel<false, false>;
+}
+#endif
 #endif  // FMJ_TU_F64

@@ -1526,7 +1526,8 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 // ---------------------------------------------------------------------------------------------
 // Build layout: this file is compiled once per register row length with -DFMJ_TU_MAXD=<4..64> (only the step-kernel
 // instantiations of that MAXD and a getter for their host stubs), once per row length of the two-wave kernel with
-// -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64 (kernel and getter: fmj_f64.inc), and once without any of
+// -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64 and once for its LIMITS instantiations with -DFMJ_TU_F64=2
+// (kernels and getters: fmj_f64.inc), and once without any of
 // them (standalone operators and all host code), in parallel, and the objects are
 // linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
 // Every csrc/*.inc is part of this one source (the build and build_id() depend on all of them):
@@ -1835,7 +1836,7 @@ void* fmj_tu_kernel_20(int, int); void* fmj_tu_kernel_24(int, int); void* fmj_tu
 void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu_kernel_44(int, int); void* fmj_tu_kernel_48(int, int);
 void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
-void* fmj_tu_f64(int);
+void* fmj_tu_f64(int); void* fmj_tu_f64_limits(int);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -1852,13 +1853,16 @@ static int launch(const char* what, step_kernel_t k, int blocks, int threads, si
 // the fp64 model of an fp64 context: the kernel's argument and host mirrors of the tables that change after fmj_create
 struct F64Host {
   F64Model fm = {};
+  F64Limits lim = {};            // limits contexts (fmj_create_ex2, FMJ_CREATE_F64_LIMITS): the fourth kernel argument
+  int limits = 0;                // the LIMITS instantiations run every launch of the context
   size_t lds_bytes = 0;
   std::vector<double> h_ad;      // actuator table mirror (fmj_set_actuator_forcerange)
   std::vector<int> h_asrc;
   std::vector<int> h_bi, h_di;   // body / dof table mirrors: the rows and swimming slots of the fused loop (fmj_set_readout_maps, fmj_set_swimming)
   const double* d_sw = nullptr;  // [nbody][F64_SW] the swimming slots in double: allocated once (a body has at most one slot), filled by fmj_set_swimming
 };
-typedef void (*f64_kernel_t)(const F64Model, const StepArgs, const F64Fused);
+typedef void (*f64_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits);
+static f64_kernel_t f64_kernel(bool fused, int limits) { return (f64_kernel_t)(limits ? fmj_tu_f64_limits(fused) : fmj_tu_f64(fused)); }
 
 // the rows and swimming slots of fmj_ctx's tables (h_b_info2, h_d_info) into the fp64 body / dof tables
 static int sync_f64_maps(fmj_ctx* c) {
@@ -1876,7 +1880,7 @@ static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream, 
   if (c->path == PATH_F64) {
     if (fused && !f64_fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: an fp64 context steps through fmj_step; write the rows with fmj_before_step");
     const F64Fused U = f64_fused ? *f64_fused : F64Fused{};      // (the plain step reads none of it)
-    hipLaunchKernelGGL((f64_kernel_t)fmj_tu_f64(fused), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream, c->f64->fm, A, U);
+    hipLaunchKernelGGL(f64_kernel(fused, c->f64->limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream, c->f64->fm, A, U, c->f64->lim);
     if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string("fp64 step kernel launch: ") + hipGetErrorString(e));
     return FMJ_OK;
   }
@@ -1957,6 +1961,8 @@ static int resolve_kernel_choice(const fmj_create_options* opts, KernelChoice* K
 // ---- stage 1: every check of the model (host only, before any device call) and the facts the later stages build on
 struct ModelFacts {
   KernelChoice kernel;        // set by fmj_create_ex before check_model
+  bool f64_limits_ok = false; // set by fmj_create_ex2 (FMJ_CREATE_F64_LIMITS): an fp64 context takes joint limits
+  int f64_limits = 0;         // such a context whose model has limited joints: the LIMITS builds of the fp64 kernel; cons stays 0
   int cons = 0, big = 0;      // limits, contacts or pairs (the constraint kernels); nbody or nv above 64 (past one wavefront)
   int wide = 0;               // every step launch runs the two-wave kernel (fmj_wide.inc): big, or kernel.two_wave
   int nplane = 0, n_hfield = 0, any_mesh = 0, any_box = 0, any_polypair = 0;     // nplane counts the ground geoms: planes and the heightfield
@@ -2012,10 +2018,15 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
     }
     if (m->geom_bodyid[g1] == m->geom_bodyid[g2]) return set_err(FMJ_ERR_ARG, "fmj_create: a contact pair joins geoms of two bodies");
   }
-  const int cons = any_limit || (nplane > 0 && m->ngeom > nplane) || m->npair > 0;
+  int cons = any_limit || (nplane > 0 && m->ngeom > nplane) || m->npair > 0;
   if (precision == FMJ_PRECISION_F64) {      // the fp64 step kernel (fmj_f64.inc) is the unconstrained Euler / implicitfast step
+    // on request (fmj_create_ex2) it solves joint limits itself: such a model is no constraint-path model to the stages below,
+    // whose limits (64 bodies / dofs, a dof chain of 32, 192 rows) belong to the fp32 constraint kernels
+    if (F->f64_limits_ok) { any_limit = 0; cons = (nplane > 0 && m->ngeom > nplane) || m->npair > 0; }
     if (cons) return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex: the fp64 step has no constraint solver: the model has ") +
                              (any_limit ? "joint limits" : m->npair > 0 ? "explicit contact pairs" : "contact geoms"));
+    if (F->f64_limits_ok) for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) F->f64_limits = 1;
+    if (F->f64_limits && (m->solver_iterations < 0 || !(m->solver_tolerance >= 0))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
     if (m->integrator == FMJ_INT_RK4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
   }
   if (big && cons) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: nbody or nv above 64 with limits, contacts or pairs (one wavefront per environment on the constraint path)");
@@ -2120,7 +2131,7 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
 static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
   const int nb = m->nbody, nv = m->nv, nj = m->njnt;
   DevModel& D = c->dm;
-  c->solver_requested = F.cons ? m->solver : FMJ_SOLVER_PGS;
+  c->solver_requested = (F.cons || F.f64_limits) ? m->solver : FMJ_SOLVER_PGS;
   c->nbody = nb; c->nv = nv; c->nu = m->nu; c->njnt = nj;
   c->rk4 = m->integrator == FMJ_INT_RK4;
   D.nbody = nb; D.nv = nv; D.nq = m->nq; D.nu = m->nu; D.njnt = nj; D.nM = m->nM;
@@ -2154,7 +2165,7 @@ static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) 
   D.solver_iterations = F.dual_instead ? 10 * m->solver_iterations : m->solver_iterations; D.solver_tolerance = (float)m->solver_tolerance;
   D.cone = cons ? m->cone : FMJ_CONE_PYRAMIDAL;
   D.noslip_iterations = cons ? m->noslip_iterations : 0; D.noslip_tolerance = (float)m->noslip_tolerance;
-  D.solver = (cons && !F.dual_instead) ? m->solver : FMJ_SOLVER_PGS; D.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
+  D.solver = F.f64_limits ? FMJ_SOLVER_NEWTON : (cons && !F.dual_instead) ? m->solver : FMJ_SOLVER_PGS; D.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
   D.ls_tolerance = (float)(m->ls_tolerance > 0 ? m->ls_tolerance : 0.01);
   D.impratio_isqrt = (float)(1.0 / sqrt(m->impratio > 0 ? m->impratio : 1.0));
   D.pgs_scale = (float)(1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1)));
@@ -2596,10 +2607,26 @@ static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
       (rc = upload_f64(c, ad, &M.ad)) || (rc = upload_f64(c, asrc, &M.asrc)) || (rc = upload_f64(c, danc, &M.danc)) || (rc = upload_f64(c, rw, &M.rounds)))
     return rc;
   M.b_anc = D.b_anc;
-  H.lds_bytes = (size_t)ldsd_layout(nb, nv, m->nq, M.rs).total_bytes;
+  if (F.f64_limits) {      // the rows' constants, unrounded (oracle make_constraints)
+    std::vector<double> lm((size_t)nv * F64_LM, 0.0);
+    for (int j = 0; j < nj; j++) {
+      if (m->jnt_type[j] == FMJ_JNT_FREE) continue;
+      double* t = &lm[(size_t)m->jnt_dofadr[j] * F64_LM];
+      t[0] = m->jnt_limited[j] ? 1.0 : 0.0; t[1] = m->jnt_range[2 * j]; t[2] = m->jnt_range[2 * j + 1]; t[3] = m->jnt_margin[j];
+      t[4] = m->jnt_solref[2 * j]; t[5] = m->jnt_solref[2 * j + 1];
+      for (int k = 0; k < 5; k++) t[6 + k] = m->jnt_solimp[5 * j + k];
+      t[11] = m->dof_invweight0[m->jnt_dofadr[j]];
+    }
+    if ((rc = upload_f64(c, lm, &H.lim.lm))) return rc;
+    H.limits = 1;
+    H.lim.solver_iterations = m->solver_iterations; H.lim.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
+    H.lim.tolerance = m->solver_tolerance; H.lim.ls_tolerance = m->ls_tolerance > 0 ? m->ls_tolerance : 0.01;
+    H.lim.scale = 1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1));
+  }
+  H.lds_bytes = (size_t)ldsd_total_bytes(nb, nv, m->nq, M.rs, H.limits);
   if (H.lds_bytes > 160 * 1024) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: fp64 step kernel LDS above 160 KB");     // (cannot happen within the size limits)
   for (int fused = 0; fused < 2; fused++)
-    if (hipFuncSetAttribute((const void*)fmj_tu_f64(fused), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)f64_kernel(fused, H.limits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
       return set_err(FMJ_ERR_HIP, "fmj_create_ex: LDS request of the fp64 step kernel too large");
   c->path = PATH_F64;
   return sync_f64_maps(c);      // the default rows; no swimming slots yet
@@ -2623,13 +2650,22 @@ int fmj_create(const fmj_model* m, int32_t n_envs, int32_t device, fmj_ctx** out
 int fmj_precision(const fmj_ctx* c) { return c ? c->precision : FMJ_PRECISION_F32; }
 
 int fmj_create_ex(const fmj_model* m, int32_t n_envs, int32_t device, const fmj_create_options* opts, fmj_ctx** out) {
+  return fmj_create_ex2(m, n_envs, device, opts, nullptr, out);
+}
+
+int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj_create_options* opts, const fmj_create_ext* ext, fmj_ctx** out) {
   if (!m || !out || n_envs <= 0) return set_err(FMJ_ERR_ARG, "fmj_create: NULL model/out or n_envs <= 0");
   *out = nullptr;
+  if (ext && ext->size != (int32_t)sizeof(fmj_create_ext)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: fmj_create_ext.size is not sizeof(fmj_create_ext)");
+  if (ext && (ext->flags & ~(int32_t)FMJ_CREATE_F64_LIMITS)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: unknown bits in fmj_create_ext.flags");
+  if (ext && (ext->flags & FMJ_CREATE_F64_LIMITS) && !(opts && opts->precision == FMJ_PRECISION_F64))
+    return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_LIMITS needs precision = FMJ_PRECISION_F64 (the limits solve belongs to the fp64 step kernel)");
   if (opts && opts->size != 8 && opts->size != (int32_t)sizeof(fmj_create_options))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex: fmj_create_options.size is neither sizeof(fmj_create_options) nor 8 (the struct before the kernel fields)");
   const int precision = opts ? opts->precision : FMJ_PRECISION_F32;
   if (precision != FMJ_PRECISION_F32 && precision != FMJ_PRECISION_F64) return set_err(FMJ_ERR_ARG, "fmj_create_ex: precision must be FMJ_PRECISION_F32 or FMJ_PRECISION_F64");
   ModelFacts F;
+  F.f64_limits_ok = ext && (ext->flags & FMJ_CREATE_F64_LIMITS);
   if (int rc = resolve_kernel_choice(opts, &F.kernel)) return rc;
   if (int rc = check_model(m, &F, precision)) return rc;
   int ndev = 0;

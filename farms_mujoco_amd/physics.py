@@ -40,7 +40,8 @@ class _MjData(SimpleNamespace):
 class BatchedPhysics:
     """Device-resident mjData for ``n_envs`` copies of one model + the HIP step context."""
 
-    def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None, fp64_fused: bool = False):
+    def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None, fp64_fused: bool = False,
+                 fp64_limits: bool = False):
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
         # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
         # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
@@ -50,7 +51,12 @@ class BatchedPhysics:
             raise ValueError(f'precision must be one of {sorted(_lib.PRECISIONS)}, not {precision!r}')
         if fp64_fused and precision != 'fp64':
             raise ValueError(f"fp64_fused=True needs precision='fp64', not {precision!r}: an fp32 context fuses through fmj_step_fused")
+        # fp64_limits: the fp64 context takes joint limits, solved by the kernel's primal Newton solve (fmj_create_ex2,
+        # FMJ_CREATE_F64_LIMITS; include/fmj.h) - limited swimmers past the sizes of the fp32 constraint path.
+        if fp64_limits and precision != 'fp64':
+            raise ValueError(f"fp64_limits=True needs precision='fp64', not {precision!r}: an fp32 context solves limits on its constraint path")
         self.fp64_fused = bool(fp64_fused)
+        self.fp64_limits = bool(fp64_limits)
         if kernel is not None and not isinstance(kernel, KernelOptions):
             raise TypeError(f'kernel must be a KernelOptions or None, not {kernel!r}')
         if not torch.cuda.is_available():
@@ -73,8 +79,15 @@ class BatchedPhysics:
             flags = (k.two_wave * _lib.KERNEL_TWO_WAVE | (not k.two_env) * _lib.KERNEL_ONE_ENV_PER_WAVE |
                      (not k.lean) * _lib.KERNEL_NO_LEAN | (not k.prio) * _lib.KERNEL_NO_PRIO)
             opts = _lib.CCreateOptions(ctypes.sizeof(_lib.CCreateOptions), _lib.PRECISIONS[precision], flags, k.wps or 0)
-            rc = self._lib.fmj_create_ex(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
-                                         ctypes.byref(opts), ctypes.byref(ctx))
+            if fp64_limits:
+                if not _lib.has('fmj_create_ex2'):      # an A/B base build (FMJ_SO)
+                    raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex2: fp64_limits=True needs a current build')
+                ext = _lib.CCreateExt(ctypes.sizeof(_lib.CCreateExt), _lib.CREATE_F64_LIMITS)
+                rc = self._lib.fmj_create_ex2(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
+                                              ctypes.byref(opts), ctypes.byref(ext), ctypes.byref(ctx))
+            else:
+                rc = self._lib.fmj_create_ex(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
+                                             ctypes.byref(opts), ctypes.byref(ctx))
             if rc and b'fmj_create_options.size' in self._lib.fmj_last_error():      # an A/B base build from before the kernel fields
                 raise _lib.FmjError(f'this libfmj_hip.so has no kernel fields in fmj_create_options: {asked} needs a current build')
             _lib.check(rc)
@@ -103,7 +116,12 @@ class BatchedPhysics:
         rq, ef, it = _lib.ints(self._lib.fmj_solver_info, self._ctx) if _lib.has('fmj_solver_info') else (0, 0, 0)     # absent only from an A/B base build (FMJ_SO)
         names = {0: 'PGS', 1: 'CG', 2: 'Newton'}
         self.solver_requested, self.solver_effective, self.solver_budget = names[rq], names[ef], it
-        if rq != ef:
+        if rq != ef and self.fp64_limits:      # (raised only when the model asked for PGS or CG: Newton is what runs)
+            import warnings
+            warnings.warn(f'solver={self.solver_requested!r} was requested, but the fp64 step solves joint limits with its primal Newton solve: '
+                          f'{self.solver_effective}, until the active set stops changing or {self.solver_budget} iterations per step '
+                          '(same minimiser; include/fmj.h: fmj_create_ex2)', stacklevel=2)
+        elif rq != ef:
             import warnings
             why = ('the noslip post-pass works on the dual matrices, which a primal solver never forms' if int(getattr(model, 'noslip_iterations', 0)) > 0 else
                    'explicit pairs under the elliptic cone have the dual block update only' if (int(getattr(model, 'cone', 0)) == 1 and int(getattr(model, 'npair', 0)) > 0) else

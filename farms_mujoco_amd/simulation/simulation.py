@@ -104,7 +104,8 @@ class Simulation:
     ``mjcf_model`` is a compiled :class:`~farms_mujoco_amd.model.Model` (the dm_control MJCF element tree is
     replaced).  Extra kwargs: ``n_envs``, ``device``, ``precision`` ('fp32' | 'fp64': the step kernel's arithmetic,
     :class:`~farms_mujoco_amd.physics.BatchedPhysics`), ``fp64_fused`` (with 'fp64': fused launches through fmj_step_fused_f64 - rows and
-    drag in double, the state rounded to fp32 where a launch ends, not every iteration, so results differ from the default's), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
+    drag in double, the state rounded to fp32 where a launch ends, not every iteration, so results differ from the default's), ``fp64_limits``
+    (with 'fp64': the context takes joint limits, solved by the fp64 kernel's primal Newton solve; fmj_create_ex2), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
     kernels this simulation's context runs).  ``legacy_step`` is accepted for signature
     compatibility; the step is always the full mj_step (legacy_step=False semantics, simulation.py:36-37).
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here
@@ -127,7 +128,7 @@ class Simulation:
         n_envs = kwargs.pop('n_envs', 1)
         device = kwargs.pop('device', 'cuda:0')
         self.physics = BatchedPhysics(mjcf_model, n_envs, device, precision=kwargs.pop('precision', 'fp32'), kernel=kwargs.pop('kernel', None),
-                                      fp64_fused=kwargs.pop('fp64_fused', False))
+                                      fp64_fused=kwargs.pop('fp64_fused', False), fp64_limits=kwargs.pop('fp64_limits', False))
         self.handle_exceptions = kwargs.pop('handle_exceptions', False)
         # dm_control raises PhysicsError inside the offending step; here the device freezes the offending env at that
         # step (include/fmj.h) and the host looks at the status words every `check_every` steps (one sync each)
@@ -225,7 +226,7 @@ class Simulation:
         contacts = task.data.sensors.contacts
         if contacts.names:
             a.rows_base.contacts, a.row_stride_contacts = contacts.row_ptr(0), contacts.array.stride(0)
-        if phys.has_constraints and self.order_by_contacts:
+        if phys.has_constraints and self.order_by_contacts and phys.precision != 'fp64':      # (an fp64 context has limits at most: nothing to order by)
             # envs with the most contacts (the slowest to step) are launched first instead of wherever they sit; the two-env constraint
             # kernel steps entries 2b and 2b + 1 of the order in one wave: neighbours have similar row counts (one PGS sweep length
             # for both; pairing the heaviest with the lightest instead was measured: no difference in the launch time)

@@ -290,7 +290,8 @@ typedef struct fmj_ctx fmj_ctx;   /* opaque */
 /* Replaces mjcf.Physics.from_mjcf_model (reference simulation.py:53): validates the model,
  * builds the level / ancestor tables, uploads the fp32 device copy. `device` = HIP ordinal.
  * Model size: nbody <= 128 and nv <= 128, a dof chain of at most 64 (32 with limits / contacts).  A model past 64 bodies or dofs
- * steps on one workgroup of two wavefronts per environment and must have no limits, contacts or pairs and not use RK4; these
+ * steps on one workgroup of two wavefronts per environment and must have no limits (but see fmj_create_ex2: an fp64 context can take
+ * joint limits at any size), contacts or pairs and not use RK4; these
  * are FMJ_ERR_UNSUPPORTED with the limit named in fmj_last_error().  Which kernels a context runs within those limits
  * can be chosen per context: "Kernel selection" at fmj_create_ex. */
 int fmj_create(const fmj_model* model, int32_t n_envs, int32_t device, fmj_ctx** out);
@@ -302,7 +303,8 @@ int fmj_create(const fmj_model* model, int32_t n_envs, int32_t device, fmj_ctx**
  * chains of light links, whose joint-space inertia is too ill-conditioned for fp32 ("Accuracy of long chains").
  * An fp64 context covers fmj_step (any n_steps, ctrl tape), fmj_forward (disable_actuation included) and fmj_forward_debug (H_rows /
  * qfrc_smooth rounded to fp32 on store), with the Euler and implicitfast integrators.  Refused with FMJ_ERR_UNSUPPORTED and a message
- * containing "fp64": a model with limits, contacts or pairs, the RK4 integrator (both at fmj_create_ex, before the device lookup) and
+ * containing "fp64": a model with limits (unless opted in: fmj_create_ex2), contacts or pairs, the RK4 integrator (all at fmj_create_ex,
+ * before the device lookup) and
  * fmj_step_fused / fmj_step_fused_ex (write the rows with fmj_before_step, as with RK4, or opt in to the fused fp64 loop through its own
  * entry point, fmj_step_fused_f64, whose results differ from the per-iteration ones).  The standalone operators (fmj_before_step, fmj_physics2data,
  * fmj_drag, fmj_contacts2data) work unchanged, in fp32, from the fmj_data fields.  An unknown precision is FMJ_ERR_ARG.
@@ -329,6 +331,27 @@ typedef struct fmj_create_options {
 } fmj_create_options;
 int fmj_create_ex(const fmj_model* model, int32_t n_envs, int32_t device, const fmj_create_options* opts, fmj_ctx** out);
 int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
+/* fmj_create_ex with an extension struct (additive: FMJ_ABI_VERSION stays 6; fmj_model, fmj_data and fmj_create_options do not
+ * change).  ext == NULL or flags == 0 is fmj_create_ex: the same path, the same bits.  FMJ_ERR_ARG, decided before the device lookup:
+ * another size, an unknown flag bit, FMJ_CREATE_F64_LIMITS without precision = FMJ_PRECISION_F64.
+ * FMJ_CREATE_F64_LIMITS: the fp64 context accepts a model whose only constraints are joint limits on hinge and slide joints, within the
+ * fp64 kernel's own sizes (nbody, nv <= 128, dof chain <= 64, Euler or implicitfast); the limits of the fp32 constraint path (64 bodies
+ * / dofs, a dof chain of 32, 192 rows) do not apply.  Contact geoms, explicit pairs and RK4 stay refused as by fmj_create_ex.  The
+ * limits are solved on the primal problem by Newton's method with an exact line search, until the active set stops changing (or the
+ * model's solver_tolerance / solver_iterations): a limit row's Jacobian is a unit vector, so the Newton matrix is M with a larger
+ * diagonal and the step kernel's tree-sparse factorisation applies; a step in which no joint is within its margin of a limit is, bit
+ * for bit, the step of the same model without limits.  Whatever solver the model names, the result is the same to the bit:
+ * fmj_solver_info reports it as requested, FMJ_SOLVER_NEWTON as effective and solver_iterations as the budget.  The context covers
+ * fmj_step, fmj_forward, fmj_forward_debug (H_rows: M + h B, as without limits) and fmj_step_fused_f64, limits included: sensordata's
+ * jointlimitfrc slots and the fused joints rows' FMJ_JOINT_LIMIT_FORCE carry the limit forces, fmj_data.qacc the acceleration the
+ * integrator used, and fmj_data.qacc_warmstart (optional for this context; the solve starts from the unconstrained acceleration and
+ * does not read it) the constrained acceleration of the launch's last step. */
+enum { FMJ_CREATE_F64_LIMITS = 1 };
+typedef struct fmj_create_ext {
+  int32_t size;           /* = sizeof(fmj_create_ext); anything else: FMJ_ERR_ARG */
+  int32_t flags;          /* FMJ_CREATE_*, or 0 */
+} fmj_create_ext;
+int fmj_create_ex2(const fmj_model* model, int32_t n_envs, int32_t device, const fmj_create_options* opts, const fmj_create_ext* ext /* may be NULL */, fmj_ctx** out);
 void fmj_destroy(fmj_ctx* ctx);
 const char* fmj_last_error(void);
 int fmj_abi_version(void);
