@@ -14,9 +14,9 @@ import numpy as np
 import pytest
 
 from parity_metrics import relerr
-from wide_trees import shape_tree
-from support_models import tree_inputs
-from support_sims import f64 as _f64, swim_sim, wave_at, load_batch
+from support_sims import swim_sim, wave_at, load_batch
+from support_limits import (limited as _limited, scalar_q as _scalar_q, engaged_inputs as _engaged_inputs, phys as _phys,
+                            rows_engaged as _rows_engaged, excess as _excess, tape as _tape)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,96 +27,6 @@ MODELS = ('salamander33', 'eel48', 'centipede_20_25') + TREES
 # the seed of each model's inputs: the first of 100, 101, ... (0, 1, ... for the larger models) at which the oracle finds, in every
 # env, at least 5 rows with a force and a candidate row without one (the test asserts both before it looks at the device)
 SEEDS = {'salamander33': 104, 'eel48': 100, 'centipede_20_25': 2, 'shape1': 3, 'shape4': 4, 'shape6': 5, 'shape10': 6}
-
-
-def _base(name):
-    import farms_mujoco_amd.model as mm
-    if name.startswith('shape'):
-        return shape_tree(int(name[5:]))
-    return {'salamander33': lambda: mm.salamander33(limits=True), 'eel48': lambda: mm.eel(n_joints=48),
-            'centipede_20_25': lambda: mm.centipede(20, 25)}[name]()
-
-
-def _newton(m):
-    from farms_mujoco_amd.model import SOLVERS
-    m.solver = SOLVERS['newton']; m.solver_iterations = 100
-    return m
-
-
-def _limited(name, lim=0.1, margin_even=0.02, which=slice(None), integrator='euler'):
-    """The model with joints ``which`` (of its hinge and slide joints) limited to +-lim, ``margin_even`` on the even joints, set after
-    the build as test_fp64_refuses_limits does; the solver fields are the reference's: Newton, 100 iterations."""
-    import farms_mujoco_amd.model as mm
-    m = _base(name)
-    assert m.ngeom == 0
-    on = np.zeros(m.njnt, bool); on[which] = True
-    on &= m.jnt_type != 0
-    m.jnt_limited = on.astype(m.jnt_limited.dtype)
-    m.jnt_range = np.tile([-lim, lim], (m.njnt, 1)).astype(float)
-    margin = np.zeros(m.njnt); margin[::2] = margin_even
-    m.jnt_margin = margin
-    m.integrator = mm.INTEGRATORS[integrator]
-    return _newton(m)
-
-
-def _scalar_q(m):
-    return m.jnt_qposadr[m.jnt_type != 0]
-
-
-def _engaged_inputs(m, n, seed):
-    """tree_inputs with the joint positions uniform in +-0.15, qvel normal x 0.5 and ctrl uniform in +-0.3."""
-    qpos, qvel, ctrl, xf, qs = tree_inputs(m, n, seed)
-    rng = np.random.default_rng([4242, seed])
-    qpos[:, _scalar_q(m)] = rng.uniform(-0.15, 0.15, (n, len(_scalar_q(m))))
-    qvel = rng.normal(size=(n, m.nv))*0.5
-    ctrl = rng.uniform(-0.3, 0.3, (n, max(m.nu, 1)))[:, :m.nu]
-    return qpos, qvel, ctrl, xf, qs
-
-
-def _phys(m, n, qpos, qvel, ctrl=None, xf=None, qs=None, precision='fp64', limits=True):
-    import test_gpu_f64_step as S
-    import torch
-    from farms_mujoco_amd.physics import BatchedPhysics
-    if precision == 'fp32':
-        return S._phys(m, n, qpos, qvel, ctrl, xf, qs, precision)
-    phys = BatchedPhysics(m, n, precision='fp64', fp64_limits=limits)
-    assert phys.precision == 'fp64' and phys.kernel_info()['threads_per_env'] == 128
-    d = phys.data
-    f32 = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32)
-    d.qpos[:] = f32(qpos); d.qvel[:] = f32(qvel)
-    if xf is not None:
-        d.xfrc_applied[:] = f32(xf)
-    if qs is not None:
-        d.qpos_spring[:] = f32(qs)
-    if ctrl is not None and m.nu:
-        d.ctrl[:] = f32(ctrl)
-    return phys, dict(qpos=_f64(d.qpos), qvel=_f64(d.qvel), ctrl=_f64(d.ctrl) if m.nu else None, xfrc_applied=_f64(d.xfrc_applied),
-                      qpos_spring=_f64(d.qpos_spring))
-
-
-def _rows_engaged(oracle, m, ins):
-    """Per env, from oracle.step_tf: the rows with a positive force and the candidate rows with none."""
-    o = oracle.step_tf(m, ins['qpos'], ins['qvel'], ctrl=ins['ctrl'], qpos_spring=ins['qpos_spring'], xfrc_applied=ins['xfrc_applied'], want_AR=False)
-    pos = np.array([(o['efc'][e, :o['nefc'][e], 0] > 0).sum() for e in range(len(o['nefc']))])
-    return pos, o['nefc'] - pos
-
-
-def _excess(oracle, m, phys, ins, forward):
-    import test_gpu_f64_step as S
-    import torch
-    q0, v0 = phys.data.qpos.clone(), phys.data.qvel.clone()
-    if forward:
-        phys.forward()
-    else:
-        phys.step(1)
-    torch.cuda.synchronize()
-    assert int(phys.data.status.abs().sum()) == 0
-    ref = oracle.step(m, ins['qpos'], ins['qvel'], ctrl=ins['ctrl'], qpos_spring=ins['qpos_spring'], xfrc_applied=ins['xfrc_applied'])
-    if forward:
-        assert torch.equal(phys.data.qpos, q0) and torch.equal(phys.data.qvel, v0)
-        ref = dict(ref, qpos=ins['qpos'], qvel=ins['qvel'])
-    groups = S._field_groups(m)
-    return {k: S.ulp_excess(getattr(phys.data, k).cpu().numpy(), ref[k], groups[k]) for k in ('qpos', 'qvel', 'qacc', 'sensordata')}, ref
 
 
 @pytest.mark.parametrize('integrator', ['euler', 'implicitfast'])
@@ -196,13 +106,6 @@ def test_limits_that_never_engage_change_no_bit(name):
     ra, rb = rows(sa), rows(sb)
     for k in ra:
         assert np.array_equal(ra[k], rb[k]), k
-
-
-def _tape(m, n, T, f):
-    """ctrl[t, env, a] = 0.3 sin(2 pi f t + 0.7 env - 2 pi a / nu), rounded to fp32 as the device holds it."""
-    t = np.arange(T)[:, None, None]*m.timestep
-    tape = 0.3*np.sin(2*np.pi*f*t + 0.7*np.arange(n)[None, :, None] - 2*np.pi*np.arange(m.nu)[None, None, :]/m.nu)
-    return tape.astype(np.float32)
 
 
 @pytest.mark.parametrize('recipe', ['A', 'B'])
