@@ -1526,13 +1526,13 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 // ---------------------------------------------------------------------------------------------
 // Build layout: this file is compiled once per register row length with -DFMJ_TU_MAXD=<4..64> (only the step-kernel
 // instantiations of that MAXD and a getter for their host stubs), once per row length of the two-wave kernel with
-// -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64 and once for its LIMITS instantiations with -DFMJ_TU_F64=2
-// (kernels and getters: fmj_f64.inc), and once without any of
+// -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64, once for its LIMITS instantiations with -DFMJ_TU_F64=2
+// and once for its RK4 kernels with -DFMJ_TU_F64=3 (kernels and getters: fmj_f64.inc + fmj_f64_step.inc), and once without any of
 // them (standalone operators and all host code), in parallel, and the objects are
 // linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
 // Every csrc/*.inc is part of this one source (the build and build_id() depend on all of them):
 //   fmj_cons_rows.inc, fmj_newton.inc          constraint rows and solvers of fmj_step_kernel<.., CONS = true>
-//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc      the other step kernels
+//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc (+ fmj_f64_step.inc)      the other step kernels
 //   fmj_stage_{carry_in,step_head,k,c,v,f,q,m,dbg_h,euler_check,euler_commit,euler_root}.inc      stages shared by fmj_step_kernel and fmj_step_wide_kernel
 //   fmj_stage2_{k,c,v,f,s}.inc                 stages shared by fmj_step_dual2_kernel and fmj_step_cons2_kernel
 //   fmj_narrow.inc                             collision helpers (device functions, CONTACT_RECORD), included once ahead of the kernels
@@ -1836,7 +1836,7 @@ void* fmj_tu_kernel_20(int, int); void* fmj_tu_kernel_24(int, int); void* fmj_tu
 void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu_kernel_44(int, int); void* fmj_tu_kernel_48(int, int);
 void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
-void* fmj_tu_f64(int); void* fmj_tu_f64_limits(int);
+void* fmj_tu_f64(int); void* fmj_tu_f64_limits(int); void* fmj_tu_f64_rk4(int, int);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -1855,6 +1855,7 @@ struct F64Host {
   F64Model fm = {};
   F64Limits lim = {};            // limits contexts (fmj_create_ex2, FMJ_CREATE_F64_LIMITS): the fourth kernel argument
   int limits = 0;                // the LIMITS instantiations run every launch of the context
+  int rk4 = 0;                   // fmj_create_ex2 with FMJ_CREATE_F64_RK4 and an RK4 model: fmj_step_f64_rk4_kernel runs every launch
   size_t lds_bytes = 0;
   std::vector<double> h_ad;      // actuator table mirror (fmj_set_actuator_forcerange)
   std::vector<int> h_asrc;
@@ -1862,7 +1863,9 @@ struct F64Host {
   const double* d_sw = nullptr;  // [nbody][F64_SW] the swimming slots in double: allocated once (a body has at most one slot), filled by fmj_set_swimming
 };
 typedef void (*f64_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits);
-static f64_kernel_t f64_kernel(bool fused, int limits) { return (f64_kernel_t)(limits ? fmj_tu_f64_limits(fused) : fmj_tu_f64(fused)); }
+static f64_kernel_t f64_kernel(bool fused, int limits, int rk4) {
+  return (f64_kernel_t)(rk4 ? fmj_tu_f64_rk4(fused, limits) : limits ? fmj_tu_f64_limits(fused) : fmj_tu_f64(fused));
+}
 
 // the rows and swimming slots of fmj_ctx's tables (h_b_info2, h_d_info) into the fp64 body / dof tables
 static int sync_f64_maps(fmj_ctx* c) {
@@ -1880,7 +1883,7 @@ static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream, 
   if (c->path == PATH_F64) {
     if (fused && !f64_fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: an fp64 context steps through fmj_step; write the rows with fmj_before_step");
     const F64Fused U = f64_fused ? *f64_fused : F64Fused{};      // (the plain step reads none of it)
-    hipLaunchKernelGGL(f64_kernel(fused, c->f64->limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream, c->f64->fm, A, U, c->f64->lim);
+    hipLaunchKernelGGL(f64_kernel(fused, c->f64->limits, c->f64->rk4), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream, c->f64->fm, A, U, c->f64->lim);
     if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string("fp64 step kernel launch: ") + hipGetErrorString(e));
     return FMJ_OK;
   }
@@ -1963,6 +1966,8 @@ struct ModelFacts {
   KernelChoice kernel;        // set by fmj_create_ex before check_model
   bool f64_limits_ok = false; // set by fmj_create_ex2 (FMJ_CREATE_F64_LIMITS): an fp64 context takes joint limits
   int f64_limits = 0;         // such a context whose model has limited joints: the LIMITS builds of the fp64 kernel; cons stays 0
+  bool f64_rk4_ok = false;    // set by fmj_create_ex2 (FMJ_CREATE_F64_RK4): an fp64 context takes integrator = FMJ_INT_RK4
+  int f64_rk4 = 0;            // such a context whose model integrates with RK4: fmj_step_f64_rk4_kernel, four passes inside one launch
   int cons = 0, big = 0;      // limits, contacts or pairs (the constraint kernels); nbody or nv above 64 (past one wavefront)
   int wide = 0;               // every step launch runs the two-wave kernel (fmj_wide.inc): big, or kernel.two_wave
   int nplane = 0, n_hfield = 0, any_mesh = 0, any_box = 0, any_polypair = 0;     // nplane counts the ground geoms: planes and the heightfield
@@ -2027,7 +2032,8 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
                              (any_limit ? "joint limits" : m->npair > 0 ? "explicit contact pairs" : "contact geoms"));
     if (F->f64_limits_ok) for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) F->f64_limits = 1;
     if (F->f64_limits && (m->solver_iterations < 0 || !(m->solver_tolerance >= 0))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
-    if (m->integrator == FMJ_INT_RK4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
+    if (m->integrator == FMJ_INT_RK4 && !F->f64_rk4_ok) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
+    F->f64_rk4 = m->integrator == FMJ_INT_RK4;
   }
   if (big && cons) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: nbody or nv above 64 with limits, contacts or pairs (one wavefront per environment on the constraint path)");
   if (cons && m->solver != FMJ_SOLVER_PGS && m->solver != FMJ_SOLVER_NEWTON && m->solver != FMJ_SOLVER_CG) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: solver must be FMJ_SOLVER_PGS, FMJ_SOLVER_CG or FMJ_SOLVER_NEWTON");
@@ -2050,7 +2056,7 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   if (m->noslip_iterations < 0 || !(m->noslip_tolerance >= 0)) return set_err(FMJ_ERR_ARG, "fmj_create: noslip_iterations / noslip_tolerance must not be negative");
   if (m->integrator != FMJ_INT_EULER && m->integrator != FMJ_INT_IMPLICITFAST && m->integrator != FMJ_INT_RK4)
     return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: integrator must be FMJ_INT_EULER, FMJ_INT_IMPLICITFAST or FMJ_INT_RK4 (implicit keeps the Coriolis derivatives, a non-symmetric matrix outside this path's tree-sparse factorisation)");
-  if (big && m->integrator == FMJ_INT_RK4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: RK4 on a model with more than 64 bodies or dofs (its stage kernel holds one dof per lane of one wavefront)");
+  if (big && m->integrator == FMJ_INT_RK4 && !F->f64_rk4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: RK4 on a model with more than 64 bodies or dofs (its stage kernel holds one dof per lane of one wavefront)");
   if (cons && (m->ngeom > nplane || m->npair > 0) && !any_limit && m->max_contacts < 1) return set_err(FMJ_ERR_ARG, "fmj_create: max_contacts must be >= 1 with collision geoms");
   if ((m->npair > 0 || (nplane > 0 && m->ngeom > nplane)) && m->max_contacts < 1) return set_err(FMJ_ERR_ARG, "fmj_create: max_contacts must be >= 1 with collision geoms");
   // structure checks: single tree rooted at body 1, DFS pre-order, <= 1 joint per body
@@ -2133,7 +2139,7 @@ static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) 
   DevModel& D = c->dm;
   c->solver_requested = (F.cons || F.f64_limits) ? m->solver : FMJ_SOLVER_PGS;
   c->nbody = nb; c->nv = nv; c->nu = m->nu; c->njnt = nj;
-  c->rk4 = m->integrator == FMJ_INT_RK4;
+  c->rk4 = m->integrator == FMJ_INT_RK4 && !F.f64_rk4;      // (an fp64 RK4 context runs its passes inside the kernel: no stage buffers, no stage launches)
   D.nbody = nb; D.nv = nv; D.nq = m->nq; D.nu = m->nu; D.njnt = nj; D.nM = m->nM;
   D.max_bdepth = F.jump_rounds;       // pointer-jumping rounds
   D.max_subsize = F.max_sub;
@@ -2623,10 +2629,11 @@ static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
     H.lim.tolerance = m->solver_tolerance; H.lim.ls_tolerance = m->ls_tolerance > 0 ? m->ls_tolerance : 0.01;
     H.lim.scale = 1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1));
   }
-  H.lds_bytes = (size_t)ldsd_total_bytes(nb, nv, m->nq, M.rs, H.limits);
+  H.rk4 = F.f64_rk4;
+  H.lds_bytes = (size_t)ldsd_total_bytes(nb, nv, m->nq, M.rs, H.limits) + (H.rk4 ? (size_t)F64_RK4_LDS_DOUBLES(m->nu) * 8 : 0);
   if (H.lds_bytes > 160 * 1024) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: fp64 step kernel LDS above 160 KB");     // (cannot happen within the size limits)
   for (int fused = 0; fused < 2; fused++)
-    if (hipFuncSetAttribute((const void*)f64_kernel(fused, H.limits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
+    if (hipFuncSetAttribute((const void*)f64_kernel(fused, H.limits, H.rk4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
       return set_err(FMJ_ERR_HIP, "fmj_create_ex: LDS request of the fp64 step kernel too large");
   c->path = PATH_F64;
   return sync_f64_maps(c);      // the default rows; no swimming slots yet
@@ -2657,15 +2664,18 @@ int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj
   if (!m || !out || n_envs <= 0) return set_err(FMJ_ERR_ARG, "fmj_create: NULL model/out or n_envs <= 0");
   *out = nullptr;
   if (ext && ext->size != (int32_t)sizeof(fmj_create_ext)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: fmj_create_ext.size is not sizeof(fmj_create_ext)");
-  if (ext && (ext->flags & ~(int32_t)FMJ_CREATE_F64_LIMITS)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: unknown bits in fmj_create_ext.flags");
+  if (ext && (ext->flags & ~(int32_t)(FMJ_CREATE_F64_LIMITS | FMJ_CREATE_F64_RK4))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: unknown bits in fmj_create_ext.flags");
   if (ext && (ext->flags & FMJ_CREATE_F64_LIMITS) && !(opts && opts->precision == FMJ_PRECISION_F64))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_LIMITS needs precision = FMJ_PRECISION_F64 (the limits solve belongs to the fp64 step kernel)");
+  if (ext && (ext->flags & FMJ_CREATE_F64_RK4) && !(opts && opts->precision == FMJ_PRECISION_F64))
+    return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_RK4 needs precision = FMJ_PRECISION_F64 (the in-kernel RK4 belongs to the fp64 step kernel)");
   if (opts && opts->size != 8 && opts->size != (int32_t)sizeof(fmj_create_options))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex: fmj_create_options.size is neither sizeof(fmj_create_options) nor 8 (the struct before the kernel fields)");
   const int precision = opts ? opts->precision : FMJ_PRECISION_F32;
   if (precision != FMJ_PRECISION_F32 && precision != FMJ_PRECISION_F64) return set_err(FMJ_ERR_ARG, "fmj_create_ex: precision must be FMJ_PRECISION_F32 or FMJ_PRECISION_F64");
   ModelFacts F;
   F.f64_limits_ok = ext && (ext->flags & FMJ_CREATE_F64_LIMITS);
+  F.f64_rk4_ok = ext && (ext->flags & FMJ_CREATE_F64_RK4);
   if (int rc = resolve_kernel_choice(opts, &F.kernel)) return rc;
   if (int rc = check_model(m, &F, precision)) return rc;
   int ndev = 0;

@@ -41,7 +41,7 @@ class BatchedPhysics:
     """Device-resident mjData for ``n_envs`` copies of one model + the HIP step context."""
 
     def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None, fp64_fused: bool = False,
-                 fp64_limits: bool = False):
+                 fp64_limits: bool = False, fp64_rk4: bool = False):
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
         # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
         # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
@@ -55,8 +55,13 @@ class BatchedPhysics:
         # FMJ_CREATE_F64_LIMITS; include/fmj.h) - limited swimmers past the sizes of the fp32 constraint path.
         if fp64_limits and precision != 'fp64':
             raise ValueError(f"fp64_limits=True needs precision='fp64', not {precision!r}: an fp32 context solves limits on its constraint path")
+        # fp64_rk4: the fp64 context takes integrator = RK4 and runs the four forward passes of a step inside the kernel, one launch for
+        # all steps of fmj_step (fmj_create_ex2, FMJ_CREATE_F64_RK4; include/fmj.h); with fp64_fused such a run fuses too.
+        if fp64_rk4 and precision != 'fp64':
+            raise ValueError(f"fp64_rk4=True needs precision='fp64', not {precision!r}: an fp32 context integrates RK4 with four launches per step")
         self.fp64_fused = bool(fp64_fused)
         self.fp64_limits = bool(fp64_limits)
+        self.fp64_rk4 = bool(fp64_rk4)
         if kernel is not None and not isinstance(kernel, KernelOptions):
             raise TypeError(f'kernel must be a KernelOptions or None, not {kernel!r}')
         if not torch.cuda.is_available():
@@ -79,10 +84,10 @@ class BatchedPhysics:
             flags = (k.two_wave * _lib.KERNEL_TWO_WAVE | (not k.two_env) * _lib.KERNEL_ONE_ENV_PER_WAVE |
                      (not k.lean) * _lib.KERNEL_NO_LEAN | (not k.prio) * _lib.KERNEL_NO_PRIO)
             opts = _lib.CCreateOptions(ctypes.sizeof(_lib.CCreateOptions), _lib.PRECISIONS[precision], flags, k.wps or 0)
-            if fp64_limits:
+            if fp64_limits or fp64_rk4:
                 if not _lib.has('fmj_create_ex2'):      # an A/B base build (FMJ_SO)
-                    raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex2: fp64_limits=True needs a current build')
-                ext = _lib.CCreateExt(ctypes.sizeof(_lib.CCreateExt), _lib.CREATE_F64_LIMITS)
+                    raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex2: fp64_limits=True / fp64_rk4=True need a current build')
+                ext = _lib.CCreateExt(ctypes.sizeof(_lib.CCreateExt), bool(fp64_limits) * _lib.CREATE_F64_LIMITS | bool(fp64_rk4) * _lib.CREATE_F64_RK4)
                 rc = self._lib.fmj_create_ex2(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
                                               ctypes.byref(opts), ctypes.byref(ext), ctypes.byref(ctx))
             else:
@@ -105,7 +110,9 @@ class BatchedPhysics:
             xfrc_applied=z(n, m.nbody, 6), xpos=z(n, m.nbody, 3), xquat=z(n, m.nbody, 4), xipos=z(n, m.nbody, 3),
             sensordata=z(n, m.nsensordata), qacc=z(n, m.nv), time=z(n), status=z(n, dtype=torch.int32))
         self.has_constraints = bool(np.any(m.jnt_limited)) or m.ngeom > 0
-        self.rk4 = int(getattr(m, 'integrator', 0)) == 1      # FMJ_INT_RK4: fmj_step runs four forward launches per step, fmj_step_fused refuses
+        # FMJ_INT_RK4: fmj_step runs four forward launches per step and fmj_step_fused refuses - or, in an fp64_rk4 context, the fp64
+        # kernel runs the four passes itself (one launch for all steps; fmj_step_fused_f64 fuses)
+        self.rk4 = int(getattr(m, 'integrator', 0)) == 1
         self.max_contacts = max(int(m.max_contacts), 1)
         self.data.qacc_warmstart = z(n, m.nv)
         self.data.contact = z(n, self.max_contacts, 16)

@@ -105,7 +105,8 @@ class Simulation:
     replaced).  Extra kwargs: ``n_envs``, ``device``, ``precision`` ('fp32' | 'fp64': the step kernel's arithmetic,
     :class:`~farms_mujoco_amd.physics.BatchedPhysics`), ``fp64_fused`` (with 'fp64': fused launches through fmj_step_fused_f64 - rows and
     drag in double, the state rounded to fp32 where a launch ends, not every iteration, so results differ from the default's), ``fp64_limits``
-    (with 'fp64': the context takes joint limits, solved by the fp64 kernel's primal Newton solve; fmj_create_ex2), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
+    (with 'fp64': the context takes joint limits, solved by the fp64 kernel's primal Newton solve; fmj_create_ex2), ``fp64_rk4`` (with 'fp64': the
+    context takes an RK4 model and runs the four passes of a step inside the fp64 kernel; the run fuses when ``fp64_fused`` is set too), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
     kernels this simulation's context runs).  ``legacy_step`` is accepted for signature
     compatibility; the step is always the full mj_step (legacy_step=False semantics, simulation.py:36-37).
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here
@@ -128,7 +129,8 @@ class Simulation:
         n_envs = kwargs.pop('n_envs', 1)
         device = kwargs.pop('device', 'cuda:0')
         self.physics = BatchedPhysics(mjcf_model, n_envs, device, precision=kwargs.pop('precision', 'fp32'), kernel=kwargs.pop('kernel', None),
-                                      fp64_fused=kwargs.pop('fp64_fused', False), fp64_limits=kwargs.pop('fp64_limits', False))
+                                      fp64_fused=kwargs.pop('fp64_fused', False), fp64_limits=kwargs.pop('fp64_limits', False),
+                                      fp64_rk4=kwargs.pop('fp64_rk4', False))
         self.handle_exceptions = kwargs.pop('handle_exceptions', False)
         # dm_control raises PhysicsError inside the offending step; here the device freezes the offending env at that
         # step (include/fmj.h) and the host looks at the status words every `check_every` steps (one sync each)
@@ -140,7 +142,9 @@ class Simulation:
                                    substeps=self.options.num_sub_steps, **kwargs)
         # RK4 (four forward launches per step, fmj_step) and the fp64 step kernel without fp64_fused: no fused launch, the controller is
         # evaluated on the host path (task.step_control)
-        self.task.host_step_only = self.physics.rk4 or (self.physics.precision == 'fp64' and not self.physics.fp64_fused)
+        # (an RK4 model fuses only in an fp64 context made with fp64_rk4 and fp64_fused: fmj_step_fused_f64 runs the passes in the kernel)
+        self.task.host_step_only = ((self.physics.rk4 and not (self.physics.fp64_rk4 and self.physics.fp64_fused)) or
+                                    (self.physics.precision == 'fp64' and not self.physics.fp64_fused))
         self._needs_reset = True
 
     @property

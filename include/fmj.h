@@ -333,10 +333,10 @@ int fmj_create_ex(const fmj_model* model, int32_t n_envs, int32_t device, const 
 int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
 /* fmj_create_ex with an extension struct (additive: FMJ_ABI_VERSION stays 6; fmj_model, fmj_data and fmj_create_options do not
  * change).  ext == NULL or flags == 0 is fmj_create_ex: the same path, the same bits.  FMJ_ERR_ARG, decided before the device lookup:
- * another size, an unknown flag bit, FMJ_CREATE_F64_LIMITS without precision = FMJ_PRECISION_F64.
+ * another size, an unknown flag bit, FMJ_CREATE_F64_LIMITS or FMJ_CREATE_F64_RK4 without precision = FMJ_PRECISION_F64.
  * FMJ_CREATE_F64_LIMITS: the fp64 context accepts a model whose only constraints are joint limits on hinge and slide joints, within the
  * fp64 kernel's own sizes (nbody, nv <= 128, dof chain <= 64, Euler or implicitfast); the limits of the fp32 constraint path (64 bodies
- * / dofs, a dof chain of 32, 192 rows) do not apply.  Contact geoms, explicit pairs and RK4 stay refused as by fmj_create_ex.  The
+ * / dofs, a dof chain of 32, 192 rows) do not apply.  Contact geoms, explicit pairs and (without FMJ_CREATE_F64_RK4) RK4 stay refused as by fmj_create_ex.  The
  * limits are solved on the primal problem by Newton's method with an exact line search, until the active set stops changing (or the
  * model's solver_tolerance / solver_iterations): a limit row's Jacobian is a unit vector, so the Newton matrix is M with a larger
  * diagonal and the step kernel's tree-sparse factorisation applies; a step in which no joint is within its margin of a limit is, bit
@@ -345,8 +345,20 @@ int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
  * fmj_step, fmj_forward, fmj_forward_debug (H_rows: M + h B, as without limits) and fmj_step_fused_f64, limits included: sensordata's
  * jointlimitfrc slots and the fused joints rows' FMJ_JOINT_LIMIT_FORCE carry the limit forces, fmj_data.qacc the acceleration the
  * integrator used, and fmj_data.qacc_warmstart (optional for this context; the solve starts from the unconstrained acceleration and
- * does not read it) the constrained acceleration of the launch's last step. */
-enum { FMJ_CREATE_F64_LIMITS = 1 };
+ * does not read it) the constrained acceleration of the launch's last step.
+ * FMJ_CREATE_F64_RK4 (without precision = FMJ_PRECISION_F64: FMJ_ERR_ARG, before the device lookup): the fp64 context accepts
+ * integrator = FMJ_INT_RK4, at the same sizes, and with FMJ_CREATE_F64_LIMITS | FMJ_CREATE_F64_RK4 a limited RK4 model; without the
+ * flag RK4 stays refused, and with it an Euler or implicitfast model gives the context it gives without it.  Bits 2 and 4 are not
+ * assigned: they are unknown bits and refused.  The four forward passes of mj_RungeKutta (classical tableau) run inside the kernel, one
+ * launch for all n_steps of fmj_step: no stage buffers, no stage launches, fmj_data.qacc optional, fmj_kernel_info reports 128 threads.
+ * No pass has implicit damping (H = M; fmj_forward_debug's H_rows is M), and with limits every pass ends on the minimiser of its own
+ * primal problem.  ctrl, the wave controller's value and the external wrench are held over a step.  A step leaves what mj_step leaves:
+ * sensordata of its first pass, xpos / xquat / xipos and qacc (and qacc_warmstart) of its fourth, time advanced by the timestep.  The
+ * freeze checks are made in every pass, for the whole environment, before anything is stored: a step with a failing pass is undone
+ * (state, poses, sensors and time stay those of the last completed step) and the warning is set.  Covered: fmj_step, fmj_forward (the
+ * first pass alone), fmj_forward_debug and fmj_step_fused_f64, whose links rows and drag pair the fourth pass's poses with the first
+ * pass's link velocities, as fmj_before_step reads them out of fmj_data after an RK4 fmj_step; fmj_step_fused / _ex keep refusing. */
+enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8 };
 typedef struct fmj_create_ext {
   int32_t size;           /* = sizeof(fmj_create_ext); anything else: FMJ_ERR_ARG */
   int32_t flags;          /* FMJ_CREATE_*, or 0 */
