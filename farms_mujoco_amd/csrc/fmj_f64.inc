@@ -38,6 +38,18 @@
 // the active rows, qfrc_constraint = J' f, and one more fill and factorisation of M + h B solved with qfrc_smooth + qfrc_constraint
 // (the constrained qacc itself when nothing is damped).  Every new branch is decided from a workgroup reduction: it is uniform, and every
 // barrier is reached by all 128 threads.
+//
+// fmj_step_f64_contacts_kernel<LIMITS> (fmj_create_ex2 with FMJ_CREATE_F64_CONTACTS; the step's text with F64_STEP_CONTACTS 1, helpers in
+// fmj_f64_contacts.inc) adds ground contacts of sphere / capsule / box geoms under the pyramidal cone: four more unilateral rows per
+// contact in the same Newton solve.  A row e of a contact at world point p with direction u = normal +- mu tangent is one spatial force
+// about the centre of mass, W_e = {(p - com) x u, u}, and J_e[j] = cdof_j . W_e on the dof chain of the contact's body, zero elsewhere.
+// J' D J therefore fills only entries (i, j) with j an ancestor of i - the pattern of M the rows in HR already have - and row i of the
+// Newton matrix is the M stage's with buf_i + sum over active rows of the subtree of i of D_e (W_e . cdof_i) W_e in the place of buf_i.
+// Lane = geom runs the narrow phase (oracle collide_plane) from the pass's poses, a workgroup prefix sum puts the contacts in the
+// oracle's order, lane = contact owns the four rows of its contact (parameters, residuals and forces in registers; W, the active D
+// and the forces in LDS for the dof lanes: F64_CT doubles per contact past the LIMITS block).  J a, J p and J qvel are W_e . the sum
+// of cdof_j x_j over the chain of the contact's body.  A step in which no contact penetrates (and no limit row is a candidate) is the
+// unconstrained step, bit for bit.
 
 #define FMJ_F64_LANES 128
 #define F64_BD 28      // doubles per body: pos(3) mass, quat(4), ipos(3) subtree mass, iquat(4), inertia(3) -, axis(3) qpos0, jnt_pos(3) stiffness
@@ -46,6 +58,10 @@
 #define F64_AD 8       // doubles per actuator (sorted by dof): gain, bias(3), ctrlrange(2), forcerange(2) (infinite where not limited)
 #define F64_SW 10      // doubles per swimming slot: drag coefficients (3 force, 3 torque), mass, height, density, xfrc row
 #define F64_LM 12      // doubles per dof of a limits context: limited (0 / 1), range(2), margin, solref(2), solimp(5), dof_invweight0
+#define F64_GD 24      // doubles per geom of a contacts context: size(3), pos(3), quat(4), friction, invweight0 of its body + the world's, then F64_LM doubles laid out as a limit row's (margin 0, the geom's solref / solimp)
+#define F64_GI 4       // ints per geom: type, body, last dof of the body's chain (-1: none), -
+#define F64_PD 16      // doubles per plane: normal(3), point(3), tangents(6) (oracle add_contact's frame), friction, geom index
+#define F64_CT 33      // doubles of LDS per contact: W of the four rows (24), D of the active rows (4), a row scalar for J' (4), body
 
 struct F64Model {
   int nbody, nv, nq, nu, rs, jump_rounds, anc_stride, root_free, any_stiffness, implicitfast, nsensordata, njs, maxdep, nround;
@@ -78,6 +94,16 @@ struct F64Limits {
   const double* lm;             // [nv][F64_LM]
 };
 
+// What only the contacts kernels read (a fifth argument of theirs).  The solver's settings come in F64Limits, whose lm is NULL
+// when the model has no limited joint.
+struct F64Contacts {
+  int ngeom, nplane, max_contacts;
+  double sqrt_impratio;         // sqrt(impratio), 1 where the model names none
+  const double* gd;             // [ngeom][F64_GD]
+  const int* gi;                // [ngeom][F64_GI]
+  const double* pd;             // [nplane][F64_PD]
+};
+
 // LDS map, in doubles (ints at the end)
 struct LdsLayoutD { int QP, QV, XA, XCH, CD, CI, CR, CF, CS, MX, HR, XW, FLG, total_bytes; };
 __host__ __device__ inline LdsLayoutD ldsd_layout(int nb, int nv, int nq, int rs) {
@@ -103,6 +129,10 @@ __host__ __device__ inline LdsLayoutD ldsd_layout(int nb, int nv, int nq, int rs
 #define F64_LIMITS_LDS_DOUBLES 20
 __host__ __device__ inline int ldsd_total_bytes(int nb, int nv, int nq, int rs, int limits) {
   return ldsd_layout(nb, nv, nq, rs).total_bytes + (limits ? F64_LIMITS_LDS_DOUBLES * 8 : 0);
+}
+// What the contacts kernels append after the LIMITS block (which they always have): F64_CT doubles per contact
+__host__ __device__ inline int ldsd_contacts_bytes(int nb, int nv, int nq, int rs, int max_contacts) {
+  return ldsd_total_bytes(nb, nv, nq, rs, 1) + max_contacts * F64_CT * 8;
 }
 // What the RK4 kernels append after that: the first pass's actuator forces [nu] and controls [nu], kept until the step's fourth pass
 // has passed its checks (each slot is written and read back by the one lane that owns the actuator's dof), then F64_RK4_ROWS rows of
@@ -235,16 +265,15 @@ __device__ __forceinline__ void wg_sum4(double& s0, double& s1, double& s2, doub
   s0 = buf[0] + buf[4]; s1 = buf[1] + buf[5]; s2 = buf[2] + buf[6]; s3 = buf[3] + buf[7];
 }
 
-// One candidate limit row (oracle make_constraints: get_impedance, mj_makeImpedance, mj_referenceConstraint): D = 1 / R and aref from
-// the row's pos = dist, vel = J qvel.  lm: the dof's F64_LM doubles.
+// One candidate row (oracle make_constraints: get_impedance, mj_makeImpedance, mj_referenceConstraint): the impedance and the
+// spring / damper of aref from the row's pos = dist.  lm: F64_LM doubles (a dof's, or the tail of a geom's F64_GD).
 #define F64_MINVAL 1e-15
 #define F64_MINIMP 0.0001
 #define F64_MAXIMP 0.9999
-__device__ __forceinline__ void f64_limit_row(const double* lm, double h, double pos, double vel, double& D, double& aref) {
+__device__ __forceinline__ void f64_row_impedance(const double* lm, double h, double pos, double& imp, double& K, double& B) {
   const double margin = lm[3], sr0 = lm[4], sr1 = lm[5];
   const double dmin = fmin(fmax(lm[6], F64_MINIMP), F64_MAXIMP), dmax = fmin(fmax(lm[7], F64_MINIMP), F64_MAXIMP);
   const double width = fmax(0.0, lm[8]), mid = fmin(fmax(lm[9], F64_MINIMP), F64_MAXIMP), power = fmax(1.0, lm[10]);
-  double imp;
   if (dmin == dmax || width <= F64_MINVAL) imp = 0.5 * (dmin + dmax);
   else {
     const double xx = fabs((pos - margin) / width);
@@ -256,14 +285,18 @@ __device__ __forceinline__ void f64_limit_row(const double* lm, double h, double
     else y = 1.0 - pow(1.0 - xx, power) / pow(1.0 - mid, power - 1.0);
     imp = dmin + y * (dmax - dmin);
   }
-  double K, B;
   if (sr0 > 0.0) {
     const double tc = fmax(sr0, 2.0 * h);
     K = 1.0 / fmax(F64_MINVAL, dmax * dmax * tc * tc * sr1 * sr1);
     B = 2.0 / fmax(F64_MINVAL, dmax * tc);
   } else { K = -sr0 / fmax(F64_MINVAL, dmax * dmax); B = -sr1 / fmax(F64_MINVAL, dmax); }
+}
+// a limit row: D = 1 / R with the dof's invweight0 (lm[11]) and aref from vel = J qvel
+__device__ __forceinline__ void f64_limit_row(const double* lm, double h, double pos, double vel, double& D, double& aref) {
+  double imp, K, B;
+  f64_row_impedance(lm, h, pos, imp, K, B);
   D = 1.0 / fmax(F64_MINVAL, (1.0 - imp) * lm[11] / imp);
-  aref = -B * vel - K * imp * (pos - margin);
+  aref = -B * vel - K * imp * (pos - lm[3]);
 }
 
 // A point of the line search (oracle ls_pt): the cost along the search line and its first two derivatives
@@ -279,9 +312,10 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
   qp[3] = qo.w; qp[4] = qo.x; qp[5] = qo.y; qp[6] = qo.z;
 }
 
-// The step's text (fmj_f64_step.inc), once per integrator family
+// The step's text (fmj_f64_step.inc), once per integrator family, and once more with ground contacts
 #define F64_STEP_KERNEL fmj_step_f64_kernel
 #define F64_STEP_RK4 0
+#define F64_STEP_CONTACTS 0
 #include "fmj_f64_step.inc"
 #undef F64_STEP_KERNEL
 #undef F64_STEP_RK4
@@ -292,10 +326,25 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
 #undef F64_STEP_KERNEL
 #undef F64_STEP_RK4
 #endif
+#undef F64_STEP_CONTACTS
+#if FMJ_TU_F64 == 4
+#include "fmj_f64_contacts.inc"
+#define F64_STEP_KERNEL fmj_step_f64_contacts_kernel
+#define F64_STEP_RK4 0
+#define F64_STEP_CONTACTS 1
+#include "fmj_f64_step.inc"
+#undef F64_STEP_KERNEL
+#undef F64_STEP_RK4
+#undef F64_STEP_CONTACTS
+#endif
 
 // -DFMJ_TU_F64: the two instantiations without limits; -DFMJ_TU_F64=2: the two LIMITS instantiations, a translation unit of their own;
-// -DFMJ_TU_F64=3: the four RK4 instantiations, one more
-#if FMJ_TU_F64 == 3
+// -DFMJ_TU_F64=3: the four RK4 instantiations, one more; -DFMJ_TU_F64=4: the two contacts kernels, one more
+#if FMJ_TU_F64 == 4
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_contacts(int limits) {
+  return limits ? (void*)fmj_step_f64_contacts_kernel<true> : (void*)fmj_step_f64_contacts_kernel<false>;
+}
+#elif FMJ_TU_F64 == 3
 extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_rk4(int fused, int limits) {
   if (limits) return fused ? (void*)fmj_step_f64_rk4_kernel<true, true> : (void*)fmj_step_f64_rk4_kernel<false, true>;
   return fused ? (void*)fmj_step_f64_rk4_kernel<true, false> : (void*)fmj_step_f64_rk4_kernel<false, false>;

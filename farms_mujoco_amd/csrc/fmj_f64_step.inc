@@ -2,9 +2,20 @@
 // and the helpers): with F64_STEP_RK4 0 it is fmj_step_f64_kernel (one forward pass and the semi-implicit Euler commit per step), with
 // F64_STEP_RK4 1 fmj_step_f64_rk4_kernel (the pass loop below runs four times per step; dynamic LDS is ldsd_total_bytes +
 // F64_RK4_LDS_DOUBLES(nu)).  Every `RK4` condition is a compile-time constant: the first kernel compiles to what it was before the loop.
+// With F64_STEP_CONTACTS 1 it is fmj_step_f64_contacts_kernel<LIMITS> (never fused, never RK4; a fifth argument, F64Contacts; dynamic
+// LDS is ldsd_contacts_bytes): ground contacts as four more unilateral rows each in the Newton solve of the LIMITS build.  Every
+// `CONTACTS` condition is a compile-time constant, and CONS = LIMITS || CONTACTS is LIMITS in the other two texts.
+#if F64_STEP_CONTACTS
+template <bool LIMITS>
+__global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model FM, const StepArgs A, const F64Fused U, const F64Limits LM, const F64Contacts CM) {
+  constexpr bool FUSED = false;
+#else
 template <bool FUSED, bool LIMITS>
 __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model FM, const StepArgs A, const F64Fused U, const F64Limits LM) {
+#endif
   constexpr bool RK4 = F64_STEP_RK4 != 0;
+  constexpr bool CONTACTS = F64_STEP_CONTACTS != 0;
+  constexpr bool CONS = LIMITS || CONTACTS;      // the step has a Newton solve
   extern __shared__ __align__(16) double ldsd[];
   const int env = blockIdx.x;
   const int lane = threadIdx.x;
@@ -17,6 +28,9 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
   int* FLG = (int*)(ldsd + L.FLG);
   double* SUM = ldsd + L.total_bytes / 8; int* FLX = (int*)(SUM + 16);      // LIMITS only: past the map (ldsd_total_bytes)
   double* RKS = ldsd + ldsd_total_bytes(nb, nv, nq, rs, LIMITS) / 8;      // RK4 only: past the map and the LIMITS block (F64_RK4_LDS_DOUBLES)
+#if F64_STEP_CONTACTS
+  double* CT = ldsd + ldsd_total_bytes(nb, nv, nq, rs, 1) / 8;            // the contact records (F64_CT doubles each), past the LIMITS block
+#endif
   int sumpar = 0;
 #define WG_SUM4(a_, b_, c_, d_) do { wg_sum4(a_, b_, c_, d_, SUM + sumpar * 8); sumpar ^= 1; } while (0)
 
@@ -36,6 +50,14 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
   const double h = FM.h;
   const double* lmp = LIMITS ? LM.lm + (size_t)dl * F64_LM : nullptr;
   const bool lim_on = LIMITS && d_scalar && lmp[0] != 0.0;
+#if F64_STEP_CONTACTS
+  // lane = geom: its tables; lane = dof: the depth-first range of its body (the contacts of that subtree act on the dof)
+  const bool isg = lane < CM.ngeom;
+  const int gl = isg ? lane : 0;
+  const double* gdp = CM.gd + (size_t)gl * F64_GD;
+  const int g_type = isg ? CM.gi[gl * F64_GI] : -1, g_body = CM.gi[gl * F64_GI + 1];
+  const int d_b0 = isd ? d_body : 1, d_b1 = isd ? d_body + FM.bi[(size_t)d_body * F64_BI + 4] - 1 : 0;
+#endif
 
   // ---- load the state: widened once
   int warn = 0;
@@ -249,6 +271,74 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
       }
     }
     __syncthreads();
+#if F64_STEP_CONTACTS
+    // ---- contacts: the narrow phase (lane = geom) into the oracle's order (ground geom, animat geom, slot), then the four rows of
+    // each contact (lane = contact).  XCH is free between the V stage and the next pass's K: buffer 0 holds the poses, buffer 1 the list
+    int ncon = 0;
+    bool is_c = false;
+    d3 c_pos = dmk(0.0, 0.0, 0.0);
+    int c_geom = 0, c_plane = 0, c_ld = 0, c_dep = 0;
+    double c_mu = 0.0, c_D = 0.0, c_ar0 = 0.0, c_ar1 = 0.0, c_ar2 = 0.0, c_ar3 = 0.0;
+    double c_ja0 = 0.0, c_ja1 = 0.0, c_ja2 = 0.0, c_ja3 = 0.0, c_jp0 = 0.0, c_jp1 = 0.0, c_jp2 = 0.0, c_jp3 = 0.0;      // J a - aref, J p
+    double c_f0 = 0.0, c_f1 = 0.0, c_f2 = 0.0, c_f3 = 0.0;
+    bool c_a0 = false, c_a1 = false, c_a2 = false, c_a3 = false;
+    d6 cbuf = {dmk(0.0, 0.0, 0.0), dmk(0.0, 0.0, 0.0)};      // lane = dof: the contact stiffness of its row
+    {
+      double* XP = XCH; double* XL = XCH + FMJ_F64_LANES * 8;
+      if (lane < nb) {
+        XP[lane * 8 + 0] = xp.x; XP[lane * 8 + 1] = xp.y; XP[lane * 8 + 2] = xp.z;
+        XP[lane * 8 + 4] = xq.w; XP[lane * 8 + 5] = xq.x; XP[lane * 8 + 6] = xq.y; XP[lane * 8 + 7] = xq.z;
+      }
+      __syncthreads();
+      const bool animat = g_type == FMJ_GEOM_SPHERE || g_type == FMJ_GEOM_CAPSULE || g_type == FMJ_GEOM_BOX;
+      const d3 gbp = dmk(XP[g_body * 8], XP[g_body * 8 + 1], XP[g_body * 8 + 2]);
+      const dq gbq = {XP[g_body * 8 + 4], XP[g_body * 8 + 5], XP[g_body * 8 + 6], XP[g_body * 8 + 7]};
+      int ntot = 0;
+#pragma unroll 1
+      for (int p = 0; p < CM.nplane; p++) {
+        const double* pdp = CM.pd + (size_t)p * F64_PD;
+        const int cnt = animat ? f64_ground_contacts(gdp, g_type, gbp, gbq, pdp, lane, p, 0, 0, nullptr) : 0;
+        int tot;
+        const int base = ntot + wg_scan_excl(cnt, FLX + 4, tot);
+        if (cnt > 0 && base < CM.max_contacts) f64_ground_contacts(gdp, g_type, gbp, gbq, pdp, lane, p, base, CM.max_contacts, XL);
+        ntot += tot;
+        __syncthreads();
+      }
+      ncon = ntot;
+      if (ncon > CM.max_contacts) { ncon = CM.max_contacts; warn |= FMJ_WARN_CONTACTFULL; }
+      is_c = lane < ncon;
+      if (is_c) {
+        const double* rec = XL + lane * 8;
+        c_pos = dmk(rec[0], rec[1], rec[2]);
+        const double dist = rec[3];
+        c_geom = (int)rec[4]; c_plane = (int)rec[5];
+        const double* cg = CM.gd + (size_t)c_geom * F64_GD;
+        const double* cp = CM.pd + (size_t)c_plane * F64_PD;
+        const int cb = CM.gi[c_geom * F64_GI + 1];
+        c_ld = CM.gi[c_geom * F64_GI + 2];
+        c_dep = FM.di[(size_t)c_ld * F64_DI + 1];
+        c_mu = fmax(fmax(cp[12], cg[10]), 1e-5);      // max over the two geoms (mj_contactParam), floor mjMINMU
+        const d3 n = dmk(cp[0], cp[1], cp[2]), t1 = dmk(cp[6], cp[7], cp[8]), t2 = dmk(cp[9], cp[10], cp[11]);
+        const d3 off = dsub(c_pos, com);
+        const d6 V = f64_chain_sum(CD, QV, FM.danc, rs, c_ld, c_dep);
+        const double diag = cg[11] + c_mu * c_mu * cg[11];
+        double* ct = CT + lane * F64_CT;
+        double imp, K, B;
+        f64_row_impedance(cg + 12, h, dist, imp, K, B);      // (margin 0)
+        const double R = fmax(F64_MINVAL, (1.0 - imp) * diag / imp);
+#define F64_CONTACT_ROW(r_, t_, sgn_, ar_) do { \
+          const d3 u_ = dadd(n, dscl(t_, (sgn_) * c_mu)); \
+          const d6 W_ = {dcross(off, u_), u_}; \
+          dput6(ct + 6 * (r_), W_); \
+          ar_ = -B * d6dot(W_, V) - K * imp * dist; } while (0)
+        F64_CONTACT_ROW(0, t1, 1.0, c_ar0); F64_CONTACT_ROW(1, t1, -1.0, c_ar1); F64_CONTACT_ROW(2, t2, 1.0, c_ar2); F64_CONTACT_ROW(3, t2, -1.0, c_ar3);
+#undef F64_CONTACT_ROW
+        const double mi = c_mu / CM.sqrt_impratio;      // all rows of a contact share R = 2 mu^2 R_first, mu scaled by 1 / sqrt(impratio)
+        c_D = 1.0 / fmax(F64_MINVAL, 2.0 * mi * mi * R);
+        ct[32] = (double)cb;
+      }
+    }
+#endif
     // ---- S: composite inertia and subtree force: the rows of the lane's own depth-first range, last body first
     if (isb) {
       di10 s = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -315,7 +405,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
     bool c_lo = false, c_hi = false;
     double D_lo = 0.0, D_hi = 0.0, ar_lo = 0.0, ar_hi = 0.0;
     int lflags = 0;      // workgroup: 1 = some row is a candidate, 2 = some dof is damped
-    if (LIMITS) {
+    if (CONS) {
       if (lim_on) {
         const double qj = QP[d_qadr], qd = QV[lane];
         const double dist_lo = qj - lmp[1], dist_hi = lmp[2] - qj;
@@ -323,7 +413,11 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         if (c_lo) f64_limit_row(lmp, h, dist_lo, qd, D_lo, ar_lo);
         if (c_hi) f64_limit_row(lmp, h, dist_hi, -qd, D_hi, ar_hi);
       }
+#if F64_STEP_CONTACTS
+      lflags = wg_or(((c_lo || c_hi || ncon > 0) ? 1 : 0) | ((isd && bdamp != 0.0) ? 2 : 0), FLX + 0);
+#else
       lflags = wg_or(((c_lo || c_hi) ? 1 : 0) | ((isd && bdamp != 0.0) ? 2 : 0), FLX + 0);
+#endif
     }
     // The solve below runs once in a step without candidate rows (phase 2: M + h B, qfrc_smooth).  With candidate rows it runs for
     // a_s (phase 0: M), once per Newton iteration (phase 1: M + D_S, the gradient), and once more for the damped step (phase 2).
@@ -331,7 +425,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
     double hb = RK4 ? 0.0 : bdamp, dadd = 0.0, rhs = isd ? qfrc : 0.0;      // RK4: no implicit damping, H = M in every pass
     double nt_a = 0.0, nt_as = 0.0, nt_r = 0.0, nt_g = 0.0, nt_qfc = 0.0, lim_f = 0.0;      // a, a_s, M (a - a_s), gradient, J' f, the joint's limit force
     bool act_lo = false, act_hi = false;
-    if (LIMITS && (lflags & 1) != 0) { phase = 0; hb = 0.0; }
+    if (CONS && (lflags & 1) != 0) { phase = 0; hb = 0.0; }
     const d6 buf = dinert_mul(dget10(CR + d_body * 10), cd);
     double x;
 #pragma unroll 1
@@ -341,10 +435,15 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
       if (isd) {
         double* row = HR + lane * rs;
         const uint8_t* an = FM.danc + (size_t)lane * rs;
-        for (int d = 0; d < ddepth; d++) row[d] = d6dot(dget6(CD + (int)an[d] * 6), buf);
-        row[ddepth] = (d_arm + d6dot(cd, buf)) + h * hb;
-        if (LIMITS) row[ddepth] += dadd;
-        if (A.dbg_H && (!LIMITS || phase != 1) && (!RK4 || pass == 0)) {
+#if F64_STEP_CONTACTS
+        const d6 bufm = phase == 1 ? d6add(buf, cbuf) : buf;      // the Newton matrix: the composite contact stiffness beside the composite inertia
+#else
+        const d6& bufm = buf;
+#endif
+        for (int d = 0; d < ddepth; d++) row[d] = d6dot(dget6(CD + (int)an[d] * 6), bufm);
+        row[ddepth] = (d_arm + d6dot(cd, bufm)) + h * hb;
+        if (CONS) row[ddepth] += dadd;
+        if (A.dbg_H && (!CONS || phase != 1) && (!RK4 || pass == 0)) {
           for (int d = 0; d < rs; d++) A.dbg_H[((size_t)env * nv + lane) * rs + d] = d <= ddepth ? (float)row[d] : 0.f;
           A.dbg_qfrc[(size_t)env * nv + lane] = (float)qfrc;
         }
@@ -386,15 +485,43 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
       __syncthreads();
       if (isd && ddepth > lvl) x -= (HR[lane * rs + lvl] / Dm) * XW[FM.danc[(size_t)lane * rs + lvl]];
     }
-    if (!LIMITS || phase == 2) break;
+    if (!CONS || phase == 2) break;
     // ---- limits: the Newton iteration on the primal problem (oracle solve_primal, unilateral rows); every branch below is uniform
     bool stop;
     if (phase == 0) {                       // x = a_s: the first iterate, where M (a - a_s) = 0
       nt_as = nt_a = x; nt_r = 0.0;
       phase = 1;
       stop = LM.solver_iterations <= 0;     // (the forces of a_s, as primal_update leaves them)
+#if F64_STEP_CONTACTS
+      __syncthreads();                      // (the sweep's last reads of XW)
+      XW[lane] = x;
+      __syncthreads();
+      if (is_c) {                           // J a_s - aref
+        const d6 S = f64_chain_sum(CD, XW, FM.danc, rs, c_ld, c_dep);
+        const double* ct = CT + lane * F64_CT;
+        c_ja0 = d6dot(dget6(ct), S) - c_ar0; c_ja1 = d6dot(dget6(ct + 6), S) - c_ar1;
+        c_ja2 = d6dot(dget6(ct + 12), S) - c_ar2; c_ja3 = d6dot(dget6(ct + 18), S) - c_ar3;
+      }
+#endif
     } else {                                // x = (M + D_S)^-1 g: the search direction p = -x and M p = -g - D_S p
+#if F64_STEP_CONTACTS
+      const double sp = -x;
+      double cMp = 0.0;                     // (J' D_S J p)_i = cdof_i . sum over the active rows of the subtree of D_e (J p)_e W_e
+      __syncthreads();                      // (the sweep's last reads of XW)
+      XW[lane] = sp;
+      __syncthreads();
+      if (is_c) {
+        const d6 S = f64_chain_sum(CD, XW, FM.danc, rs, c_ld, c_dep);
+        double* ct = CT + lane * F64_CT;
+        c_jp0 = d6dot(dget6(ct), S); c_jp1 = d6dot(dget6(ct + 6), S); c_jp2 = d6dot(dget6(ct + 12), S); c_jp3 = d6dot(dget6(ct + 18), S);
+        ct[28] = c_a0 ? c_D * c_jp0 : 0.0; ct[29] = c_a1 ? c_D * c_jp1 : 0.0; ct[30] = c_a2 ? c_D * c_jp2 : 0.0; ct[31] = c_a3 ? c_D * c_jp3 : 0.0;
+      }
+      __syncthreads();
+      if (isd) { d6 fs, unused; f64_contact_subtree(CT, ncon, d_b0, d_b1, cd, false, fs, unused); cMp = d6dot(cd, fs); }
+      const double Mp = -nt_g - dadd * sp - cMp;
+#else
       const double sp = -x, Mp = -nt_g - dadd * sp;
+#endif
       double s0 = sp * sp, s1 = sp * Mp, s2 = sp * nt_r, s3 = nt_r * (nt_a - nt_as);
       WG_SUM4(s0, s1, s2, s3);
       const double snorm = sqrt(s0), qg0 = 0.5 * s3, qg1 = s2, qg2 = 0.5 * s1;
@@ -405,6 +532,14 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         const double x_lo = j_lo + alpha * sp, x_hi = j_hi - alpha * sp;
         if (c_lo && x_lo < 0.0) { c += 0.5 * D_lo * x_lo * x_lo; e0 += D_lo * x_lo * sp; e1 += D_lo * sp * sp; }
         if (c_hi && x_hi < 0.0) { c += 0.5 * D_hi * x_hi * x_hi; e0 -= D_hi * x_hi * sp; e1 += D_hi * sp * sp; }
+#if F64_STEP_CONTACTS
+        if (is_c) {
+#define F64_LS_ROW(ja_, jp_) do { const double x_ = (ja_) + alpha * (jp_); \
+            if (x_ < 0.0) { c += 0.5 * c_D * x_ * x_; e0 += c_D * x_ * (jp_); e1 += c_D * (jp_) * (jp_); } } while (0)
+          F64_LS_ROW(c_ja0, c_jp0); F64_LS_ROW(c_ja1, c_jp1); F64_LS_ROW(c_ja2, c_jp2); F64_LS_ROW(c_ja3, c_jp3);
+#undef F64_LS_ROW
+        }
+#endif
         WG_SUM4(c, e0, e1, unused);
         F64LsPt pt;
         pt.alpha = alpha; pt.cost = qg0 + alpha * (qg1 + alpha * qg2) + c; pt.d0 = qg1 + 2.0 * alpha * qg2 + e0;
@@ -446,16 +581,40 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         }
       }
       nt_a += alpha * sp; nt_r += alpha * Mp;
+#if F64_STEP_CONTACTS
+      c_ja0 += alpha * c_jp0; c_ja1 += alpha * c_jp1; c_ja2 += alpha * c_jp2; c_ja3 += alpha * c_jp3;
+#endif
       nt_iter++;
       stop = alpha == 0.0 || nt_iter >= LM.solver_iterations;
     }
     // the rows at the iterate (primal_update): active set, forces, J' f, gradient
     const double j_lo = nt_a - ar_lo, j_hi = -nt_a - ar_hi;
     const bool n_lo = c_lo && j_lo < 0.0, n_hi = c_hi && j_hi < 0.0;
+#if F64_STEP_CONTACTS
+    bool changed = n_lo != act_lo || n_hi != act_hi;
+    double qfc_con = 0.0;
+    {
+      const bool n0 = is_c && c_ja0 < 0.0, n1 = is_c && c_ja1 < 0.0, n2 = is_c && c_ja2 < 0.0, n3 = is_c && c_ja3 < 0.0;
+      changed = changed || n0 != c_a0 || n1 != c_a1 || n2 != c_a2 || n3 != c_a3;
+      c_a0 = n0; c_a1 = n1; c_a2 = n2; c_a3 = n3;
+      c_f0 = n0 ? -c_D * c_ja0 : 0.0; c_f1 = n1 ? -c_D * c_ja1 : 0.0; c_f2 = n2 ? -c_D * c_ja2 : 0.0; c_f3 = n3 ? -c_D * c_ja3 : 0.0;
+      if (is_c) {      // (the last readers of these slots passed a workgroup sum since)
+        double* ct = CT + lane * F64_CT;
+        ct[24] = n0 ? c_D : 0.0; ct[25] = n1 ? c_D : 0.0; ct[26] = n2 ? c_D : 0.0; ct[27] = n3 ? c_D : 0.0;
+        ct[28] = c_f0; ct[29] = c_f1; ct[30] = c_f2; ct[31] = c_f3;
+      }
+      __syncthreads();
+      if (isd) { d6 fs; f64_contact_subtree(CT, ncon, d_b0, d_b1, cd, true, fs, cbuf); qfc_con = d6dot(cd, fs); }      // J' f, and the next matrix
+    }
+#else
     const bool changed = n_lo != act_lo || n_hi != act_hi;
+#endif
     act_lo = n_lo; act_hi = n_hi;
     const double f_lo = act_lo ? -D_lo * j_lo : 0.0, f_hi = act_hi ? -D_hi * j_hi : 0.0;
     nt_qfc = f_lo - f_hi; lim_f = f_lo + f_hi;
+#if F64_STEP_CONTACTS
+    nt_qfc += qfc_con;
+#endif
     nt_g = nt_r - nt_qfc;
     {
       double g2 = nt_g * nt_g, u1 = 0.0, u2 = 0.0, u3 = 0.0;
@@ -555,7 +714,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
     if (wg_or(warn & FMJ_WARN_FREEZE, FLG + 2) != 0) frozen = true;
     if (isd && !frozen) {
       XA[lane] = my_qacc;
-      if (LIMITS) { ws_qacc = (lflags & 1) != 0 ? nt_a : my_qacc; if (FUSED) cy_limfrc = lim_f * U.inv_torques; }
+      if (CONS) { ws_qacc = (lflags & 1) != 0 ? nt_a : my_qacc; if (FUSED) cy_limfrc = lim_f * U.inv_torques; }
       QV[lane] = nvel;
       if (d_scalar) {
         const double pre_q = QP[d_qadr];
@@ -566,6 +725,20 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         }
       }
     }
+#if F64_STEP_CONTACTS
+    if (last && !frozen) {      // the contact list of the launch's last pass: pos, frame, force in the contact frame (mju_decodePyramid), geom1 << 16 | geom2
+      if (is_c) {
+        const double* cp = CM.pd + (size_t)c_plane * F64_PD;
+        float* o = A.contact + ((size_t)env * CM.max_contacts + lane) * 16;
+        o[0] = (float)c_pos.x; o[1] = (float)c_pos.y; o[2] = (float)c_pos.z;
+        o[3] = (float)cp[0]; o[4] = (float)cp[1]; o[5] = (float)cp[2];
+        for (int k = 0; k < 6; k++) o[6 + k] = (float)cp[6 + k];
+        o[12] = (float)(c_f0 + c_f1 + c_f2 + c_f3); o[13] = (float)(c_mu * (c_f0 - c_f1)); o[14] = (float)(c_mu * (c_f2 - c_f3));
+        o[15] = __int_as_float(((int)cp[13] << 16) | c_geom);
+      }
+      if (lane == 0) A.ncon[env] = ncon;
+    }
+#endif
     if (!frozen) steps_done++;
     __syncthreads();
     if (jtype == FMJ_JNT_FREE && A.integrate && !frozen) {     // mj_integratePos of the free joint (lane = root body)
@@ -596,7 +769,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
       for (int i = lane; i < nv; i += FMJ_F64_LANES) ov[i] = (float)QV[i];
     }
     if (A.qacc) for (int i = lane; i < nv; i += FMJ_F64_LANES) A.qacc[(size_t)env * nv + i] = (float)XA[i];
-    if (LIMITS && A.qacc_warmstart && A.integrate && isd) A.qacc_warmstart[(size_t)env * nv + lane] = (float)ws_qacc;
+    if (CONS && A.qacc_warmstart && A.integrate && isd) A.qacc_warmstart[(size_t)env * nv + lane] = (float)ws_qacc;
     if (A.time && lane == 0 && A.integrate) A.time[env] = (float)((double)A.time[env] + h * steps_done);
   }
   const int w = wg_or(warn, FLG + 6);

@@ -1527,12 +1527,12 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 // Build layout: this file is compiled once per register row length with -DFMJ_TU_MAXD=<4..64> (only the step-kernel
 // instantiations of that MAXD and a getter for their host stubs), once per row length of the two-wave kernel with
 // -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64, once for its LIMITS instantiations with -DFMJ_TU_F64=2
-// and once for its RK4 kernels with -DFMJ_TU_F64=3 (kernels and getters: fmj_f64.inc + fmj_f64_step.inc), and once without any of
-// them (standalone operators and all host code), in parallel, and the objects are
+// once for its RK4 kernels with -DFMJ_TU_F64=3 and once for its contacts kernels with -DFMJ_TU_F64=4 (kernels and getters: fmj_f64.inc +
+// fmj_f64_step.inc, the last with fmj_f64_contacts.inc), and once without any of them (standalone operators and all host code), in parallel, and the objects are
 // linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
 // Every csrc/*.inc is part of this one source (the build and build_id() depend on all of them):
 //   fmj_cons_rows.inc, fmj_newton.inc          constraint rows and solvers of fmj_step_kernel<.., CONS = true>
-//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc (+ fmj_f64_step.inc)      the other step kernels
+//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc (+ fmj_f64_step.inc, fmj_f64_contacts.inc)      the other step kernels
 //   fmj_stage_{carry_in,step_head,k,c,v,f,q,m,dbg_h,euler_check,euler_commit,euler_root}.inc      stages shared by fmj_step_kernel and fmj_step_wide_kernel
 //   fmj_stage2_{k,c,v,f,s}.inc                 stages shared by fmj_step_dual2_kernel and fmj_step_cons2_kernel
 //   fmj_narrow.inc                             collision helpers (device functions, CONTACT_RECORD), included once ahead of the kernels
@@ -1836,7 +1836,7 @@ void* fmj_tu_kernel_20(int, int); void* fmj_tu_kernel_24(int, int); void* fmj_tu
 void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu_kernel_44(int, int); void* fmj_tu_kernel_48(int, int);
 void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
-void* fmj_tu_f64(int); void* fmj_tu_f64_limits(int); void* fmj_tu_f64_rk4(int, int);
+void* fmj_tu_f64(int); void* fmj_tu_f64_limits(int); void* fmj_tu_f64_rk4(int, int); void* fmj_tu_f64_contacts(int);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -1856,6 +1856,8 @@ struct F64Host {
   F64Limits lim = {};            // limits contexts (fmj_create_ex2, FMJ_CREATE_F64_LIMITS): the fourth kernel argument
   int limits = 0;                // the LIMITS instantiations run every launch of the context
   int rk4 = 0;                   // fmj_create_ex2 with FMJ_CREATE_F64_RK4 and an RK4 model: fmj_step_f64_rk4_kernel runs every launch
+  int contacts = 0;              // fmj_create_ex2 with FMJ_CREATE_F64_CONTACTS and a model with ground contacts: fmj_step_f64_contacts_kernel runs every launch
+  F64Contacts con = {};          // its fifth argument
   size_t lds_bytes = 0;
   std::vector<double> h_ad;      // actuator table mirror (fmj_set_actuator_forcerange)
   std::vector<int> h_asrc;
@@ -1863,6 +1865,7 @@ struct F64Host {
   const double* d_sw = nullptr;  // [nbody][F64_SW] the swimming slots in double: allocated once (a body has at most one slot), filled by fmj_set_swimming
 };
 typedef void (*f64_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits);
+typedef void (*f64_contacts_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits, const F64Contacts);
 static f64_kernel_t f64_kernel(bool fused, int limits, int rk4) {
   return (f64_kernel_t)(rk4 ? fmj_tu_f64_rk4(fused, limits) : limits ? fmj_tu_f64_limits(fused) : fmj_tu_f64(fused));
 }
@@ -1883,6 +1886,14 @@ static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream, 
   if (c->path == PATH_F64) {
     if (fused && !f64_fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: an fp64 context steps through fmj_step; write the rows with fmj_before_step");
     const F64Fused U = f64_fused ? *f64_fused : F64Fused{};      // (the plain step reads none of it)
+    if (c->f64->contacts) {
+      if (fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused_f64: an fp64 context with contacts (FMJ_CREATE_F64_CONTACTS) steps through fmj_step: fused contact rows are not built");
+      if (!A.qacc_warmstart || !A.contact || !A.ncon) return set_err(FMJ_ERR_ARG, "fmj_data: qacc_warmstart, contact and ncon are required for models with limits / contacts");
+      hipLaunchKernelGGL((f64_contacts_kernel_t)fmj_tu_f64_contacts(c->f64->limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream,
+                         c->f64->fm, A, U, c->f64->lim, c->f64->con);
+      if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string("fp64 contacts step kernel launch: ") + hipGetErrorString(e));
+      return FMJ_OK;
+    }
     hipLaunchKernelGGL(f64_kernel(fused, c->f64->limits, c->f64->rk4), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream, c->f64->fm, A, U, c->f64->lim);
     if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string("fp64 step kernel launch: ") + hipGetErrorString(e));
     return FMJ_OK;
@@ -1968,6 +1979,8 @@ struct ModelFacts {
   int f64_limits = 0;         // such a context whose model has limited joints: the LIMITS builds of the fp64 kernel; cons stays 0
   bool f64_rk4_ok = false;    // set by fmj_create_ex2 (FMJ_CREATE_F64_RK4): an fp64 context takes integrator = FMJ_INT_RK4
   int f64_rk4 = 0;            // such a context whose model integrates with RK4: fmj_step_f64_rk4_kernel, four passes inside one launch
+  bool f64_contacts_ok = false; // set by fmj_create_ex2 (FMJ_CREATE_F64_CONTACTS): an fp64 context takes ground contacts
+  int f64_contacts = 0;       // such a context whose model has animat geoms and a plane: fmj_step_f64_contacts_kernel; cons stays 0
   int cons = 0, big = 0;      // limits, contacts or pairs (the constraint kernels); nbody or nv above 64 (past one wavefront)
   int wide = 0;               // every step launch runs the two-wave kernel (fmj_wide.inc): big, or kernel.two_wave
   int nplane = 0, n_hfield = 0, any_mesh = 0, any_box = 0, any_polypair = 0;     // nplane counts the ground geoms: planes and the heightfield
@@ -1977,6 +1990,16 @@ struct ModelFacts {
   int jump_rounds = 0, anc_stride = 0, rs = 0;         // pointer-jumping rounds, bytes per chain row of b_anc, register row length
   int max_contacts = 0, maxefc = 0;
 };
+
+// some ground contact's friction / sqrt(impratio) can fall below 1e-3: too stiff a pyramid for a primal solve (see check_model)
+static bool low_friction_ground_contact(const fmj_model* m) {
+  double gmu = 0;
+  const double isq = 1.0 / sqrt(m->impratio > 0 ? m->impratio : 1.0);      // the rule uses mu = friction / sqrt(impratio)
+  for (int g = 0; g < m->ngeom; g++) if (m->geom_type[g] == FMJ_GEOM_PLANE || m->geom_type[g] == FMJ_GEOM_HFIELD) gmu = std::max(gmu, m->geom_friction[3 * g]);
+  for (int g = 0; g < m->ngeom; g++)
+    if (m->geom_type[g] != FMJ_GEOM_PLANE && m->geom_type[g] != FMJ_GEOM_HFIELD && std::max(gmu, m->geom_friction[3 * g]) * isq < 1e-3) return true;
+  return false;
+}
 
 static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   if (m->abi_version != FMJ_ABI_VERSION) return set_err(FMJ_ERR_ARG, "fmj_create: abi_version mismatch");
@@ -2028,6 +2051,32 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
     // on request (fmj_create_ex2) it solves joint limits itself: such a model is no constraint-path model to the stages below,
     // whose limits (64 bodies / dofs, a dof chain of 32, 192 rows) belong to the fp32 constraint kernels
     if (F->f64_limits_ok) { any_limit = 0; cons = (nplane > 0 && m->ngeom > nplane) || m->npair > 0; }
+    // on request it solves ground contacts too (FMJ_CREATE_F64_CONTACTS): body-vs-world rows keep the tree-sparse pattern of M
+    if (F->f64_contacts_ok && !any_limit && cons) {
+      const auto no = [](const char* what) { return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex2: the fp64 contact solve (FMJ_CREATE_F64_CONTACTS) has no ") + what); };
+      if (m->npair > 0) return no("explicit contact pairs (their rows couple two chains: outside the tree-sparse pattern of M)");
+      for (int g = 0; g < m->ngeom; g++) {
+        const int t = m->geom_type[g];
+        if (t == FMJ_GEOM_HFIELD) return no("heightfield geoms");
+        if (t == FMJ_GEOM_CYLINDER) return no("cylinder geoms");
+        if (t == FMJ_GEOM_MESH) return no("mesh geoms");
+      }
+      if (m->cone != FMJ_CONE_PYRAMIDAL) return no("elliptic cone (pyramidal only)");
+      if (m->noslip_iterations > 0) return no("noslip post-pass (noslip_iterations > 0)");
+      if (m->integrator == FMJ_INT_RK4) return no("RK4 (Euler or implicitfast only, also with FMJ_CREATE_F64_RK4)");
+      if (m->max_contacts > FMJ_F64_LANES) return no("lane for every contact: max_contacts > 128");
+      if (m->ngeom > FMJ_F64_LANES) return no("lane for every geom: more than 128 geoms");
+      if (m->max_contacts >= 1 && low_friction_ground_contact(m))
+        return no("primal solve for a ground contact whose friction / sqrt(impratio) can fall below 1e-3 (rows too stiff for it: the fp32 constraint path solves such a model on the dual problem)");
+      if (m->solver_iterations < 0 || !(m->solver_tolerance >= 0)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
+      for (int g = 0; g < m->ngeom; g++) {
+        if (m->geom_type[g] == FMJ_GEOM_PLANE) continue;
+        int a = m->geom_bodyid[g];
+        while (a >= 1 && m->body_dofnum[a] == 0) a = m->body_parentid[a];
+        if (a < 1) return no("rows for a collision geom on a body without dofs");
+      }
+      F->f64_contacts = 1; cons = 0;
+    }
     if (cons) return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex: the fp64 step has no constraint solver: the model has ") +
                              (any_limit ? "joint limits" : m->npair > 0 ? "explicit contact pairs" : "contact geoms"));
     if (F->f64_limits_ok) for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) F->f64_limits = 1;
@@ -2043,13 +2092,7 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   // iteration (see fmj_cons_rows.inc on the friction-0 pairs).  Such a model is solved on the dual problem throughout: the PGS
   // kernels, run to the solver's tolerance (up to 10 x solver_iterations sweeps) - the same convex problem, the same minimiser.
   bool& dual_instead = F->dual_instead;
-  if (cons && m->solver != FMJ_SOLVER_PGS && m->cone == FMJ_CONE_PYRAMIDAL && nplane > 0) {
-    double gmu = 0;
-    const double isq = 1.0 / sqrt(m->impratio > 0 ? m->impratio : 1.0);      // the rule uses mu = friction / sqrt(impratio)
-    for (int g = 0; g < m->ngeom; g++) if (m->geom_type[g] == FMJ_GEOM_PLANE || m->geom_type[g] == FMJ_GEOM_HFIELD) gmu = std::max(gmu, m->geom_friction[3 * g]);
-    for (int g = 0; g < m->ngeom; g++)
-      if (m->geom_type[g] != FMJ_GEOM_PLANE && m->geom_type[g] != FMJ_GEOM_HFIELD && std::max(gmu, m->geom_friction[3 * g]) * isq < 1e-3) dual_instead = true;
-  }
+  if (cons && m->solver != FMJ_SOLVER_PGS && m->cone == FMJ_CONE_PYRAMIDAL && nplane > 0 && low_friction_ground_contact(m)) dual_instead = true;
   // The noslip post-pass works on the dual matrices, which the primal solvers never form; explicit pairs under the elliptic cone have the
   // dual block update only (fmj_cons_rows.inc (8c)).  Such a model requested with Newton / CG is solved on the dual problem as well.
   if (cons && m->solver != FMJ_SOLVER_PGS && (m->noslip_iterations > 0 || (m->cone == FMJ_CONE_ELLIPTIC && m->npair > 0))) dual_instead = true;
@@ -2128,6 +2171,13 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   // the block solvers (elliptic PGS, noslip) keep forces, b, R and mu of every row in the LDS staging area of the row code: min(maxefc, 64) * rs floats
   if (cons && (m->noslip_iterations > 0 || (m->cone == FMJ_CONE_ELLIPTIC && (m->solver == FMJ_SOLVER_PGS || dual_instead))) && std::min(F->maxefc, FMJ_NA) * F->rs < 4 * F->maxefc)
     return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: PGS with the elliptic cone / noslip: too many constraint rows for this model's row length (needs min(maxefc, 64) * rs >= 4 * maxefc): lower max_contacts");
+  if (F->f64_contacts) {      // what fmj_constraint_info reports; the LDS of fmj_step_f64_contacts_kernel at this model's sizes
+    F->max_contacts = m->max_contacts; F->maxefc = 2 * nj + 4 * m->max_contacts;
+    const int bytes = ldsd_contacts_bytes(nb, nv, nq, r4(max_ddepth + 1), m->max_contacts);
+    if (bytes > 160 * 1024)
+      return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex2: the fp64 contact solve (FMJ_CREATE_F64_CONTACTS) needs " + std::to_string(bytes) +
+                                          " bytes of LDS for this model (its bodies, dofs, dof chain and max_contacts), above 160 KB: lower max_contacts");
+  }
   if (F->wide && (size_t)ldsw_layout(nb, nv, nq, F->rs, F->anc_stride).total * sizeof(float) > 64 * 1024)
     return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: two-wave kernel LDS above 64 KB");     // (cannot happen within the size limits above)
   return FMJ_OK;
@@ -2137,7 +2187,7 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
 static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
   const int nb = m->nbody, nv = m->nv, nj = m->njnt;
   DevModel& D = c->dm;
-  c->solver_requested = (F.cons || F.f64_limits) ? m->solver : FMJ_SOLVER_PGS;
+  c->solver_requested = (F.cons || F.f64_limits || F.f64_contacts) ? m->solver : FMJ_SOLVER_PGS;
   c->nbody = nb; c->nv = nv; c->nu = m->nu; c->njnt = nj;
   c->rk4 = m->integrator == FMJ_INT_RK4 && !F.f64_rk4;      // (an fp64 RK4 context runs its passes inside the kernel: no stage buffers, no stage launches)
   D.nbody = nb; D.nv = nv; D.nq = m->nq; D.nu = m->nu; D.njnt = nj; D.nM = m->nM;
@@ -2171,7 +2221,7 @@ static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) 
   D.solver_iterations = F.dual_instead ? 10 * m->solver_iterations : m->solver_iterations; D.solver_tolerance = (float)m->solver_tolerance;
   D.cone = cons ? m->cone : FMJ_CONE_PYRAMIDAL;
   D.noslip_iterations = cons ? m->noslip_iterations : 0; D.noslip_tolerance = (float)m->noslip_tolerance;
-  D.solver = F.f64_limits ? FMJ_SOLVER_NEWTON : (cons && !F.dual_instead) ? m->solver : FMJ_SOLVER_PGS; D.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
+  D.solver = (F.f64_limits || F.f64_contacts) ? FMJ_SOLVER_NEWTON : (cons && !F.dual_instead) ? m->solver : FMJ_SOLVER_PGS; D.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
   D.ls_tolerance = (float)(m->ls_tolerance > 0 ? m->ls_tolerance : 0.01);
   D.impratio_isqrt = (float)(1.0 / sqrt(m->impratio > 0 ? m->impratio : 1.0));
   D.pgs_scale = (float)(1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1)));
@@ -2613,6 +2663,11 @@ static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
       (rc = upload_f64(c, ad, &M.ad)) || (rc = upload_f64(c, asrc, &M.asrc)) || (rc = upload_f64(c, danc, &M.danc)) || (rc = upload_f64(c, rw, &M.rounds)))
     return rc;
   M.b_anc = D.b_anc;
+  if (F.f64_limits || F.f64_contacts) {      // the Newton solve's settings
+    H.lim.solver_iterations = m->solver_iterations; H.lim.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
+    H.lim.tolerance = m->solver_tolerance; H.lim.ls_tolerance = m->ls_tolerance > 0 ? m->ls_tolerance : 0.01;
+    H.lim.scale = 1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1));
+  }
   if (F.f64_limits) {      // the rows' constants, unrounded (oracle make_constraints)
     std::vector<double> lm((size_t)nv * F64_LM, 0.0);
     for (int j = 0; j < nj; j++) {
@@ -2625,12 +2680,48 @@ static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
     }
     if ((rc = upload_f64(c, lm, &H.lim.lm))) return rc;
     H.limits = 1;
-    H.lim.solver_iterations = m->solver_iterations; H.lim.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
-    H.lim.tolerance = m->solver_tolerance; H.lim.ls_tolerance = m->ls_tolerance > 0 ? m->ls_tolerance : 0.01;
-    H.lim.scale = 1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1));
   }
   H.rk4 = F.f64_rk4;
   H.lds_bytes = (size_t)ldsd_total_bytes(nb, nv, m->nq, M.rs, H.limits) + (H.rk4 ? (size_t)F64_RK4_LDS_DOUBLES(m->nu) * 8 : 0);
+  if (F.f64_contacts) {      // the geom and plane tables, unrounded (oracle collide_plane, add_contact, make_constraints)
+    F64Contacts& C = H.con;
+    C.ngeom = m->ngeom; C.nplane = F.nplane; C.max_contacts = m->max_contacts; C.sqrt_impratio = sqrt(m->impratio > 0 ? m->impratio : 1.0);
+    std::vector<double> gd((size_t)m->ngeom * F64_GD, 0.0), pd((size_t)F.nplane * F64_PD, 0.0);
+    std::vector<int> gi((size_t)m->ngeom * F64_GI, 0);
+    int ip = 0;
+    for (int g = 0; g < m->ngeom; g++) {
+      double* t = &gd[(size_t)g * F64_GD]; int* ti = &gi[(size_t)g * F64_GI];
+      const int b = m->geom_bodyid[g];
+      for (int k = 0; k < 3; k++) { t[k] = m->geom_size[3 * g + k]; t[3 + k] = m->geom_pos[3 * g + k]; }
+      for (int k = 0; k < 4; k++) t[6 + k] = m->geom_quat[4 * g + k];
+      t[10] = m->geom_friction[3 * g]; t[11] = m->body_invweight0[2 * b] + m->body_invweight0[0];
+      t[16] = m->geom_solref[2 * g]; t[17] = m->geom_solref[2 * g + 1];
+      for (int k = 0; k < 5; k++) t[18 + k] = m->geom_solimp[5 * g + k];
+      int a = b;
+      while (a >= 1 && m->body_dofnum[a] == 0) a = m->body_parentid[a];
+      ti[0] = m->geom_type[g]; ti[1] = b; ti[2] = a >= 1 ? m->body_dofadr[a] + m->body_dofnum[a] - 1 : -1;
+      if (m->geom_type[g] != FMJ_GEOM_PLANE) continue;
+      // world-attached plane: normal = z axis of the geom frame (mju_quat2Mat of the geom's quaternion), point = geom_pos; the frame of add_contact
+      const double* q = m->geom_quat + 4 * g;
+      double* pt = &pd[(size_t)ip++ * F64_PD];
+      const double n[3] = {2.0 * (q[1] * q[3] + q[0] * q[2]), 2.0 * (q[2] * q[3] - q[0] * q[1]), q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3]};
+      double t1[3] = {0, 0, 0};
+      if (n[1] < -0.5 || n[1] > 0.5) t1[2] = 1; else t1[1] = 1;
+      const double dt = t1[0] * n[0] + t1[1] * n[1] + t1[2] * n[2];
+      for (int k = 0; k < 3; k++) t1[k] -= dt * n[k];
+      const double nn = sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
+      for (int k = 0; k < 3; k++) { pt[k] = n[k]; pt[3 + k] = m->geom_pos[3 * g + k]; pt[6 + k] = t1[k] / nn; }
+      pt[9] = pt[1] * pt[8] - pt[2] * pt[7]; pt[10] = pt[2] * pt[6] - pt[0] * pt[8]; pt[11] = pt[0] * pt[7] - pt[1] * pt[6];
+      pt[12] = m->geom_friction[3 * g]; pt[13] = g;
+    }
+    if ((rc = upload_f64(c, gd, &C.gd)) || (rc = upload_f64(c, gi, &C.gi)) || (rc = upload_f64(c, pd, &C.pd))) return rc;
+    H.contacts = 1;
+    H.lds_bytes = (size_t)ldsd_contacts_bytes(nb, nv, m->nq, M.rs, m->max_contacts);      // (check_model held it to 160 KB)
+    if (hipFuncSetAttribute((const void*)fmj_tu_f64_contacts(H.limits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
+      return set_err(FMJ_ERR_HIP, "fmj_create_ex2: LDS request of the fp64 contacts step kernel too large");
+    c->path = PATH_F64;
+    return sync_f64_maps(c);
+  }
   if (H.lds_bytes > 160 * 1024) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: fp64 step kernel LDS above 160 KB");     // (cannot happen within the size limits)
   for (int fused = 0; fused < 2; fused++)
     if (hipFuncSetAttribute((const void*)f64_kernel(fused, H.limits, H.rk4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
@@ -2664,11 +2755,13 @@ int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj
   if (!m || !out || n_envs <= 0) return set_err(FMJ_ERR_ARG, "fmj_create: NULL model/out or n_envs <= 0");
   *out = nullptr;
   if (ext && ext->size != (int32_t)sizeof(fmj_create_ext)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: fmj_create_ext.size is not sizeof(fmj_create_ext)");
-  if (ext && (ext->flags & ~(int32_t)(FMJ_CREATE_F64_LIMITS | FMJ_CREATE_F64_RK4))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: unknown bits in fmj_create_ext.flags");
+  if (ext && (ext->flags & ~(int32_t)(FMJ_CREATE_F64_LIMITS | FMJ_CREATE_F64_RK4 | FMJ_CREATE_F64_CONTACTS))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: unknown bits in fmj_create_ext.flags");
   if (ext && (ext->flags & FMJ_CREATE_F64_LIMITS) && !(opts && opts->precision == FMJ_PRECISION_F64))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_LIMITS needs precision = FMJ_PRECISION_F64 (the limits solve belongs to the fp64 step kernel)");
   if (ext && (ext->flags & FMJ_CREATE_F64_RK4) && !(opts && opts->precision == FMJ_PRECISION_F64))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_RK4 needs precision = FMJ_PRECISION_F64 (the in-kernel RK4 belongs to the fp64 step kernel)");
+  if (ext && (ext->flags & FMJ_CREATE_F64_CONTACTS) && !(opts && opts->precision == FMJ_PRECISION_F64))
+    return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_CONTACTS needs precision = FMJ_PRECISION_F64 (the contact solve belongs to the fp64 step kernel)");
   if (opts && opts->size != 8 && opts->size != (int32_t)sizeof(fmj_create_options))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex: fmj_create_options.size is neither sizeof(fmj_create_options) nor 8 (the struct before the kernel fields)");
   const int precision = opts ? opts->precision : FMJ_PRECISION_F32;
@@ -2676,6 +2769,7 @@ int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj
   ModelFacts F;
   F.f64_limits_ok = ext && (ext->flags & FMJ_CREATE_F64_LIMITS);
   F.f64_rk4_ok = ext && (ext->flags & FMJ_CREATE_F64_RK4);
+  F.f64_contacts_ok = ext && (ext->flags & FMJ_CREATE_F64_CONTACTS);
   if (int rc = resolve_kernel_choice(opts, &F.kernel)) return rc;
   if (int rc = check_model(m, &F, precision)) return rc;
   int ndev = 0;
@@ -2968,6 +3062,7 @@ int fmj_step_fused_ex(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, co
 }
 
 int fmj_step_fused_f64(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, const fmj_fused_ext* ext, void* stream) {
+  if (c && c->f64 && c->f64->contacts) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused_f64: an fp64 context with contacts (FMJ_CREATE_F64_CONTACTS) steps through fmj_step: fused contact rows are not built");
   StepArgs A; int rc = fused_step_args(c, d, a, ext, FMJ_PRECISION_F64, &A); if (rc) return rc;
   if (a->rows_base.contacts) return set_err(FMJ_ERR_ARG, "fmj_step_fused_f64: contact rows: an fp64 model has no collision geoms");
   if (a->rows_ahead) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused_f64: rows_ahead is not built for the fp64 step kernel (write the rows with fmj_before_step instead)");

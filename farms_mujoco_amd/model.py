@@ -811,15 +811,31 @@ def eel(n_joints: int = 20, timestep: float = 1e-3) -> Model:
     return b.compile()
 
 
-def centipede(n_segments: int = 10, n_spine_joints: int = 15, timestep: float = 1e-3, full_actuators: bool = False) -> Model:
+CENTIPEDE_LEG_PITCH = 0.6      # centipede(contacts=True): how far below the horizontal the lower legs point at qpos0 (rad)
+
+
+def centipede_touch_height(foot_radius: float = 0.0015) -> float:
+    """Height of the root of ``centipede(contacts=True)`` at which its foot spheres touch the plane z = 0 at qpos0."""
+    return 0.015*np.sin(CENTIPEDE_LEG_PITCH) + foot_radius
+
+
+def centipede(n_segments: int = 10, n_spine_joints: int = 15, timestep: float = 1e-3, full_actuators: bool = False,
+              contacts: bool = False) -> Model:
     """Config-5 centipede: free + 15 spine hinges + 2x2-DoF legs on 10 segments (nv = 61).  ``full_actuators``: the position /
-    velocity / motor triple of mjcf.py:819-854 on every joint (salamander33's layout) instead of the position actuator alone."""
+    velocity / motor triple of mjcf.py:819-854 on every joint (salamander33's layout) instead of the position actuator alone.
+    ``contacts``: the walking model - a capsule on each spine segment and a sphere at each leg tip (friction 1.0), the friction-0
+    world plane z = 0 (mjcf.py:1202), the lower legs pointing ``CENTIPEDE_LEG_PITCH`` below the horizontal at qpos0, leg joints damped at 4e-4, spawned with the
+    feet 0.2 mm into the ground, and ``max_contacts`` for every possible contact (two per capsule, one per foot; at most 128).
+    centipede(20, 25, contacts=True) steps only in an fp64 context made with ``fp64_contacts=True`` (107 bodies)."""
     b = ModelBuilder('centipede', timestep=timestep)
     L, r = 0.03, 0.006
     n = n_spine_joints + 1
     mass = 1000.0*(np.pi*r*r*L + 4.0/3.0*np.pi*r**3)
+    foot_r = 0.0015
+    spawn_z = centipede_touch_height(foot_r) - 2e-4 if contacts else -0.1
+    leg_damping = 4e-4 if contacts else 5e-5      # standing on its 2 n_segments legs the body is a mass on their springs: near critical damping
     for i in range(n):
-        kw = dict(pos=(0, 0, -0.1) if i == 0 else (L, 0, 0), mass=mass, ipos=(L/2, 0, 0),
+        kw = dict(pos=(0, 0, spawn_z) if i == 0 else (L, 0, 0), mass=mass, ipos=(L/2, 0, 0),
                   inertia=_capsule_inertia(mass, r, L))
         if i == 0:
             b.add_body('body_0', 'world', joint='free', **kw)
@@ -828,18 +844,27 @@ def centipede(n_segments: int = 10, n_spine_joints: int = 15, timestep: float = 
                        damping=2e-4, **kw)
         b.set_swimming(f'body_{i}', drag_coefficients=[[-0.005, -0.3, -0.3], [-1e-6, -1e-5, -1e-5]],
                        height=0.5*(L/2 + r))
+        if contacts:
+            b.add_geom(f'body_{i}', GEOM_CAPSULE, (r, L/2), pos=(L/2, 0, 0), quat=axisangle2quat([0, 1, 0], np.pi/2), friction=(1.0, 0, 0))
         if i < n_segments:
             for side, sname in ((+1, 'L'), (-1, 'R')):
                 up = f'leg_{i}_{sname}_0'
                 lo = f'leg_{i}_{sname}_1'
                 b.add_body(up, f'body_{i}', pos=(L/2, side*r, 0), mass=2e-4, inertia=(5e-7,)*3, joint='hinge',
-                           jname=f'joint_{up}', axis=(0, 0, 1), damping=5e-5)
+                           jname=f'joint_{up}', axis=(0, 0, 1), damping=leg_damping)
                 lm = 1000.0*np.pi*0.0015**2*0.015
+                lq = dict(quat=axisangle2quat([1, 0, 0], -side*CENTIPEDE_LEG_PITCH)) if contacts else {}      # the leg's y axis points outwards and down
                 b.add_body(lo, up, pos=(0, side*0.004, 0), mass=lm, ipos=(0, side*0.0075, 0),
                            inertia=(lm*0.015**2/12 + 2e-7, 2e-7, lm*0.015**2/12 + 2e-7), joint='hinge', jname=f'joint_{lo}',
-                           axis=(1, 0, 0), damping=5e-5)
+                           axis=(1, 0, 0), damping=leg_damping, **lq)
+                if contacts:
+                    b.add_geom(lo, GEOM_SPHERE, (foot_r,), pos=(0, side*0.015, 0), friction=(1.0, 0, 0))
                 b.set_swimming(up, drag_coefficients=[[-1e-4]*3, [-1e-7]*3], height=0.001)
                 b.set_swimming(lo, drag_coefficients=[[-0.02, -0.0002, -0.02], [-1e-7]*3], height=0.004)
+    if contacts:
+        b.add_geom('world', GEOM_PLANE, (0, 0, 0), friction=(0, 0, 0))     # arena friction 0 (mjcf.py:1202)
+        b.options['max_contacts'] = 2*n + 2*n_segments
+        assert b.options['max_contacts'] <= 128, 'one lane per contact in the fp64 contact solve'
     for jn in [x for x in [bd.joint['name'] for bd in b.bodies[1:] if bd.joint] if not x.startswith('root_')]:
         kp = 0.2 if jn.startswith('joint_body_') else 0.05
         if full_actuators:

@@ -41,7 +41,7 @@ class BatchedPhysics:
     """Device-resident mjData for ``n_envs`` copies of one model + the HIP step context."""
 
     def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None, fp64_fused: bool = False,
-                 fp64_limits: bool = False, fp64_rk4: bool = False):
+                 fp64_limits: bool = False, fp64_rk4: bool = False, fp64_contacts: bool = False):
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
         # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
         # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
@@ -59,6 +59,16 @@ class BatchedPhysics:
         # all steps of fmj_step (fmj_create_ex2, FMJ_CREATE_F64_RK4; include/fmj.h); with fp64_fused such a run fuses too.
         if fp64_rk4 and precision != 'fp64':
             raise ValueError(f"fp64_rk4=True needs precision='fp64', not {precision!r}: an fp32 context integrates RK4 with four launches per step")
+        # fp64_contacts: the fp64 context takes ground contacts (sphere / capsule / box geoms against world planes, pyramidal cone) as
+        # more rows of the same Newton solve (fmj_create_ex2, FMJ_CREATE_F64_CONTACTS; include/fmj.h) - walking models past the
+        # sizes of the fp32 constraint path.  Such a context steps through fmj_step only: no fused launch, no RK4.
+        if fp64_contacts and precision != 'fp64':
+            raise ValueError(f"fp64_contacts=True needs precision='fp64', not {precision!r}: an fp32 context solves contacts on its constraint path")
+        if fp64_contacts and fp64_fused:
+            raise ValueError('fp64_contacts=True does not go with fp64_fused=True: fused contact rows are not built for the fp64 step')
+        if fp64_contacts and fp64_rk4:
+            raise ValueError('fp64_contacts=True does not go with fp64_rk4=True: the fp64 contact solve integrates with Euler or implicitfast')
+        self.fp64_contacts = bool(fp64_contacts)
         self.fp64_fused = bool(fp64_fused)
         self.fp64_limits = bool(fp64_limits)
         self.fp64_rk4 = bool(fp64_rk4)
@@ -84,10 +94,11 @@ class BatchedPhysics:
             flags = (k.two_wave * _lib.KERNEL_TWO_WAVE | (not k.two_env) * _lib.KERNEL_ONE_ENV_PER_WAVE |
                      (not k.lean) * _lib.KERNEL_NO_LEAN | (not k.prio) * _lib.KERNEL_NO_PRIO)
             opts = _lib.CCreateOptions(ctypes.sizeof(_lib.CCreateOptions), _lib.PRECISIONS[precision], flags, k.wps or 0)
-            if fp64_limits or fp64_rk4:
+            if fp64_limits or fp64_rk4 or fp64_contacts:
                 if not _lib.has('fmj_create_ex2'):      # an A/B base build (FMJ_SO)
-                    raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex2: fp64_limits=True / fp64_rk4=True need a current build')
-                ext = _lib.CCreateExt(ctypes.sizeof(_lib.CCreateExt), bool(fp64_limits) * _lib.CREATE_F64_LIMITS | bool(fp64_rk4) * _lib.CREATE_F64_RK4)
+                    raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex2: fp64_limits=True / fp64_rk4=True / fp64_contacts=True need a current build')
+                ext = _lib.CCreateExt(ctypes.sizeof(_lib.CCreateExt), bool(fp64_limits) * _lib.CREATE_F64_LIMITS | bool(fp64_rk4) * _lib.CREATE_F64_RK4 |
+                                      bool(fp64_contacts) * _lib.CREATE_F64_CONTACTS)
                 rc = self._lib.fmj_create_ex2(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
                                               ctypes.byref(opts), ctypes.byref(ext), ctypes.byref(ctx))
             else:
@@ -123,9 +134,10 @@ class BatchedPhysics:
         rq, ef, it = _lib.ints(self._lib.fmj_solver_info, self._ctx) if _lib.has('fmj_solver_info') else (0, 0, 0)     # absent only from an A/B base build (FMJ_SO)
         names = {0: 'PGS', 1: 'CG', 2: 'Newton'}
         self.solver_requested, self.solver_effective, self.solver_budget = names[rq], names[ef], it
-        if rq != ef and self.fp64_limits:      # (raised only when the model asked for PGS or CG: Newton is what runs)
+        if rq != ef and (self.fp64_limits or self.fp64_contacts):      # (raised only when the model asked for PGS or CG: Newton is what runs)
             import warnings
-            warnings.warn(f'solver={self.solver_requested!r} was requested, but the fp64 step solves joint limits with its primal Newton solve: '
+            what = 'joint limits' if not self.fp64_contacts else 'limits and contacts'
+            warnings.warn(f'solver={self.solver_requested!r} was requested, but the fp64 step solves {what} with its primal Newton solve: '
                           f'{self.solver_effective}, until the active set stops changing or {self.solver_budget} iterations per step '
                           '(same minimiser; include/fmj.h: fmj_create_ex2)', stacklevel=2)
         elif rq != ef:

@@ -333,7 +333,7 @@ int fmj_create_ex(const fmj_model* model, int32_t n_envs, int32_t device, const 
 int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
 /* fmj_create_ex with an extension struct (additive: FMJ_ABI_VERSION stays 6; fmj_model, fmj_data and fmj_create_options do not
  * change).  ext == NULL or flags == 0 is fmj_create_ex: the same path, the same bits.  FMJ_ERR_ARG, decided before the device lookup:
- * another size, an unknown flag bit, FMJ_CREATE_F64_LIMITS or FMJ_CREATE_F64_RK4 without precision = FMJ_PRECISION_F64.
+ * another size, an unknown flag bit, FMJ_CREATE_F64_LIMITS, FMJ_CREATE_F64_RK4 or FMJ_CREATE_F64_CONTACTS without precision = FMJ_PRECISION_F64.
  * FMJ_CREATE_F64_LIMITS: the fp64 context accepts a model whose only constraints are joint limits on hinge and slide joints, within the
  * fp64 kernel's own sizes (nbody, nv <= 128, dof chain <= 64, Euler or implicitfast); the limits of the fp32 constraint path (64 bodies
  * / dofs, a dof chain of 32, 192 rows) do not apply.  Contact geoms, explicit pairs and (without FMJ_CREATE_F64_RK4) RK4 stay refused as by fmj_create_ex.  The
@@ -357,8 +357,26 @@ int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
  * freeze checks are made in every pass, for the whole environment, before anything is stored: a step with a failing pass is undone
  * (state, poses, sensors and time stay those of the last completed step) and the warning is set.  Covered: fmj_step, fmj_forward (the
  * first pass alone), fmj_forward_debug and fmj_step_fused_f64, whose links rows and drag pair the fourth pass's poses with the first
- * pass's link velocities, as fmj_before_step reads them out of fmj_data after an RK4 fmj_step; fmj_step_fused / _ex keep refusing. */
-enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8 };
+ * pass's link velocities, as fmj_before_step reads them out of fmj_data after an RK4 fmj_step; fmj_step_fused / _ex keep refusing.
+ * FMJ_CREATE_F64_CONTACTS (without precision = FMJ_PRECISION_F64: FMJ_ERR_ARG, before the device lookup; bit 16 is not assigned
+ * either): the fp64 context accepts a model with max_contacts > 0, sphere, capsule and box geoms on the animat and world-attached
+ * planes, at the fp64 kernel's own sizes (nbody, nv <= 128, dof chain <= 64, Euler or implicitfast) - ground contacts past the 64
+ * bodies / dofs of the fp32 constraint path.  A model that also has joint limits needs FMJ_CREATE_F64_LIMITS | FMJ_CREATE_F64_CONTACTS.
+ * Under the pyramidal cone a contact is four more unilateral rows of the limits' primal Newton solve.  The Jacobian of a ground contact
+ * on body b is non-zero only on the dofs of b's ancestor chain, so J' D J fills only entries (i, j) with j an ancestor of i, the pattern
+ * of M, and the tree-sparse factorisation stays exact.  Refused with FMJ_ERR_UNSUPPORTED before the device lookup, "fp64" and the
+ * thing named in the message: explicit pairs (they couple two chains), heightfield, cylinder and mesh geoms, the elliptic cone,
+ * noslip_iterations > 0, RK4 (also with FMJ_CREATE_F64_RK4), max_contacts > 128 or more than 128 geoms (one lane each), a geom on a
+ * body without dofs, a contact whose friction / sqrt(impratio) can fall below 1e-3 (fmj_solver_info's rule: too stiff for a primal
+ * solve) and a model whose LDS at these sizes exceeds 160 KB (the bytes are named: nbody = nv = 128 with a dof chain of 64 and 128
+ * contacts fits).  Without the flag every refusal is what it was.  The solver is the Newton solve whatever the model names
+ * (fmj_solver_info as with limits); fmj_constraint_info reports maxefc = 2 njnt + 4 max_contacts.  The context covers fmj_step (any
+ * n_steps, ctrl tape), fmj_forward and fmj_forward_debug; fmj_step_fused_f64 refuses it (fused contact rows are not built).  A step
+ * leaves fmj_data.contact and ncon as the fp32 constraint path does (contacts ordered by ground geom, animat geom, slot within the
+ * geom; FMJ_WARN_CONTACTFULL when the list is truncated at max_contacts, which does not freeze), qacc, qacc_warmstart and jointlimitfrc
+ * as a limits context; fmj_contacts2data and fmj_before_step work unchanged from those fields.  A step in which no contact penetrates
+ * and no limit is within its margin is, bit for bit, the unconstrained step. */
+enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8, FMJ_CREATE_F64_CONTACTS = 32 };
 typedef struct fmj_create_ext {
   int32_t size;           /* = sizeof(fmj_create_ext); anything else: FMJ_ERR_ARG */
   int32_t flags;          /* FMJ_CREATE_*, or 0 */
