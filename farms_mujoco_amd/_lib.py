@@ -82,6 +82,7 @@ class CCreateExt(ctypes.Structure):      # fmj_create_ext (fmj_create_ex2)
 CREATE_F64_LIMITS = 1      # FMJ_CREATE_F64_LIMITS of include/fmj.h
 CREATE_F64_RK4 = 8         # FMJ_CREATE_F64_RK4 (bits 2 and 4 are not assigned)
 CREATE_F64_CONTACTS = 32   # FMJ_CREATE_F64_CONTACTS (bit 16 is not assigned)
+CREATE_F64_TERRAIN = 128   # FMJ_CREATE_F64_TERRAIN (bit 64 is not assigned)
 PRECISIONS = {'fp32': 0, 'fp64': 1}      # FMJ_PRECISION_* of include/fmj.h
 KERNEL_TWO_WAVE, KERNEL_ONE_ENV_PER_WAVE, KERNEL_NO_LEAN, KERNEL_NO_PRIO = 1, 2, 4, 8      # FMJ_KERNEL_* of include/fmj.h ("Kernel selection" at fmj_create_ex)
 
@@ -182,7 +183,8 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
         f64_jobs = [(os.path.join(objdir, 'kf64.o'), ['-DFMJ_TU_F64']),      # the fp64 step kernel (csrc/fmj_f64.inc)
                     (os.path.join(objdir, 'kf64l.o'), ['-DFMJ_TU_F64=2']),   # its instantiations with joint limits (fmj_create_ex2)
                     (os.path.join(objdir, 'kf64r.o'), ['-DFMJ_TU_F64=3']),   # its RK4 kernels (FMJ_CREATE_F64_RK4; csrc/fmj_f64_step.inc)
-                    (os.path.join(objdir, 'kf64c.o'), ['-DFMJ_TU_F64=4'])]   # its contacts kernels (FMJ_CREATE_F64_CONTACTS; csrc/fmj_f64_contacts.inc)
+                    (os.path.join(objdir, 'kf64c.o'), ['-DFMJ_TU_F64=4']),   # its contacts kernels (FMJ_CREATE_F64_CONTACTS; csrc/fmj_f64_contacts.inc)
+                    (os.path.join(objdir, 'kf64t.o'), ['-DFMJ_TU_F64=5'])]   # its terrain kernels (FMJ_CREATE_F64_TERRAIN; csrc/fmj_f64_terrain.inc)
         if dev:
             todo = [j for j in jobs if not j[1] or int(j[1][0].split('=')[1]) in dev or not os.path.exists(j[0])] + f64_jobs
             jobs += f64_jobs

@@ -50,6 +50,14 @@
 // and the forces in LDS for the dof lanes: F64_CT doubles per contact past the LIMITS block).  J a, J p and J qvel are W_e . the sum
 // of cdof_j x_j over the chain of the contact's body.  A step in which no contact penetrates (and no limit row is a candidate) is the
 // unconstrained step, bit for bit.
+//
+// fmj_step_f64_terrain_kernel<LIMITS> (fmj_create_ex2 with FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_TERRAIN; the step's text with
+// F64_STEP_CONTACTS 1 and F64_STEP_TERRAIN 1, helpers in fmj_f64_terrain.inc) is that kernel with the ground's normal a per-contact
+// quantity: the ground entries are the world's planes and its one heightfield (oracle ground_dist: the plane of the grid triangle under
+// each candidate point; the samples are a double table in global memory), and the animat may carry cylinders (up to four rim points
+// against the plane under the cylinder's centre).  The normal travels in the exchange record (pos, dist, normal, geom and ground entry
+// in one double), the tangents come from it by add_contact's rule per contact (a plane's are its host-computed constants), and the
+// normal stays in LDS (F64_TN doubles per contact past the records) for the record store of the launch's last step.
 
 #define FMJ_F64_LANES 128
 #define F64_BD 28      // doubles per body: pos(3) mass, quat(4), ipos(3) subtree mass, iquat(4), inertia(3) -, axis(3) qpos0, jnt_pos(3) stiffness
@@ -62,6 +70,8 @@
 #define F64_GI 4       // ints per geom: type, body, last dof of the body's chain (-1: none), -
 #define F64_PD 16      // doubles per plane: normal(3), point(3), tangents(6) (oracle add_contact's frame), friction, geom index
 #define F64_CT 33      // doubles of LDS per contact: W of the four rows (24), D of the active rows (4), a row scalar for J' (4), body
+#define F64_TG 24      // doubles per ground entry of a terrain context: frame (9, row-major), point(3), friction, geom index, kind (0 plane, 1 heightfield), then a plane's tangents (6) or a heightfield's ncol, nrow, x / y radius, z scale, cells per metre in x / y
+#define F64_TN 3       // doubles of LDS per contact that the terrain kernels add past the F64_CT records: the contact's normal
 
 struct F64Model {
   int nbody, nv, nq, nu, rs, jump_rounds, anc_stride, root_free, any_stiffness, implicitfast, nsensordata, njs, maxdep, nround;
@@ -104,6 +114,12 @@ struct F64Contacts {
   const double* pd;             // [nplane][F64_PD]
 };
 
+// What only the terrain kernels read (a sixth argument of theirs; they read no F64Contacts.pd)
+struct F64Terrain {
+  const double* tg;             // [F64Contacts.nplane][F64_TG] the ground entries in geom order
+  const double* hf;             // [nrow][ncol] the heightfield's samples (NULL without one)
+};
+
 // LDS map, in doubles (ints at the end)
 struct LdsLayoutD { int QP, QV, XA, XCH, CD, CI, CR, CF, CS, MX, HR, XW, FLG, total_bytes; };
 __host__ __device__ inline LdsLayoutD ldsd_layout(int nb, int nv, int nq, int rs) {
@@ -133,6 +149,10 @@ __host__ __device__ inline int ldsd_total_bytes(int nb, int nv, int nq, int rs, 
 // What the contacts kernels append after the LIMITS block (which they always have): F64_CT doubles per contact
 __host__ __device__ inline int ldsd_contacts_bytes(int nb, int nv, int nq, int rs, int max_contacts) {
   return ldsd_total_bytes(nb, nv, nq, rs, 1) + max_contacts * F64_CT * 8;
+}
+// The terrain kernels: the normals of the contacts (F64_TN doubles each) past the records
+__host__ __device__ inline int ldsd_terrain_bytes(int nb, int nv, int nq, int rs, int max_contacts) {
+  return ldsd_contacts_bytes(nb, nv, nq, rs, max_contacts) + max_contacts * F64_TN * 8;
 }
 // What the RK4 kernels append after that: the first pass's actuator forces [nu] and controls [nu], kept until the step's fourth pass
 // has passed its checks (each slot is written and read back by the one lane that owns the actuator's dof), then F64_RK4_ROWS rows of
@@ -312,10 +332,11 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
   qp[3] = qo.w; qp[4] = qo.x; qp[5] = qo.y; qp[6] = qo.z;
 }
 
-// The step's text (fmj_f64_step.inc), once per integrator family, and once more with ground contacts
+// The step's text (fmj_f64_step.inc), once per integrator family, and once more with ground contacts (on planes, or on terrain)
 #define F64_STEP_KERNEL fmj_step_f64_kernel
 #define F64_STEP_RK4 0
 #define F64_STEP_CONTACTS 0
+#define F64_STEP_TERRAIN 0
 #include "fmj_f64_step.inc"
 #undef F64_STEP_KERNEL
 #undef F64_STEP_RK4
@@ -337,10 +358,29 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
 #undef F64_STEP_RK4
 #undef F64_STEP_CONTACTS
 #endif
+#undef F64_STEP_TERRAIN
+#if FMJ_TU_F64 == 5
+#include "fmj_f64_contacts.inc"
+#include "fmj_f64_terrain.inc"
+#define F64_STEP_KERNEL fmj_step_f64_terrain_kernel
+#define F64_STEP_RK4 0
+#define F64_STEP_CONTACTS 1
+#define F64_STEP_TERRAIN 1
+#include "fmj_f64_step.inc"
+#undef F64_STEP_KERNEL
+#undef F64_STEP_RK4
+#undef F64_STEP_CONTACTS
+#undef F64_STEP_TERRAIN
+#endif
 
 // -DFMJ_TU_F64: the two instantiations without limits; -DFMJ_TU_F64=2: the two LIMITS instantiations, a translation unit of their own;
-// -DFMJ_TU_F64=3: the four RK4 instantiations, one more; -DFMJ_TU_F64=4: the two contacts kernels, one more
-#if FMJ_TU_F64 == 4
+// -DFMJ_TU_F64=3: the four RK4 instantiations, one more; -DFMJ_TU_F64=4: the two contacts kernels, one more; -DFMJ_TU_F64=5: the two
+// terrain kernels, one more
+#if FMJ_TU_F64 == 5
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_terrain(int limits) {
+  return limits ? (void*)fmj_step_f64_terrain_kernel<true> : (void*)fmj_step_f64_terrain_kernel<false>;
+}
+#elif FMJ_TU_F64 == 4
 extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_contacts(int limits) {
   return limits ? (void*)fmj_step_f64_contacts_kernel<true> : (void*)fmj_step_f64_contacts_kernel<false>;
 }

@@ -5,7 +5,14 @@
 // With F64_STEP_CONTACTS 1 it is fmj_step_f64_contacts_kernel<LIMITS> (never fused, never RK4; a fifth argument, F64Contacts; dynamic
 // LDS is ldsd_contacts_bytes): ground contacts as four more unilateral rows each in the Newton solve of the LIMITS build.  Every
 // `CONTACTS` condition is a compile-time constant, and CONS = LIMITS || CONTACTS is LIMITS in the other two texts.
-#if F64_STEP_CONTACTS
+// With F64_STEP_TERRAIN 1 on top of that it is fmj_step_f64_terrain_kernel<LIMITS> (a sixth argument, F64Terrain; dynamic LDS is
+// ldsd_terrain_bytes): the ground entries are planes and the heightfield, the animat may carry cylinders, and a contact has its own normal.
+#if F64_STEP_TERRAIN
+template <bool LIMITS>
+__global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model FM, const StepArgs A, const F64Fused U, const F64Limits LM, const F64Contacts CM,
+                                                                 const F64Terrain TM) {
+  constexpr bool FUSED = false;
+#elif F64_STEP_CONTACTS
 template <bool LIMITS>
 __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model FM, const StepArgs A, const F64Fused U, const F64Limits LM, const F64Contacts CM) {
   constexpr bool FUSED = false;
@@ -30,6 +37,9 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
   double* RKS = ldsd + ldsd_total_bytes(nb, nv, nq, rs, LIMITS) / 8;      // RK4 only: past the map and the LIMITS block (F64_RK4_LDS_DOUBLES)
 #if F64_STEP_CONTACTS
   double* CT = ldsd + ldsd_total_bytes(nb, nv, nq, rs, 1) / 8;            // the contact records (F64_CT doubles each), past the LIMITS block
+#endif
+#if F64_STEP_TERRAIN
+  double* CN = CT + CM.max_contacts * F64_CT;                             // the contacts' normals (F64_TN doubles each), past the records
 #endif
   int sumpar = 0;
 #define WG_SUM4(a_, b_, c_, d_) do { wg_sum4(a_, b_, c_, d_, SUM + sumpar * 8); sumpar ^= 1; } while (0)
@@ -290,17 +300,29 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         XP[lane * 8 + 4] = xq.w; XP[lane * 8 + 5] = xq.x; XP[lane * 8 + 6] = xq.y; XP[lane * 8 + 7] = xq.z;
       }
       __syncthreads();
+#if F64_STEP_TERRAIN
+      const bool animat = g_type == FMJ_GEOM_SPHERE || g_type == FMJ_GEOM_CAPSULE || g_type == FMJ_GEOM_BOX || g_type == FMJ_GEOM_CYLINDER;
+#else
       const bool animat = g_type == FMJ_GEOM_SPHERE || g_type == FMJ_GEOM_CAPSULE || g_type == FMJ_GEOM_BOX;
+#endif
       const d3 gbp = dmk(XP[g_body * 8], XP[g_body * 8 + 1], XP[g_body * 8 + 2]);
       const dq gbq = {XP[g_body * 8 + 4], XP[g_body * 8 + 5], XP[g_body * 8 + 6], XP[g_body * 8 + 7]};
       int ntot = 0;
 #pragma unroll 1
       for (int p = 0; p < CM.nplane; p++) {
+#if F64_STEP_TERRAIN
+        const double* tgp = TM.tg + (size_t)p * F64_TG;
+        const int cnt = animat ? f64_terrain_contacts(gdp, g_type, gbp, gbq, tgp, TM.hf, lane, p, 0, 0, nullptr) : 0;
+        int tot;
+        const int base = ntot + wg_scan_excl(cnt, FLX + 4, tot);
+        if (cnt > 0 && base < CM.max_contacts) f64_terrain_contacts(gdp, g_type, gbp, gbq, tgp, TM.hf, lane, p, base, CM.max_contacts, XL);
+#else
         const double* pdp = CM.pd + (size_t)p * F64_PD;
         const int cnt = animat ? f64_ground_contacts(gdp, g_type, gbp, gbq, pdp, lane, p, 0, 0, nullptr) : 0;
         int tot;
         const int base = ntot + wg_scan_excl(cnt, FLX + 4, tot);
         if (cnt > 0 && base < CM.max_contacts) f64_ground_contacts(gdp, g_type, gbp, gbq, pdp, lane, p, base, CM.max_contacts, XL);
+#endif
         ntot += tot;
         __syncthreads();
       }
@@ -311,14 +333,27 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         const double* rec = XL + lane * 8;
         c_pos = dmk(rec[0], rec[1], rec[2]);
         const double dist = rec[3];
+#if F64_STEP_TERRAIN
+        { const int gp = (int)rec[7]; c_geom = gp >> 7; c_plane = gp & 127; }
+        const double* cg = CM.gd + (size_t)c_geom * F64_GD;
+        const double* cp = TM.tg + (size_t)c_plane * F64_TG;      // (friction and geom index where a plane's F64_PD row has them)
+#else
         c_geom = (int)rec[4]; c_plane = (int)rec[5];
         const double* cg = CM.gd + (size_t)c_geom * F64_GD;
         const double* cp = CM.pd + (size_t)c_plane * F64_PD;
+#endif
         const int cb = CM.gi[c_geom * F64_GI + 1];
         c_ld = CM.gi[c_geom * F64_GI + 2];
         c_dep = FM.di[(size_t)c_ld * F64_DI + 1];
         c_mu = fmax(fmax(cp[12], cg[10]), 1e-5);      // max over the two geoms (mj_contactParam), floor mjMINMU
+#if F64_STEP_TERRAIN
+        const d3 n = dmk(rec[4], rec[5], rec[6]);     // the contact's own normal; the frame by add_contact's rule (a plane's: its constants)
+        d3 t1 = dmk(cp[15], cp[16], cp[17]), t2 = dmk(cp[18], cp[19], cp[20]);
+        if (cp[14] != 0.0) f64_contact_frame(n, t1, t2);
+        CN[lane * F64_TN] = n.x; CN[lane * F64_TN + 1] = n.y; CN[lane * F64_TN + 2] = n.z;      // (read back by this lane alone)
+#else
         const d3 n = dmk(cp[0], cp[1], cp[2]), t1 = dmk(cp[6], cp[7], cp[8]), t2 = dmk(cp[9], cp[10], cp[11]);
+#endif
         const d3 off = dsub(c_pos, com);
         const d6 V = f64_chain_sum(CD, QV, FM.danc, rs, c_ld, c_dep);
         const double diag = cg[11] + c_mu * c_mu * cg[11];
@@ -728,11 +763,22 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
 #if F64_STEP_CONTACTS
     if (last && !frozen) {      // the contact list of the launch's last pass: pos, frame, force in the contact frame (mju_decodePyramid), geom1 << 16 | geom2
       if (is_c) {
+#if F64_STEP_TERRAIN
+        const double* cp = TM.tg + (size_t)c_plane * F64_TG;
+        float* o = A.contact + ((size_t)env * CM.max_contacts + lane) * 16;
+        o[0] = (float)c_pos.x; o[1] = (float)c_pos.y; o[2] = (float)c_pos.z;
+        const d3 n = dmk(CN[lane * F64_TN], CN[lane * F64_TN + 1], CN[lane * F64_TN + 2]);
+        d3 t1 = dmk(cp[15], cp[16], cp[17]), t2 = dmk(cp[18], cp[19], cp[20]);
+        if (cp[14] != 0.0) f64_contact_frame(n, t1, t2);
+        o[3] = (float)n.x; o[4] = (float)n.y; o[5] = (float)n.z;
+        o[6] = (float)t1.x; o[7] = (float)t1.y; o[8] = (float)t1.z; o[9] = (float)t2.x; o[10] = (float)t2.y; o[11] = (float)t2.z;
+#else
         const double* cp = CM.pd + (size_t)c_plane * F64_PD;
         float* o = A.contact + ((size_t)env * CM.max_contacts + lane) * 16;
         o[0] = (float)c_pos.x; o[1] = (float)c_pos.y; o[2] = (float)c_pos.z;
         o[3] = (float)cp[0]; o[4] = (float)cp[1]; o[5] = (float)cp[2];
         for (int k = 0; k < 6; k++) o[6 + k] = (float)cp[6 + k];
+#endif
         o[12] = (float)(c_f0 + c_f1 + c_f2 + c_f3); o[13] = (float)(c_mu * (c_f0 - c_f1)); o[14] = (float)(c_mu * (c_f2 - c_f3));
         o[15] = __int_as_float(((int)cp[13] << 16) | c_geom);
       }

@@ -1527,12 +1527,13 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 // Build layout: this file is compiled once per register row length with -DFMJ_TU_MAXD=<4..64> (only the step-kernel
 // instantiations of that MAXD and a getter for their host stubs), once per row length of the two-wave kernel with
 // -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64, once for its LIMITS instantiations with -DFMJ_TU_F64=2
-// once for its RK4 kernels with -DFMJ_TU_F64=3 and once for its contacts kernels with -DFMJ_TU_F64=4 (kernels and getters: fmj_f64.inc +
-// fmj_f64_step.inc, the last with fmj_f64_contacts.inc), and once without any of them (standalone operators and all host code), in parallel, and the objects are
+// once for its RK4 kernels with -DFMJ_TU_F64=3, once for its contacts kernels with -DFMJ_TU_F64=4 and once for its terrain kernels with
+// -DFMJ_TU_F64=5 (kernels and getters: fmj_f64.inc + fmj_f64_step.inc, the last two with fmj_f64_contacts.inc, the last with
+// fmj_f64_terrain.inc too), and once without any of them (standalone operators and all host code), in parallel, and the objects are
 // linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
 // Every csrc/*.inc is part of this one source (the build and build_id() depend on all of them):
 //   fmj_cons_rows.inc, fmj_newton.inc          constraint rows and solvers of fmj_step_kernel<.., CONS = true>
-//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc (+ fmj_f64_step.inc, fmj_f64_contacts.inc)      the other step kernels
+//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc (+ fmj_f64_step.inc, fmj_f64_contacts.inc, fmj_f64_terrain.inc)      the other step kernels
 //   fmj_stage_{carry_in,step_head,k,c,v,f,q,m,dbg_h,euler_check,euler_commit,euler_root}.inc      stages shared by fmj_step_kernel and fmj_step_wide_kernel
 //   fmj_stage2_{k,c,v,f,s}.inc                 stages shared by fmj_step_dual2_kernel and fmj_step_cons2_kernel
 //   fmj_narrow.inc                             collision helpers (device functions, CONTACT_RECORD), included once ahead of the kernels
@@ -1836,7 +1837,7 @@ void* fmj_tu_kernel_20(int, int); void* fmj_tu_kernel_24(int, int); void* fmj_tu
 void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu_kernel_44(int, int); void* fmj_tu_kernel_48(int, int);
 void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
-void* fmj_tu_f64(int); void* fmj_tu_f64_limits(int); void* fmj_tu_f64_rk4(int, int); void* fmj_tu_f64_contacts(int);
+void* fmj_tu_f64(int); void* fmj_tu_f64_limits(int); void* fmj_tu_f64_rk4(int, int); void* fmj_tu_f64_contacts(int); void* fmj_tu_f64_terrain(int);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -1858,6 +1859,8 @@ struct F64Host {
   int rk4 = 0;                   // fmj_create_ex2 with FMJ_CREATE_F64_RK4 and an RK4 model: fmj_step_f64_rk4_kernel runs every launch
   int contacts = 0;              // fmj_create_ex2 with FMJ_CREATE_F64_CONTACTS and a model with ground contacts: fmj_step_f64_contacts_kernel runs every launch
   F64Contacts con = {};          // its fifth argument
+  int terrain = 0;               // ... also with FMJ_CREATE_F64_TERRAIN: fmj_step_f64_terrain_kernel runs every launch instead
+  F64Terrain ter = {};           // its sixth argument
   size_t lds_bytes = 0;
   std::vector<double> h_ad;      // actuator table mirror (fmj_set_actuator_forcerange)
   std::vector<int> h_asrc;
@@ -1866,6 +1869,7 @@ struct F64Host {
 };
 typedef void (*f64_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits);
 typedef void (*f64_contacts_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits, const F64Contacts);
+typedef void (*f64_terrain_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits, const F64Contacts, const F64Terrain);
 static f64_kernel_t f64_kernel(bool fused, int limits, int rk4) {
   return (f64_kernel_t)(rk4 ? fmj_tu_f64_rk4(fused, limits) : limits ? fmj_tu_f64_limits(fused) : fmj_tu_f64(fused));
 }
@@ -1889,8 +1893,13 @@ static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream, 
     if (c->f64->contacts) {
       if (fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused_f64: an fp64 context with contacts (FMJ_CREATE_F64_CONTACTS) steps through fmj_step: fused contact rows are not built");
       if (!A.qacc_warmstart || !A.contact || !A.ncon) return set_err(FMJ_ERR_ARG, "fmj_data: qacc_warmstart, contact and ncon are required for models with limits / contacts");
-      hipLaunchKernelGGL((f64_contacts_kernel_t)fmj_tu_f64_contacts(c->f64->limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream,
-                         c->f64->fm, A, U, c->f64->lim, c->f64->con);
+      if (c->f64->terrain) {
+        hipLaunchKernelGGL((f64_terrain_kernel_t)fmj_tu_f64_terrain(c->f64->limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream,
+                           c->f64->fm, A, U, c->f64->lim, c->f64->con, c->f64->ter);
+      } else {
+        hipLaunchKernelGGL((f64_contacts_kernel_t)fmj_tu_f64_contacts(c->f64->limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream,
+                           c->f64->fm, A, U, c->f64->lim, c->f64->con);
+      }
       if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string("fp64 contacts step kernel launch: ") + hipGetErrorString(e));
       return FMJ_OK;
     }
@@ -1981,6 +1990,8 @@ struct ModelFacts {
   int f64_rk4 = 0;            // such a context whose model integrates with RK4: fmj_step_f64_rk4_kernel, four passes inside one launch
   bool f64_contacts_ok = false; // set by fmj_create_ex2 (FMJ_CREATE_F64_CONTACTS): an fp64 context takes ground contacts
   int f64_contacts = 0;       // such a context whose model has animat geoms and a plane: fmj_step_f64_contacts_kernel; cons stays 0
+  bool f64_terrain_ok = false;  // set by fmj_create_ex2 (FMJ_CREATE_F64_TERRAIN, with _CONTACTS): the contact solve takes the heightfield and cylinders
+  int f64_terrain = 0;        // such a context with f64_contacts: fmj_step_f64_terrain_kernel in the place of the contacts kernel
   int cons = 0, big = 0;      // limits, contacts or pairs (the constraint kernels); nbody or nv above 64 (past one wavefront)
   int wide = 0;               // every step launch runs the two-wave kernel (fmj_wide.inc): big, or kernel.two_wave
   int nplane = 0, n_hfield = 0, any_mesh = 0, any_box = 0, any_polypair = 0;     // nplane counts the ground geoms: planes and the heightfield
@@ -2057,8 +2068,8 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
       if (m->npair > 0) return no("explicit contact pairs (their rows couple two chains: outside the tree-sparse pattern of M)");
       for (int g = 0; g < m->ngeom; g++) {
         const int t = m->geom_type[g];
-        if (t == FMJ_GEOM_HFIELD) return no("heightfield geoms");
-        if (t == FMJ_GEOM_CYLINDER) return no("cylinder geoms");
+        if (t == FMJ_GEOM_HFIELD && !F->f64_terrain_ok) return no("heightfield geoms");
+        if (t == FMJ_GEOM_CYLINDER && !F->f64_terrain_ok) return no("cylinder geoms");
         if (t == FMJ_GEOM_MESH) return no("mesh geoms");
       }
       if (m->cone != FMJ_CONE_PYRAMIDAL) return no("elliptic cone (pyramidal only)");
@@ -2070,12 +2081,13 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
         return no("primal solve for a ground contact whose friction / sqrt(impratio) can fall below 1e-3 (rows too stiff for it: the fp32 constraint path solves such a model on the dual problem)");
       if (m->solver_iterations < 0 || !(m->solver_tolerance >= 0)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
       for (int g = 0; g < m->ngeom; g++) {
-        if (m->geom_type[g] == FMJ_GEOM_PLANE) continue;
+        if (m->geom_type[g] == FMJ_GEOM_PLANE || m->geom_type[g] == FMJ_GEOM_HFIELD) continue;
         int a = m->geom_bodyid[g];
         while (a >= 1 && m->body_dofnum[a] == 0) a = m->body_parentid[a];
         if (a < 1) return no("rows for a collision geom on a body without dofs");
       }
       F->f64_contacts = 1; cons = 0;
+      F->f64_terrain = F->f64_terrain_ok;
     }
     if (cons) return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex: the fp64 step has no constraint solver: the model has ") +
                              (any_limit ? "joint limits" : m->npair > 0 ? "explicit contact pairs" : "contact geoms"));
@@ -2174,6 +2186,10 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   if (F->f64_contacts) {      // what fmj_constraint_info reports; the LDS of fmj_step_f64_contacts_kernel at this model's sizes
     F->max_contacts = m->max_contacts; F->maxefc = 2 * nj + 4 * m->max_contacts;
     const int bytes = ldsd_contacts_bytes(nb, nv, nq, r4(max_ddepth + 1), m->max_contacts);
+    const int tbytes = ldsd_terrain_bytes(nb, nv, nq, r4(max_ddepth + 1), m->max_contacts);
+    if (F->f64_terrain && tbytes > 160 * 1024)
+      return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex2: the fp64 contact solve on terrain (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_TERRAIN) needs " + std::to_string(tbytes) +
+                                          " bytes of LDS for this model (its bodies, dofs, dof chain and max_contacts), above 160 KB: lower max_contacts");
     if (bytes > 160 * 1024)
       return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex2: the fp64 contact solve (FMJ_CREATE_F64_CONTACTS) needs " + std::to_string(bytes) +
                                           " bytes of LDS for this model (its bodies, dofs, dof chain and max_contacts), above 160 KB: lower max_contacts");
@@ -2700,7 +2716,7 @@ static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
       int a = b;
       while (a >= 1 && m->body_dofnum[a] == 0) a = m->body_parentid[a];
       ti[0] = m->geom_type[g]; ti[1] = b; ti[2] = a >= 1 ? m->body_dofadr[a] + m->body_dofnum[a] - 1 : -1;
-      if (m->geom_type[g] != FMJ_GEOM_PLANE) continue;
+      if (m->geom_type[g] != FMJ_GEOM_PLANE || F.f64_terrain) continue;      // (a terrain context reads its ground entries from F64Terrain.tg)
       // world-attached plane: normal = z axis of the geom frame (mju_quat2Mat of the geom's quaternion), point = geom_pos; the frame of add_contact
       const double* q = m->geom_quat + 4 * g;
       double* pt = &pd[(size_t)ip++ * F64_PD];
@@ -2714,8 +2730,48 @@ static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
       pt[9] = pt[1] * pt[8] - pt[2] * pt[7]; pt[10] = pt[2] * pt[6] - pt[0] * pt[8]; pt[11] = pt[0] * pt[7] - pt[1] * pt[6];
       pt[12] = m->geom_friction[3 * g]; pt[13] = g;
     }
-    if ((rc = upload_f64(c, gd, &C.gd)) || (rc = upload_f64(c, gi, &C.gi)) || (rc = upload_f64(c, pd, &C.pd))) return rc;
+    if ((rc = upload_f64(c, gd, &C.gd)) || (rc = upload_f64(c, gi, &C.gi))) return rc;
+    if (!F.f64_terrain && (rc = upload_f64(c, pd, &C.pd))) return rc;
     H.contacts = 1;
+    if (F.f64_terrain) {      // the ground entries in geom order (oracle ground_dist; add_contact's frame for a plane), the samples in double
+      std::vector<double> tg((size_t)F.nplane * F64_TG, 0.0);
+      int it = 0;
+      for (int g = 0; g < m->ngeom; g++) {
+        const int t = m->geom_type[g];
+        if (t != FMJ_GEOM_PLANE && t != FMJ_GEOM_HFIELD) continue;
+        double* e = &tg[(size_t)it++ * F64_TG];
+        const double* q = m->geom_quat + 4 * g;      // world-attached: the geom's own frame (mju_quat2Mat)
+        const double q00 = q[0] * q[0], q11 = q[1] * q[1], q22 = q[2] * q[2], q33 = q[3] * q[3];
+        e[0] = q00 + q11 - q22 - q33; e[4] = q00 - q11 + q22 - q33; e[8] = q00 - q11 - q22 + q33;
+        e[1] = 2.0 * (q[1] * q[2] - q[0] * q[3]); e[2] = 2.0 * (q[1] * q[3] + q[0] * q[2]);
+        e[3] = 2.0 * (q[1] * q[2] + q[0] * q[3]); e[5] = 2.0 * (q[2] * q[3] - q[0] * q[1]);
+        e[6] = 2.0 * (q[1] * q[3] - q[0] * q[2]); e[7] = 2.0 * (q[2] * q[3] + q[0] * q[1]);
+        for (int k = 0; k < 3; k++) e[9 + k] = m->geom_pos[3 * g + k];
+        e[12] = m->geom_friction[3 * g]; e[13] = g;
+        if (t == FMJ_GEOM_PLANE) {
+          const double n[3] = {e[2], e[5], e[8]};
+          double t1[3] = {0, 0, 0};
+          if (n[1] < -0.5 || n[1] > 0.5) t1[2] = 1; else t1[1] = 1;
+          const double dt = t1[0] * n[0] + t1[1] * n[1] + t1[2] * n[2];
+          for (int k = 0; k < 3; k++) t1[k] -= dt * n[k];
+          const double nn = sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
+          for (int k = 0; k < 3; k++) e[15 + k] = t1[k] / nn;
+          e[18] = n[1] * e[17] - n[2] * e[16]; e[19] = n[2] * e[15] - n[0] * e[17]; e[20] = n[0] * e[16] - n[1] * e[15];
+        } else {
+          const int nc = m->hfield_ncol, nr = m->hfield_nrow;
+          e[14] = 1.0; e[15] = nc; e[16] = nr; e[17] = m->hfield_size[0]; e[18] = m->hfield_size[1]; e[19] = m->hfield_size[2];
+          e[20] = (nc - 1) / (2 * m->hfield_size[0]); e[21] = (nr - 1) / (2 * m->hfield_size[1]);
+          if ((rc = upload_f64(c, std::vector<double>(m->hfield_data, m->hfield_data + (size_t)nr * nc), &H.ter.hf))) return rc;
+        }
+      }
+      if ((rc = upload_f64(c, tg, &H.ter.tg))) return rc;
+      H.terrain = 1;
+      H.lds_bytes = (size_t)ldsd_terrain_bytes(nb, nv, m->nq, M.rs, m->max_contacts);      // (check_model held it to 160 KB)
+      if (hipFuncSetAttribute((const void*)fmj_tu_f64_terrain(H.limits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
+        return set_err(FMJ_ERR_HIP, "fmj_create_ex2: LDS request of the fp64 terrain step kernel too large");
+      c->path = PATH_F64;
+      return sync_f64_maps(c);
+    }
     H.lds_bytes = (size_t)ldsd_contacts_bytes(nb, nv, m->nq, M.rs, m->max_contacts);      // (check_model held it to 160 KB)
     if (hipFuncSetAttribute((const void*)fmj_tu_f64_contacts(H.limits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
       return set_err(FMJ_ERR_HIP, "fmj_create_ex2: LDS request of the fp64 contacts step kernel too large");
@@ -2755,13 +2811,15 @@ int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj
   if (!m || !out || n_envs <= 0) return set_err(FMJ_ERR_ARG, "fmj_create: NULL model/out or n_envs <= 0");
   *out = nullptr;
   if (ext && ext->size != (int32_t)sizeof(fmj_create_ext)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: fmj_create_ext.size is not sizeof(fmj_create_ext)");
-  if (ext && (ext->flags & ~(int32_t)(FMJ_CREATE_F64_LIMITS | FMJ_CREATE_F64_RK4 | FMJ_CREATE_F64_CONTACTS))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: unknown bits in fmj_create_ext.flags");
+  if (ext && (ext->flags & ~(int32_t)(FMJ_CREATE_F64_LIMITS | FMJ_CREATE_F64_RK4 | FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_TERRAIN))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: unknown bits in fmj_create_ext.flags");
   if (ext && (ext->flags & FMJ_CREATE_F64_LIMITS) && !(opts && opts->precision == FMJ_PRECISION_F64))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_LIMITS needs precision = FMJ_PRECISION_F64 (the limits solve belongs to the fp64 step kernel)");
   if (ext && (ext->flags & FMJ_CREATE_F64_RK4) && !(opts && opts->precision == FMJ_PRECISION_F64))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_RK4 needs precision = FMJ_PRECISION_F64 (the in-kernel RK4 belongs to the fp64 step kernel)");
   if (ext && (ext->flags & FMJ_CREATE_F64_CONTACTS) && !(opts && opts->precision == FMJ_PRECISION_F64))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_CONTACTS needs precision = FMJ_PRECISION_F64 (the contact solve belongs to the fp64 step kernel)");
+  if (ext && (ext->flags & FMJ_CREATE_F64_TERRAIN) && !((ext->flags & FMJ_CREATE_F64_CONTACTS) && opts && opts->precision == FMJ_PRECISION_F64))
+    return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_TERRAIN needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it widens the fp64 contact solve's narrow phase)");
   if (opts && opts->size != 8 && opts->size != (int32_t)sizeof(fmj_create_options))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex: fmj_create_options.size is neither sizeof(fmj_create_options) nor 8 (the struct before the kernel fields)");
   const int precision = opts ? opts->precision : FMJ_PRECISION_F32;
@@ -2770,6 +2828,7 @@ int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj
   F.f64_limits_ok = ext && (ext->flags & FMJ_CREATE_F64_LIMITS);
   F.f64_rk4_ok = ext && (ext->flags & FMJ_CREATE_F64_RK4);
   F.f64_contacts_ok = ext && (ext->flags & FMJ_CREATE_F64_CONTACTS);
+  F.f64_terrain_ok = ext && (ext->flags & FMJ_CREATE_F64_TERRAIN);
   if (int rc = resolve_kernel_choice(opts, &F.kernel)) return rc;
   if (int rc = check_model(m, &F, precision)) return rc;
   int ndev = 0;

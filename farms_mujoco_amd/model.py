@@ -819,20 +819,47 @@ def centipede_touch_height(foot_radius: float = 0.0015) -> float:
     return 0.015*np.sin(CENTIPEDE_LEG_PITCH) + foot_radius
 
 
+CENTIPEDE_HFIELD = dict(n=33, radius=2.0, amplitude=0.002)      # centipede(terrain='hfield'): samples per side, half side (m), +- elevation (m)
+
+
+def hfield_height(data, size, x, y):
+    """Elevation of a heightfield (``data`` [nrow, ncol], ``size`` as ModelBuilder.add_hfield) under the point (x, y) of its frame:
+    the plane of the grid triangle under the point, cells split along the diagonal (c, r) - (c + 1, r + 1)."""
+    nr, nc = data.shape
+    gx, gy = (x + size[0])*(nc - 1)/(2*size[0]), (y + size[1])*(nr - 1)/(2*size[1])
+    assert 0 <= gx <= nc - 1 and 0 <= gy <= nr - 1, 'outside the grid'
+    c, r = min(int(gx), nc - 2), min(int(gy), nr - 2)
+    fx, fy = gx - c, gy - r
+    z00, z10, z01, z11 = (data[r, c]*size[2], data[r, c + 1]*size[2], data[r + 1, c]*size[2], data[r + 1, c + 1]*size[2])
+    gxs, gys = (z10 - z00, z11 - z10) if fx >= fy else (z11 - z01, z01 - z00)
+    return z00 + gxs*fx + gys*fy
+
+
 def centipede(n_segments: int = 10, n_spine_joints: int = 15, timestep: float = 1e-3, full_actuators: bool = False,
-              contacts: bool = False) -> Model:
+              contacts: bool = False, terrain: str = 'plane') -> Model:
     """Config-5 centipede: free + 15 spine hinges + 2x2-DoF legs on 10 segments (nv = 61).  ``full_actuators``: the position /
     velocity / motor triple of mjcf.py:819-854 on every joint (salamander33's layout) instead of the position actuator alone.
     ``contacts``: the walking model - a capsule on each spine segment and a sphere at each leg tip (friction 1.0), the friction-0
     world plane z = 0 (mjcf.py:1202), the lower legs pointing ``CENTIPEDE_LEG_PITCH`` below the horizontal at qpos0, leg joints damped at 4e-4, spawned with the
     feet 0.2 mm into the ground, and ``max_contacts`` for every possible contact (two per capsule, one per foot; at most 128).
-    centipede(20, 25, contacts=True) steps only in an fp64 context made with ``fp64_contacts=True`` (107 bodies)."""
+    centipede(20, 25, contacts=True) steps only in an fp64 context made with ``fp64_contacts=True`` (107 bodies).
+    ``terrain='hfield'`` (with ``contacts``) replaces the plane by a rolling heightfield scaled to the animal, whose legs are 15 mm
+    long: +-2 mm over a 4 m x 4 m patch of 33 x 33 samples (``CENTIPEDE_HFIELD``), spawned with the foot that stands on the highest
+    ground 0.2 mm into it; such a model needs ``fp64_terrain=True`` as well."""
+    assert terrain in ('plane', 'hfield'), terrain
     b = ModelBuilder('centipede', timestep=timestep)
     L, r = 0.03, 0.006
     n = n_spine_joints + 1
     mass = 1000.0*(np.pi*r*r*L + 4.0/3.0*np.pi*r**3)
     foot_r = 0.0015
     spawn_z = centipede_touch_height(foot_r) - 2e-4 if contacts else -0.1
+    hfield = None
+    if contacts and terrain == 'hfield':
+        H = CENTIPEDE_HFIELD
+        gy, gx = np.meshgrid(np.linspace(-H['radius'], H['radius'], H['n']), np.linspace(-H['radius'], H['radius'], H['n']), indexing='ij')
+        hfield = (0.5*np.sin(7.0*gx)*np.cos(5.0*gy), (H['radius'], H['radius'], 2*H['amplitude'], 0.1))
+        reach = r + 0.004 + 0.015*np.cos(CENTIPEDE_LEG_PITCH)      # a foot's distance from the spine's axis at qpos0
+        spawn_z += max(hfield_height(hfield[0], hfield[1], i*L + L/2, side*reach) for i in range(n_segments) for side in (1, -1))
     leg_damping = 4e-4 if contacts else 5e-5      # standing on its 2 n_segments legs the body is a mass on their springs: near critical damping
     for i in range(n):
         kw = dict(pos=(0, 0, spawn_z) if i == 0 else (L, 0, 0), mass=mass, ipos=(L/2, 0, 0),
@@ -862,7 +889,10 @@ def centipede(n_segments: int = 10, n_spine_joints: int = 15, timestep: float = 
                 b.set_swimming(up, drag_coefficients=[[-1e-4]*3, [-1e-7]*3], height=0.001)
                 b.set_swimming(lo, drag_coefficients=[[-0.02, -0.0002, -0.02], [-1e-7]*3], height=0.004)
     if contacts:
-        b.add_geom('world', GEOM_PLANE, (0, 0, 0), friction=(0, 0, 0))     # arena friction 0 (mjcf.py:1202)
+        if hfield is not None:
+            b.add_hfield(hfield[0], hfield[1], friction=(0, 0, 0))
+        else:
+            b.add_geom('world', GEOM_PLANE, (0, 0, 0), friction=(0, 0, 0))     # arena friction 0 (mjcf.py:1202)
         b.options['max_contacts'] = 2*n + 2*n_segments
         assert b.options['max_contacts'] <= 128, 'one lane per contact in the fp64 contact solve'
     for jn in [x for x in [bd.joint['name'] for bd in b.bodies[1:] if bd.joint] if not x.startswith('root_')]:

@@ -41,7 +41,7 @@ class BatchedPhysics:
     """Device-resident mjData for ``n_envs`` copies of one model + the HIP step context."""
 
     def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None, fp64_fused: bool = False,
-                 fp64_limits: bool = False, fp64_rk4: bool = False, fp64_contacts: bool = False):
+                 fp64_limits: bool = False, fp64_rk4: bool = False, fp64_contacts: bool = False, fp64_terrain: bool = False):
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
         # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
         # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
@@ -68,6 +68,12 @@ class BatchedPhysics:
             raise ValueError('fp64_contacts=True does not go with fp64_fused=True: fused contact rows are not built for the fp64 step')
         if fp64_contacts and fp64_rk4:
             raise ValueError('fp64_contacts=True does not go with fp64_rk4=True: the fp64 contact solve integrates with Euler or implicitfast')
+        # fp64_terrain: the contacts context also takes the world's heightfield as ground and cylinder geoms on the animat (fmj_create_ex2,
+        # FMJ_CREATE_F64_TERRAIN; include/fmj.h) - its own kernels, whose narrow phase carries a normal per contact: opt-in, also on flat ground.
+        if fp64_terrain and not (precision == 'fp64' and fp64_contacts):
+            raise ValueError(f"fp64_terrain=True needs precision='fp64' and fp64_contacts=True (not precision={precision!r}, fp64_contacts={bool(fp64_contacts)}): "
+                             'it widens the narrow phase of the fp64 contact solve')
+        self.fp64_terrain = bool(fp64_terrain)
         self.fp64_contacts = bool(fp64_contacts)
         self.fp64_fused = bool(fp64_fused)
         self.fp64_limits = bool(fp64_limits)
@@ -98,7 +104,7 @@ class BatchedPhysics:
                 if not _lib.has('fmj_create_ex2'):      # an A/B base build (FMJ_SO)
                     raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex2: fp64_limits=True / fp64_rk4=True / fp64_contacts=True need a current build')
                 ext = _lib.CCreateExt(ctypes.sizeof(_lib.CCreateExt), bool(fp64_limits) * _lib.CREATE_F64_LIMITS | bool(fp64_rk4) * _lib.CREATE_F64_RK4 |
-                                      bool(fp64_contacts) * _lib.CREATE_F64_CONTACTS)
+                                      bool(fp64_contacts) * _lib.CREATE_F64_CONTACTS | bool(fp64_terrain) * _lib.CREATE_F64_TERRAIN)
                 rc = self._lib.fmj_create_ex2(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
                                               ctypes.byref(opts), ctypes.byref(ext), ctypes.byref(ctx))
             else:
@@ -280,6 +286,12 @@ class BatchedPhysics:
     def kernel_info(self):
         lds, thr = _lib.ints(self._lib.fmj_kernel_info, self._ctx)
         info = dict(lds_bytes_per_env=lds, threads_per_env=thr)
+        if self.precision == 'fp64':
+            # which text of csrc/fmj_f64_step.inc every launch of the context runs: an fp64 context reports contacts (fmj_constraint_info's
+            # max_contacts) only where its model has ground contacts and the contact solve was asked for
+            contacts = self.fp64_contacts and _lib.ints(self._lib.fmj_constraint_info, self._ctx)[1] > 0
+            info['fp64_step_kernel'] = ('fmj_step_f64_terrain_kernel' if contacts and self.fp64_terrain else 'fmj_step_f64_contacts_kernel' if contacts else
+                                        'fmj_step_f64_rk4_kernel' if self.fp64_rk4 and self.rk4 else 'fmj_step_f64_kernel')
         if _lib.has('fmj_dual_build_info'):     # absent only from an A/B base build (FMJ_SO)
             # the two-env step kernel's build (include/fmj.h: fmj_dual_build_info): register tier, whether fused launches of the
             # flagship shape run the lean build, what the last step launch ran, and whether fused launches alternate the issue

@@ -108,7 +108,9 @@ class Simulation:
     (with 'fp64': the context takes joint limits, solved by the fp64 kernel's primal Newton solve; fmj_create_ex2), ``fp64_rk4`` (with 'fp64': the
     context takes an RK4 model and runs the four passes of a step inside the fp64 kernel; the run fuses when ``fp64_fused`` is set too),
     ``fp64_contacts`` (with 'fp64': the context takes ground contacts, more rows of the same Newton solve; not with ``fp64_fused`` or ``fp64_rk4``: ``run()``
-    takes the per-iteration path), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
+    takes the per-iteration path), ``fp64_terrain`` (with 'fp64' and ``fp64_contacts``: the contact solve also takes the heightfield as ground and
+    cylinder geoms, on kernels of its own; a shard of a :class:`~farms_mujoco_amd.sharding.ShardedSimulation` gets it like the other kernel
+    arguments, from its factory), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
     kernels this simulation's context runs).  ``legacy_step`` is accepted for signature
     compatibility; the step is always the full mj_step (legacy_step=False semantics, simulation.py:36-37).
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here
@@ -132,7 +134,8 @@ class Simulation:
         device = kwargs.pop('device', 'cuda:0')
         self.physics = BatchedPhysics(mjcf_model, n_envs, device, precision=kwargs.pop('precision', 'fp32'), kernel=kwargs.pop('kernel', None),
                                       fp64_fused=kwargs.pop('fp64_fused', False), fp64_limits=kwargs.pop('fp64_limits', False),
-                                      fp64_rk4=kwargs.pop('fp64_rk4', False), fp64_contacts=kwargs.pop('fp64_contacts', False))
+                                      fp64_rk4=kwargs.pop('fp64_rk4', False), fp64_contacts=kwargs.pop('fp64_contacts', False),
+                                      fp64_terrain=kwargs.pop('fp64_terrain', False))
         self.handle_exceptions = kwargs.pop('handle_exceptions', False)
         # dm_control raises PhysicsError inside the offending step; here the device freezes the offending env at that
         # step (include/fmj.h) and the host looks at the status words every `check_every` steps (one sync each)

@@ -375,8 +375,18 @@ int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
  * leaves fmj_data.contact and ncon as the fp32 constraint path does (contacts ordered by ground geom, animat geom, slot within the
  * geom; FMJ_WARN_CONTACTFULL when the list is truncated at max_contacts, which does not freeze), qacc, qacc_warmstart and jointlimitfrc
  * as a limits context; fmj_contacts2data and fmj_before_step work unchanged from those fields.  A step in which no contact penetrates
- * and no limit is within its margin is, bit for bit, the unconstrained step. */
-enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8, FMJ_CREATE_F64_CONTACTS = 32 };
+ * and no limit is within its margin is, bit for bit, the unconstrained step.
+ * FMJ_CREATE_F64_TERRAIN (without FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64: FMJ_ERR_ARG, before the device lookup;
+ * bit 64 is not assigned either): a contacts context that also accepts FMJ_GEOM_CYLINDER on the animat and the model's one
+ * world-attached FMJ_GEOM_HFIELD as a ground geom, beside any planes and in geom order.  The heightfield is met as the plane of the grid
+ * triangle under each candidate point (a sphere's centre, a capsule's end centres, a box's corners; a cylinder meets the plane under
+ * its centre with up to four rim points), so the ground's normal and the contact frame are per-contact quantities; the samples are
+ * uploaded once as a double table.  Everything else the contacts context refuses stays refused with the same words, and so do a
+ * heightfield with fewer than 2 x 2 samples or no table and one on a body other than the world (fmj_create's words); the LDS limit
+ * names this context's bytes (24 more per contact: nbody = nv = 128 with a dof chain of 64 fits up to 120 contacts).  The context runs
+ * its own kernels (fmj_step_f64_terrain_kernel) on any model it accepts, flat ground included - opt-in because the general narrow
+ * phase is not free to a flat-ground user; what it covers and leaves in fmj_data is what a contacts context does. */
+enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8, FMJ_CREATE_F64_CONTACTS = 32, FMJ_CREATE_F64_TERRAIN = 128 };
 typedef struct fmj_create_ext {
   int32_t size;           /* = sizeof(fmj_create_ext); anything else: FMJ_ERR_ARG */
   int32_t flags;          /* FMJ_CREATE_*, or 0 */

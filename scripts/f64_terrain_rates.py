@@ -1,0 +1,77 @@
+"""Rate (env-steps/s) of the fp64 contact solve on terrain (fp64_contacts=True, fp64_terrain=True: fmj_step_f64_terrain_kernel of
+csrc/fmj_f64_step.inc) on 4096 envs, fmj_step in launches of 100 steps under a ctrl tape.  The walking centipede(20, 25) (a travelling
+wave on the spine, the legs held down: the tape of scripts/f64_contacts_rates.py):
+  on its plane through the contacts kernel (fp64_contacts=True alone);
+  on the same plane through the terrain kernel - what the general narrow phase costs a flat-ground user who sets the flag;
+  on the heightfield (terrain='hfield') through the terrain kernel.
+usage: python scripts/f64_terrain_rates.py [n_envs] [samples] [repeats]
+
+The three runs are sampled in turn, ``samples`` times (default 5) after two warm-up passes each (the animal settles on the ground);
+the whole measurement is repeated ``repeats`` times (default 3) on fresh contexts.  Printed per repeat: the median rate of each run,
+its spread (min .. max over the samples), the mean contacts per env at the end and each run's ratio to the first; then the spread of
+the medians over the repeats."""
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from f64_contacts_rates import context, tape_of      # noqa: E402
+
+
+def centipede_runs(n, chunk):
+    import farms_mujoco_amd.model as mm
+
+    def walker(terrain):
+        w = mm.centipede(20, 25, contacts=True, terrain=terrain)
+        w.solver = mm.SOLVERS['newton']; w.solver_iterations = 100
+        return w
+    w = walker('plane')
+    amp, lag = mm.wave_controller_params(w, amplitude=0.1)
+    stance = np.zeros(w.nu)
+    for a in range(w.nu):
+        name = w.joint_names[int(w.actuator_jntid[a])]
+        if name.startswith('joint_leg_') and name.endswith('_1'):
+            stance[a] = -0.25 if '_L_' in name else 0.25
+    runs = {}
+    for key, terrain, flag in (('plane, contacts kernel', 'plane', False), ('plane, terrain kernel', 'plane', True),
+                               ('heightfield, terrain kernel', 'hfield', True)):
+        p, psi = context(walker(terrain), n, precision='fp64', fp64_contacts=True, fp64_terrain=flag)
+        assert p.kernel_info()['fp64_step_kernel'] == ('fmj_step_f64_terrain_kernel' if flag else 'fmj_step_f64_contacts_kernel')
+        runs[key] = (p, tape_of(w, psi, amp, lag, chunk, stance))
+    return w, runs
+
+
+def rates(name, n, samples, chunk=100):
+    import torch
+    m, runs = centipede_runs(n, chunk)
+    out = {k: [] for k in runs}
+    for s in range(samples + 2):      # alternating samples; the first two passes warm up
+        for k, (phys, tape) in runs.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            phys.step(chunk, tape)
+            torch.cuda.synchronize(); dt = time.perf_counter() - t0
+            if s > 1:
+                out[k].append(n*chunk/dt)
+    for phys, _ in runs.values():
+        assert int((phys.data.status & 7).abs().sum()) == 0      # (a full contact list is reported, not an error)
+    med = {k: float(np.median(v)) for k, v in out.items()}
+    ncon = {k: float(p.data.ncon.float().mean()) for k, (p, _) in runs.items()}
+    first = list(runs)[0]
+    print(f'{name} nbody {m.nbody} nv {m.nv} envs {n}: ' +
+          '; '.join(f'{k} {med[k]/1e6:.4f} M env-steps/s ({min(v)/1e6:.4f} .. {max(v)/1e6:.4f}), {ncon[k]:.1f} contacts per env, '
+                    f'{med[k]/med[first]:.3f} of the first' for k, v in out.items()), flush=True)
+    return med
+
+
+if __name__ == '__main__':
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+    samples = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 3
+    meds = [rates('centipede(20, 25) walking', n, samples) for _ in range(repeats)]
+    print(f'centipede(20, 25) walking: medians over {repeats} runs: ' +
+          '; '.join(f'{k} {min(m[k] for m in meds)/1e6:.4f} .. {max(m[k] for m in meds)/1e6:.4f}' for k in meds[0]), flush=True)
