@@ -375,13 +375,14 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
 
 // -DFMJ_TU_F64: the two instantiations without limits; -DFMJ_TU_F64=2: the two LIMITS instantiations, a translation unit of their own;
 // -DFMJ_TU_F64=3: the four RK4 instantiations, one more; -DFMJ_TU_F64=4: the two contacts kernels, one more; -DFMJ_TU_F64=5: the two
-// terrain kernels, one more
+// terrain kernels, one more.  Every getter takes (fused, limits); a unit without fused builds, or with one setting of LIMITS, does not read that argument.
+// (a getter names only its own unit's instantiations: naming another would instantiate it here)
 #if FMJ_TU_F64 == 5
-extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_terrain(int limits) {
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_terrain(int /*fused: no fused builds*/, int limits) {
   return limits ? (void*)fmj_step_f64_terrain_kernel<true> : (void*)fmj_step_f64_terrain_kernel<false>;
 }
 #elif FMJ_TU_F64 == 4
-extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_contacts(int limits) {
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_contacts(int /*fused: no fused builds*/, int limits) {
   return limits ? (void*)fmj_step_f64_contacts_kernel<true> : (void*)fmj_step_f64_contacts_kernel<false>;
 }
 #elif FMJ_TU_F64 == 3
@@ -390,11 +391,11 @@ extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_rk4(int fused,
   return fused ? (void*)fmj_step_f64_rk4_kernel<true, false> : (void*)fmj_step_f64_rk4_kernel<false, false>;
 }
 #elif FMJ_TU_F64 == 2
-extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_limits(int fused) {
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_limits(int fused, int /*limits: always*/) {
   return fused ? (void*)fmj_step_f64_kernel<true, true> : (void*)fmj_step_f64_kernel<false, true>;
 }
 #else
-extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64(int fused) {
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64(int fused, int /*limits: never*/) {
   return fused ? (void*)fmj_step_f64_kernel<true, false> : (void*)fmj_step_f64_kernel<false, false>;
 }
 #endif

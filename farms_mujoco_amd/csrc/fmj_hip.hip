@@ -1837,7 +1837,7 @@ void* fmj_tu_kernel_20(int, int); void* fmj_tu_kernel_24(int, int); void* fmj_tu
 void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu_kernel_44(int, int); void* fmj_tu_kernel_48(int, int);
 void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
-void* fmj_tu_f64(int); void* fmj_tu_f64_limits(int); void* fmj_tu_f64_rk4(int, int); void* fmj_tu_f64_contacts(int); void* fmj_tu_f64_terrain(int);
+void* fmj_tu_f64(int, int); void* fmj_tu_f64_limits(int, int); void* fmj_tu_f64_rk4(int, int); void* fmj_tu_f64_contacts(int, int); void* fmj_tu_f64_terrain(int, int);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -1851,28 +1851,49 @@ static int launch(const char* what, step_kernel_t k, int blocks, int threads, si
   return FMJ_OK;
 }
 
-// the fp64 model of an fp64 context: the kernel's argument and host mirrors of the tables that change after fmj_create
+// ---- the fp64 kernel families (fmj_f64.inc): what the host knows of one, from the create flags to the launch.  A new family is a row.
+enum F64FamilyId { F64_PLAIN, F64_LIMITS, F64_RK4, F64_CONTACTS, F64_TERRAIN };
+static const struct F64Family {
+  void* (*tu)(int fused, int limits);   // its translation unit's getter
+  bool fused;                           // fused builds exist (fmj_step_fused_f64)
+  bool contacts;                        // it takes F64Contacts and F64Terrain past the four common arguments and needs fmj_data's contact buffers
+  const char* solve;                    // in the 160 KB refusal: the solve and its create flags (NULL: the size limits keep the map below it)
+  const char* lds_refused;              // when the runtime refuses the LDS request
+} f64_families[] = {
+  {fmj_tu_f64, true, false, nullptr, "fmj_create_ex: LDS request of the fp64 step kernel too large"},
+  {fmj_tu_f64_limits, true, false, nullptr, "fmj_create_ex: LDS request of the fp64 step kernel too large"},
+  {fmj_tu_f64_rk4, true, false, nullptr, "fmj_create_ex: LDS request of the fp64 step kernel too large"},
+  {fmj_tu_f64_contacts, false, true, "the fp64 contact solve (FMJ_CREATE_F64_CONTACTS)",
+   "fmj_create_ex2: LDS request of the fp64 contacts step kernel too large"},
+  {fmj_tu_f64_terrain, false, true, "the fp64 contact solve on terrain (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_TERRAIN)",
+   "fmj_create_ex2: LDS request of the fp64 terrain step kernel too large"},
+};
+// which kernels an fp64 context runs, decided once (check_model): every launch runs f64_families[family].tu(fused, limits)
+struct F64Kind {
+  int family = -1;                      // an F64FamilyId; -1: not an fp64 context
+  int limits = 0;                       // the model has limited joints and FMJ_CREATE_F64_LIMITS was given: the LIMITS builds
+  int lds_bytes = 0;                    // the kernels' dynamic LDS at the model's sizes
+  bool solves() const { return limits || (family >= 0 && f64_families[family].contacts); }      // the kernel's Newton solve runs: limit or contact rows
+};
+static int f64_lds_bytes(int family, int limits, int nb, int nv, int nq, int rs, int max_contacts, int nu) {
+  if (family == F64_TERRAIN) return ldsd_terrain_bytes(nb, nv, nq, rs, max_contacts);
+  if (family == F64_CONTACTS) return ldsd_contacts_bytes(nb, nv, nq, rs, max_contacts);
+  return ldsd_total_bytes(nb, nv, nq, rs, limits) + (family == F64_RK4 ? F64_RK4_LDS_DOUBLES(nu) * 8 : 0);
+}
+static const char F64_NO_FUSED[] = "fmj_step_fused_f64: an fp64 context with contacts (FMJ_CREATE_F64_CONTACTS) steps through fmj_step: fused contact rows are not built";
+
+// the fp64 model of an fp64 context: the kernel's arguments and host mirrors of the tables that change after fmj_create
 struct F64Host {
+  F64Kind kind;
   F64Model fm = {};
-  F64Limits lim = {};            // limits contexts (fmj_create_ex2, FMJ_CREATE_F64_LIMITS): the fourth kernel argument
-  int limits = 0;                // the LIMITS instantiations run every launch of the context
-  int rk4 = 0;                   // fmj_create_ex2 with FMJ_CREATE_F64_RK4 and an RK4 model: fmj_step_f64_rk4_kernel runs every launch
-  int contacts = 0;              // fmj_create_ex2 with FMJ_CREATE_F64_CONTACTS and a model with ground contacts: fmj_step_f64_contacts_kernel runs every launch
-  F64Contacts con = {};          // its fifth argument
-  int terrain = 0;               // ... also with FMJ_CREATE_F64_TERRAIN: fmj_step_f64_terrain_kernel runs every launch instead
-  F64Terrain ter = {};           // its sixth argument
-  size_t lds_bytes = 0;
+  F64Limits lim = {};            // the Newton solve's settings; lm: the limit rows of a context with kind.limits
+  F64Contacts con = {};          // families with contacts
+  F64Terrain ter = {};           // the terrain family
   std::vector<double> h_ad;      // actuator table mirror (fmj_set_actuator_forcerange)
   std::vector<int> h_asrc;
   std::vector<int> h_bi, h_di;   // body / dof table mirrors: the rows and swimming slots of the fused loop (fmj_set_readout_maps, fmj_set_swimming)
   const double* d_sw = nullptr;  // [nbody][F64_SW] the swimming slots in double: allocated once (a body has at most one slot), filled by fmj_set_swimming
 };
-typedef void (*f64_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits);
-typedef void (*f64_contacts_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits, const F64Contacts);
-typedef void (*f64_terrain_kernel_t)(const F64Model, const StepArgs, const F64Fused, const F64Limits, const F64Contacts, const F64Terrain);
-static f64_kernel_t f64_kernel(bool fused, int limits, int rk4) {
-  return (f64_kernel_t)(rk4 ? fmj_tu_f64_rk4(fused, limits) : limits ? fmj_tu_f64_limits(fused) : fmj_tu_f64(fused));
-}
 
 // the rows and swimming slots of fmj_ctx's tables (h_b_info2, h_d_info) into the fp64 body / dof tables
 static int sync_f64_maps(fmj_ctx* c) {
@@ -1888,23 +1909,16 @@ static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream, 
   const DevModel& D = c->dm;
   const int pairs = (c->n_envs + 1) / 2;
   if (c->path == PATH_F64) {
+    F64Host& H = *c->f64;
+    const F64Family& fam = f64_families[H.kind.family];
     if (fused && !f64_fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused: an fp64 context steps through fmj_step; write the rows with fmj_before_step");
-    const F64Fused U = f64_fused ? *f64_fused : F64Fused{};      // (the plain step reads none of it)
-    if (c->f64->contacts) {
-      if (fused) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused_f64: an fp64 context with contacts (FMJ_CREATE_F64_CONTACTS) steps through fmj_step: fused contact rows are not built");
-      if (!A.qacc_warmstart || !A.contact || !A.ncon) return set_err(FMJ_ERR_ARG, "fmj_data: qacc_warmstart, contact and ncon are required for models with limits / contacts");
-      if (c->f64->terrain) {
-        hipLaunchKernelGGL((f64_terrain_kernel_t)fmj_tu_f64_terrain(c->f64->limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream,
-                           c->f64->fm, A, U, c->f64->lim, c->f64->con, c->f64->ter);
-      } else {
-        hipLaunchKernelGGL((f64_contacts_kernel_t)fmj_tu_f64_contacts(c->f64->limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream,
-                           c->f64->fm, A, U, c->f64->lim, c->f64->con);
-      }
-      if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string("fp64 contacts step kernel launch: ") + hipGetErrorString(e));
-      return FMJ_OK;
-    }
-    hipLaunchKernelGGL(f64_kernel(fused, c->f64->limits, c->f64->rk4), dim3(c->n_envs), dim3(FMJ_F64_LANES), c->f64->lds_bytes, (hipStream_t)stream, c->f64->fm, A, U, c->f64->lim);
-    if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string("fp64 step kernel launch: ") + hipGetErrorString(e));
+    if (fused && !fam.fused) return set_err(FMJ_ERR_UNSUPPORTED, F64_NO_FUSED);
+    if (fam.contacts && (!A.qacc_warmstart || !A.contact || !A.ncon))
+      return set_err(FMJ_ERR_ARG, "fmj_data: qacc_warmstart, contact and ncon are required for models with limits / contacts");
+    F64Fused U = f64_fused ? *f64_fused : F64Fused{};      // (the plain step reads none of it)
+    void* args[6] = {&H.fm, (void*)&A, &U, &H.lim, &H.con, &H.ter};      // every kernel reads its own prefix
+    (void)hipLaunchKernel(fam.tu(fused, H.kind.limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), args, (size_t)H.kind.lds_bytes, (hipStream_t)stream);
+    if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string(fam.contacts ? "fp64 contacts step kernel launch: " : "fp64 step kernel launch: ") + hipGetErrorString(e));
     return FMJ_OK;
   }
   if (c->path == PATH_TWO_WAVE) return launch("two-wave step kernel", wide_kernel(D.rs, fused), c->n_envs, 128, c->lds_bytes_wide, stream, D, A);
@@ -1984,14 +1998,8 @@ static int resolve_kernel_choice(const fmj_create_options* opts, KernelChoice* K
 // ---- stage 1: every check of the model (host only, before any device call) and the facts the later stages build on
 struct ModelFacts {
   KernelChoice kernel;        // set by fmj_create_ex before check_model
-  bool f64_limits_ok = false; // set by fmj_create_ex2 (FMJ_CREATE_F64_LIMITS): an fp64 context takes joint limits
-  int f64_limits = 0;         // such a context whose model has limited joints: the LIMITS builds of the fp64 kernel; cons stays 0
-  bool f64_rk4_ok = false;    // set by fmj_create_ex2 (FMJ_CREATE_F64_RK4): an fp64 context takes integrator = FMJ_INT_RK4
-  int f64_rk4 = 0;            // such a context whose model integrates with RK4: fmj_step_f64_rk4_kernel, four passes inside one launch
-  bool f64_contacts_ok = false; // set by fmj_create_ex2 (FMJ_CREATE_F64_CONTACTS): an fp64 context takes ground contacts
-  int f64_contacts = 0;       // such a context whose model has animat geoms and a plane: fmj_step_f64_contacts_kernel; cons stays 0
-  bool f64_terrain_ok = false;  // set by fmj_create_ex2 (FMJ_CREATE_F64_TERRAIN, with _CONTACTS): the contact solve takes the heightfield and cylinders
-  int f64_terrain = 0;        // such a context with f64_contacts: fmj_step_f64_terrain_kernel in the place of the contacts kernel
+  int32_t ext_flags = 0;      // set by fmj_create_ex2: fmj_create_ext.flags (FMJ_CREATE_F64_*: what an fp64 context may take)
+  F64Kind f64;                // an fp64 context's kernel family, its limits bit and its LDS: such a model's cons stays 0
   int cons = 0, big = 0;      // limits, contacts or pairs (the constraint kernels); nbody or nv above 64 (past one wavefront)
   int wide = 0;               // every step launch runs the two-wave kernel (fmj_wide.inc): big, or kernel.two_wave
   int nplane = 0, n_hfield = 0, any_mesh = 0, any_box = 0, any_polypair = 0;     // nplane counts the ground geoms: planes and the heightfield
@@ -2018,6 +2026,7 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   if (nb < 2 || nb > 128 || nv < 1 || nv > 128) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: need 2 <= nbody <= 128 and 1 <= nv <= 128 (two wavefronts per environment at most)");
   const bool big = nb > 64 || nv > 64;      // past one wavefront: the two-wave kernel (fmj_wide.inc), unconstrained models only
   int any_limit = 0; int& nplane = F->nplane; int& n_hfield = F->n_hfield;
+  const auto asked = [F](int32_t flag) { return (F->ext_flags & flag) != 0; };
   for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) any_limit = 1;
   for (int g = 0; g < m->ngeom; g++) {
     int t = m->geom_type[g];
@@ -2061,15 +2070,16 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   if (precision == FMJ_PRECISION_F64) {      // the fp64 step kernel (fmj_f64.inc) is the unconstrained Euler / implicitfast step
     // on request (fmj_create_ex2) it solves joint limits itself: such a model is no constraint-path model to the stages below,
     // whose limits (64 bodies / dofs, a dof chain of 32, 192 rows) belong to the fp32 constraint kernels
-    if (F->f64_limits_ok) { any_limit = 0; cons = (nplane > 0 && m->ngeom > nplane) || m->npair > 0; }
+    if (asked(FMJ_CREATE_F64_LIMITS)) { any_limit = 0; cons = (nplane > 0 && m->ngeom > nplane) || m->npair > 0; }
     // on request it solves ground contacts too (FMJ_CREATE_F64_CONTACTS): body-vs-world rows keep the tree-sparse pattern of M
-    if (F->f64_contacts_ok && !any_limit && cons) {
+    bool contacts = false;
+    if (asked(FMJ_CREATE_F64_CONTACTS) && !any_limit && cons) {
       const auto no = [](const char* what) { return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex2: the fp64 contact solve (FMJ_CREATE_F64_CONTACTS) has no ") + what); };
       if (m->npair > 0) return no("explicit contact pairs (their rows couple two chains: outside the tree-sparse pattern of M)");
       for (int g = 0; g < m->ngeom; g++) {
         const int t = m->geom_type[g];
-        if (t == FMJ_GEOM_HFIELD && !F->f64_terrain_ok) return no("heightfield geoms");
-        if (t == FMJ_GEOM_CYLINDER && !F->f64_terrain_ok) return no("cylinder geoms");
+        if (t == FMJ_GEOM_HFIELD && !asked(FMJ_CREATE_F64_TERRAIN)) return no("heightfield geoms");
+        if (t == FMJ_GEOM_CYLINDER && !asked(FMJ_CREATE_F64_TERRAIN)) return no("cylinder geoms");
         if (t == FMJ_GEOM_MESH) return no("mesh geoms");
       }
       if (m->cone != FMJ_CONE_PYRAMIDAL) return no("elliptic cone (pyramidal only)");
@@ -2086,15 +2096,14 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
         while (a >= 1 && m->body_dofnum[a] == 0) a = m->body_parentid[a];
         if (a < 1) return no("rows for a collision geom on a body without dofs");
       }
-      F->f64_contacts = 1; cons = 0;
-      F->f64_terrain = F->f64_terrain_ok;
+      contacts = true; cons = 0;
     }
     if (cons) return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex: the fp64 step has no constraint solver: the model has ") +
                              (any_limit ? "joint limits" : m->npair > 0 ? "explicit contact pairs" : "contact geoms"));
-    if (F->f64_limits_ok) for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) F->f64_limits = 1;
-    if (F->f64_limits && (m->solver_iterations < 0 || !(m->solver_tolerance >= 0))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
-    if (m->integrator == FMJ_INT_RK4 && !F->f64_rk4_ok) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
-    F->f64_rk4 = m->integrator == FMJ_INT_RK4;
+    if (asked(FMJ_CREATE_F64_LIMITS)) for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) F->f64.limits = 1;
+    if (F->f64.limits && (m->solver_iterations < 0 || !(m->solver_tolerance >= 0))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
+    if (m->integrator == FMJ_INT_RK4 && !asked(FMJ_CREATE_F64_RK4)) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
+    F->f64.family = contacts ? (asked(FMJ_CREATE_F64_TERRAIN) ? F64_TERRAIN : F64_CONTACTS) : m->integrator == FMJ_INT_RK4 ? F64_RK4 : F->f64.limits ? F64_LIMITS : F64_PLAIN;
   }
   if (big && cons) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: nbody or nv above 64 with limits, contacts or pairs (one wavefront per environment on the constraint path)");
   if (cons && m->solver != FMJ_SOLVER_PGS && m->solver != FMJ_SOLVER_NEWTON && m->solver != FMJ_SOLVER_CG) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: solver must be FMJ_SOLVER_PGS, FMJ_SOLVER_CG or FMJ_SOLVER_NEWTON");
@@ -2111,7 +2120,7 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   if (m->noslip_iterations < 0 || !(m->noslip_tolerance >= 0)) return set_err(FMJ_ERR_ARG, "fmj_create: noslip_iterations / noslip_tolerance must not be negative");
   if (m->integrator != FMJ_INT_EULER && m->integrator != FMJ_INT_IMPLICITFAST && m->integrator != FMJ_INT_RK4)
     return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: integrator must be FMJ_INT_EULER, FMJ_INT_IMPLICITFAST or FMJ_INT_RK4 (implicit keeps the Coriolis derivatives, a non-symmetric matrix outside this path's tree-sparse factorisation)");
-  if (big && m->integrator == FMJ_INT_RK4 && !F->f64_rk4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: RK4 on a model with more than 64 bodies or dofs (its stage kernel holds one dof per lane of one wavefront)");
+  if (big && m->integrator == FMJ_INT_RK4 && F->f64.family != F64_RK4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: RK4 on a model with more than 64 bodies or dofs (its stage kernel holds one dof per lane of one wavefront)");
   if (cons && (m->ngeom > nplane || m->npair > 0) && !any_limit && m->max_contacts < 1) return set_err(FMJ_ERR_ARG, "fmj_create: max_contacts must be >= 1 with collision geoms");
   if ((m->npair > 0 || (nplane > 0 && m->ngeom > nplane)) && m->max_contacts < 1) return set_err(FMJ_ERR_ARG, "fmj_create: max_contacts must be >= 1 with collision geoms");
   // structure checks: single tree rooted at body 1, DFS pre-order, <= 1 joint per body
@@ -2183,16 +2192,14 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   // the block solvers (elliptic PGS, noslip) keep forces, b, R and mu of every row in the LDS staging area of the row code: min(maxefc, 64) * rs floats
   if (cons && (m->noslip_iterations > 0 || (m->cone == FMJ_CONE_ELLIPTIC && (m->solver == FMJ_SOLVER_PGS || dual_instead))) && std::min(F->maxefc, FMJ_NA) * F->rs < 4 * F->maxefc)
     return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: PGS with the elliptic cone / noslip: too many constraint rows for this model's row length (needs min(maxefc, 64) * rs >= 4 * maxefc): lower max_contacts");
-  if (F->f64_contacts) {      // what fmj_constraint_info reports; the LDS of fmj_step_f64_contacts_kernel at this model's sizes
-    F->max_contacts = m->max_contacts; F->maxefc = 2 * nj + 4 * m->max_contacts;
-    const int bytes = ldsd_contacts_bytes(nb, nv, nq, r4(max_ddepth + 1), m->max_contacts);
-    const int tbytes = ldsd_terrain_bytes(nb, nv, nq, r4(max_ddepth + 1), m->max_contacts);
-    if (F->f64_terrain && tbytes > 160 * 1024)
-      return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex2: the fp64 contact solve on terrain (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_TERRAIN) needs " + std::to_string(tbytes) +
-                                          " bytes of LDS for this model (its bodies, dofs, dof chain and max_contacts), above 160 KB: lower max_contacts");
+  if (F->f64.family >= 0) {      // the family's LDS at this model's sizes
+    const F64Family& fam = f64_families[F->f64.family];
+    if (fam.contacts) { F->max_contacts = m->max_contacts; F->maxefc = 2 * nj + 4 * m->max_contacts; }      // what fmj_constraint_info reports
+    const int bytes = F->f64.lds_bytes = f64_lds_bytes(F->f64.family, F->f64.limits, nb, nv, nq, r4(max_ddepth + 1), m->max_contacts, nu);
     if (bytes > 160 * 1024)
-      return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex2: the fp64 contact solve (FMJ_CREATE_F64_CONTACTS) needs " + std::to_string(bytes) +
-                                          " bytes of LDS for this model (its bodies, dofs, dof chain and max_contacts), above 160 KB: lower max_contacts");
+      return !fam.solve ? set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: fp64 step kernel LDS above 160 KB")     // (cannot happen within the size limits)
+                        : set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex2: ") + fam.solve + " needs " + std::to_string(bytes) +
+                                                       " bytes of LDS for this model (its bodies, dofs, dof chain and max_contacts), above 160 KB: lower max_contacts");
   }
   if (F->wide && (size_t)ldsw_layout(nb, nv, nq, F->rs, F->anc_stride).total * sizeof(float) > 64 * 1024)
     return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: two-wave kernel LDS above 64 KB");     // (cannot happen within the size limits above)
@@ -2203,9 +2210,9 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
 static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
   const int nb = m->nbody, nv = m->nv, nj = m->njnt;
   DevModel& D = c->dm;
-  c->solver_requested = (F.cons || F.f64_limits || F.f64_contacts) ? m->solver : FMJ_SOLVER_PGS;
+  c->solver_requested = (F.cons || F.f64.solves()) ? m->solver : FMJ_SOLVER_PGS;
   c->nbody = nb; c->nv = nv; c->nu = m->nu; c->njnt = nj;
-  c->rk4 = m->integrator == FMJ_INT_RK4 && !F.f64_rk4;      // (an fp64 RK4 context runs its passes inside the kernel: no stage buffers, no stage launches)
+  c->rk4 = m->integrator == FMJ_INT_RK4 && F.f64.family != F64_RK4;      // (an fp64 RK4 context runs its passes inside the kernel: no stage buffers, no stage launches)
   D.nbody = nb; D.nv = nv; D.nq = m->nq; D.nu = m->nu; D.njnt = nj; D.nM = m->nM;
   D.max_bdepth = F.jump_rounds;       // pointer-jumping rounds
   D.max_subsize = F.max_sub;
@@ -2237,7 +2244,7 @@ static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) 
   D.solver_iterations = F.dual_instead ? 10 * m->solver_iterations : m->solver_iterations; D.solver_tolerance = (float)m->solver_tolerance;
   D.cone = cons ? m->cone : FMJ_CONE_PYRAMIDAL;
   D.noslip_iterations = cons ? m->noslip_iterations : 0; D.noslip_tolerance = (float)m->noslip_tolerance;
-  D.solver = (F.f64_limits || F.f64_contacts) ? FMJ_SOLVER_NEWTON : (cons && !F.dual_instead) ? m->solver : FMJ_SOLVER_PGS; D.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
+  D.solver = F.f64.solves() ? FMJ_SOLVER_NEWTON : (cons && !F.dual_instead) ? m->solver : FMJ_SOLVER_PGS; D.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
   D.ls_tolerance = (float)(m->ls_tolerance > 0 ? m->ls_tolerance : 0.01);
   D.impratio_isqrt = (float)(1.0 / sqrt(m->impratio > 0 ? m->impratio : 1.0));
   D.pgs_scale = (float)(1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1)));
@@ -2613,9 +2620,20 @@ static int choose_path(fmj_ctx* c, const ModelFacts& F) {
 // ---- stage 8, fp64 contexts only: the fp64 model tables of the fp64 step kernel (fmj_f64.inc), its rounds and its LDS
 template <class T>
 static int upload_f64(fmj_ctx* c, const std::vector<T>& h, const T** dptr) { return upload(c, h, dptr); }
-static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+// add_contact's frame of a plane: the two tangents from its normal, t1 then t2 = n x t1
+static void plane_tangents(const double n[3], double* t) {
+  double t1[3] = {0, 0, 0};
+  if (n[1] < -0.5 || n[1] > 0.5) t1[2] = 1; else t1[1] = 1;
+  const double dt = t1[0] * n[0] + t1[1] * n[1] + t1[2] * n[2];
+  for (int k = 0; k < 3; k++) t1[k] -= dt * n[k];
+  const double nn = sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
+  for (int k = 0; k < 3; k++) t[k] = t1[k] / nn;
+  t[3] = n[1] * t[2] - n[2] * t[1]; t[4] = n[2] * t[0] - n[0] * t[2]; t[5] = n[0] * t[1] - n[1] * t[0];
+}
+
+// (a) the model tables of F64Model, the rounds, and the host mirrors
+static int f64_model_tables(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
   const int nb = m->nbody, nv = m->nv, nu = m->nu, nj = m->njnt;
-  c->f64 = new F64Host();
   F64Host& H = *c->f64;
   F64Model& M = H.fm;
   const DevModel& D = c->dm;
@@ -2679,109 +2697,103 @@ static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
       (rc = upload_f64(c, ad, &M.ad)) || (rc = upload_f64(c, asrc, &M.asrc)) || (rc = upload_f64(c, danc, &M.danc)) || (rc = upload_f64(c, rw, &M.rounds)))
     return rc;
   M.b_anc = D.b_anc;
-  if (F.f64_limits || F.f64_contacts) {      // the Newton solve's settings
-    H.lim.solver_iterations = m->solver_iterations; H.lim.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
-    H.lim.tolerance = m->solver_tolerance; H.lim.ls_tolerance = m->ls_tolerance > 0 ? m->ls_tolerance : 0.01;
-    H.lim.scale = 1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (nv > 1 ? nv : 1));
+  return FMJ_OK;
+}
+
+// (b) the Newton solve's settings, and the limit rows' constants, unrounded (oracle make_constraints)
+static int f64_solver_and_limit_rows(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  F64Host& H = *c->f64;
+  if (!F.f64.solves()) return FMJ_OK;
+  H.lim.solver_iterations = m->solver_iterations; H.lim.ls_iterations = m->ls_iterations > 0 ? m->ls_iterations : 50;
+  H.lim.tolerance = m->solver_tolerance; H.lim.ls_tolerance = m->ls_tolerance > 0 ? m->ls_tolerance : 0.01;
+  H.lim.scale = 1.0 / ((m->meaninertia > 0 ? m->meaninertia : 1.0) * (m->nv > 1 ? m->nv : 1));
+  if (!F.f64.limits) return FMJ_OK;
+  std::vector<double> lm((size_t)m->nv * F64_LM, 0.0);
+  for (int j = 0; j < m->njnt; j++) {
+    if (m->jnt_type[j] == FMJ_JNT_FREE) continue;
+    double* t = &lm[(size_t)m->jnt_dofadr[j] * F64_LM];
+    t[0] = m->jnt_limited[j] ? 1.0 : 0.0; t[1] = m->jnt_range[2 * j]; t[2] = m->jnt_range[2 * j + 1]; t[3] = m->jnt_margin[j];
+    t[4] = m->jnt_solref[2 * j]; t[5] = m->jnt_solref[2 * j + 1];
+    for (int k = 0; k < 5; k++) t[6 + k] = m->jnt_solimp[5 * j + k];
+    t[11] = m->dof_invweight0[m->jnt_dofadr[j]];
   }
-  if (F.f64_limits) {      // the rows' constants, unrounded (oracle make_constraints)
-    std::vector<double> lm((size_t)nv * F64_LM, 0.0);
-    for (int j = 0; j < nj; j++) {
-      if (m->jnt_type[j] == FMJ_JNT_FREE) continue;
-      double* t = &lm[(size_t)m->jnt_dofadr[j] * F64_LM];
-      t[0] = m->jnt_limited[j] ? 1.0 : 0.0; t[1] = m->jnt_range[2 * j]; t[2] = m->jnt_range[2 * j + 1]; t[3] = m->jnt_margin[j];
-      t[4] = m->jnt_solref[2 * j]; t[5] = m->jnt_solref[2 * j + 1];
-      for (int k = 0; k < 5; k++) t[6 + k] = m->jnt_solimp[5 * j + k];
-      t[11] = m->dof_invweight0[m->jnt_dofadr[j]];
-    }
-    if ((rc = upload_f64(c, lm, &H.lim.lm))) return rc;
-    H.limits = 1;
+  return upload_f64(c, lm, &H.lim.lm);
+}
+
+// (c) the geom table of the families with contacts, unrounded (oracle collide_plane, make_constraints)
+static int f64_geom_table(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  F64Contacts& C = c->f64->con;
+  C.ngeom = m->ngeom; C.nplane = F.nplane; C.max_contacts = m->max_contacts; C.sqrt_impratio = sqrt(m->impratio > 0 ? m->impratio : 1.0);
+  std::vector<double> gd((size_t)m->ngeom * F64_GD, 0.0);
+  std::vector<int> gi((size_t)m->ngeom * F64_GI, 0);
+  for (int g = 0; g < m->ngeom; g++) {
+    double* t = &gd[(size_t)g * F64_GD]; int* ti = &gi[(size_t)g * F64_GI];
+    const int b = m->geom_bodyid[g];
+    for (int k = 0; k < 3; k++) { t[k] = m->geom_size[3 * g + k]; t[3 + k] = m->geom_pos[3 * g + k]; }
+    for (int k = 0; k < 4; k++) t[6 + k] = m->geom_quat[4 * g + k];
+    t[10] = m->geom_friction[3 * g]; t[11] = m->body_invweight0[2 * b] + m->body_invweight0[0];
+    t[16] = m->geom_solref[2 * g]; t[17] = m->geom_solref[2 * g + 1];
+    for (int k = 0; k < 5; k++) t[18 + k] = m->geom_solimp[5 * g + k];
+    int a = b;
+    while (a >= 1 && m->body_dofnum[a] == 0) a = m->body_parentid[a];
+    ti[0] = m->geom_type[g]; ti[1] = b; ti[2] = a >= 1 ? m->body_dofadr[a] + m->body_dofnum[a] - 1 : -1;
   }
-  H.rk4 = F.f64_rk4;
-  H.lds_bytes = (size_t)ldsd_total_bytes(nb, nv, m->nq, M.rs, H.limits) + (H.rk4 ? (size_t)F64_RK4_LDS_DOUBLES(m->nu) * 8 : 0);
-  if (F.f64_contacts) {      // the geom and plane tables, unrounded (oracle collide_plane, add_contact, make_constraints)
-    F64Contacts& C = H.con;
-    C.ngeom = m->ngeom; C.nplane = F.nplane; C.max_contacts = m->max_contacts; C.sqrt_impratio = sqrt(m->impratio > 0 ? m->impratio : 1.0);
-    std::vector<double> gd((size_t)m->ngeom * F64_GD, 0.0), pd((size_t)F.nplane * F64_PD, 0.0);
-    std::vector<int> gi((size_t)m->ngeom * F64_GI, 0);
-    int ip = 0;
-    for (int g = 0; g < m->ngeom; g++) {
-      double* t = &gd[(size_t)g * F64_GD]; int* ti = &gi[(size_t)g * F64_GI];
-      const int b = m->geom_bodyid[g];
-      for (int k = 0; k < 3; k++) { t[k] = m->geom_size[3 * g + k]; t[3 + k] = m->geom_pos[3 * g + k]; }
-      for (int k = 0; k < 4; k++) t[6 + k] = m->geom_quat[4 * g + k];
-      t[10] = m->geom_friction[3 * g]; t[11] = m->body_invweight0[2 * b] + m->body_invweight0[0];
-      t[16] = m->geom_solref[2 * g]; t[17] = m->geom_solref[2 * g + 1];
-      for (int k = 0; k < 5; k++) t[18 + k] = m->geom_solimp[5 * g + k];
-      int a = b;
-      while (a >= 1 && m->body_dofnum[a] == 0) a = m->body_parentid[a];
-      ti[0] = m->geom_type[g]; ti[1] = b; ti[2] = a >= 1 ? m->body_dofadr[a] + m->body_dofnum[a] - 1 : -1;
-      if (m->geom_type[g] != FMJ_GEOM_PLANE || F.f64_terrain) continue;      // (a terrain context reads its ground entries from F64Terrain.tg)
-      // world-attached plane: normal = z axis of the geom frame (mju_quat2Mat of the geom's quaternion), point = geom_pos; the frame of add_contact
-      const double* q = m->geom_quat + 4 * g;
-      double* pt = &pd[(size_t)ip++ * F64_PD];
+  if (int rc = upload_f64(c, gd, &C.gd)) return rc;
+  return upload_f64(c, gi, &C.gi);
+}
+
+// (d) the ground entries in geom order, world-attached: the contacts family's plane rows (F64_PD: the normal is the z axis of the geom's
+// frame, mju_quat2Mat of its quaternion), or the terrain family's rows (F64_TG: the whole frame, oracle ground_dist, and the heightfield's
+// samples in double); a plane's tangents are add_contact's in both
+static int f64_ground_entries(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  F64Host& H = *c->f64;
+  const bool terrain = F.f64.family == F64_TERRAIN;
+  std::vector<double> rows((size_t)F.nplane * (terrain ? F64_TG : F64_PD), 0.0);
+  int rc, i = 0;
+  for (int g = 0; g < m->ngeom; g++) {
+    const int t = m->geom_type[g];
+    if (t != FMJ_GEOM_PLANE && !(terrain && t == FMJ_GEOM_HFIELD)) continue;
+    const double* q = m->geom_quat + 4 * g;
+    if (!terrain) {
+      double* pt = &rows[(size_t)i++ * F64_PD];
       const double n[3] = {2.0 * (q[1] * q[3] + q[0] * q[2]), 2.0 * (q[2] * q[3] - q[0] * q[1]), q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3]};
-      double t1[3] = {0, 0, 0};
-      if (n[1] < -0.5 || n[1] > 0.5) t1[2] = 1; else t1[1] = 1;
-      const double dt = t1[0] * n[0] + t1[1] * n[1] + t1[2] * n[2];
-      for (int k = 0; k < 3; k++) t1[k] -= dt * n[k];
-      const double nn = sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
-      for (int k = 0; k < 3; k++) { pt[k] = n[k]; pt[3 + k] = m->geom_pos[3 * g + k]; pt[6 + k] = t1[k] / nn; }
-      pt[9] = pt[1] * pt[8] - pt[2] * pt[7]; pt[10] = pt[2] * pt[6] - pt[0] * pt[8]; pt[11] = pt[0] * pt[7] - pt[1] * pt[6];
+      for (int k = 0; k < 3; k++) { pt[k] = n[k]; pt[3 + k] = m->geom_pos[3 * g + k]; }
+      plane_tangents(n, pt + 6);
       pt[12] = m->geom_friction[3 * g]; pt[13] = g;
+      continue;
     }
-    if ((rc = upload_f64(c, gd, &C.gd)) || (rc = upload_f64(c, gi, &C.gi))) return rc;
-    if (!F.f64_terrain && (rc = upload_f64(c, pd, &C.pd))) return rc;
-    H.contacts = 1;
-    if (F.f64_terrain) {      // the ground entries in geom order (oracle ground_dist; add_contact's frame for a plane), the samples in double
-      std::vector<double> tg((size_t)F.nplane * F64_TG, 0.0);
-      int it = 0;
-      for (int g = 0; g < m->ngeom; g++) {
-        const int t = m->geom_type[g];
-        if (t != FMJ_GEOM_PLANE && t != FMJ_GEOM_HFIELD) continue;
-        double* e = &tg[(size_t)it++ * F64_TG];
-        const double* q = m->geom_quat + 4 * g;      // world-attached: the geom's own frame (mju_quat2Mat)
-        const double q00 = q[0] * q[0], q11 = q[1] * q[1], q22 = q[2] * q[2], q33 = q[3] * q[3];
-        e[0] = q00 + q11 - q22 - q33; e[4] = q00 - q11 + q22 - q33; e[8] = q00 - q11 - q22 + q33;
-        e[1] = 2.0 * (q[1] * q[2] - q[0] * q[3]); e[2] = 2.0 * (q[1] * q[3] + q[0] * q[2]);
-        e[3] = 2.0 * (q[1] * q[2] + q[0] * q[3]); e[5] = 2.0 * (q[2] * q[3] - q[0] * q[1]);
-        e[6] = 2.0 * (q[1] * q[3] - q[0] * q[2]); e[7] = 2.0 * (q[2] * q[3] + q[0] * q[1]);
-        for (int k = 0; k < 3; k++) e[9 + k] = m->geom_pos[3 * g + k];
-        e[12] = m->geom_friction[3 * g]; e[13] = g;
-        if (t == FMJ_GEOM_PLANE) {
-          const double n[3] = {e[2], e[5], e[8]};
-          double t1[3] = {0, 0, 0};
-          if (n[1] < -0.5 || n[1] > 0.5) t1[2] = 1; else t1[1] = 1;
-          const double dt = t1[0] * n[0] + t1[1] * n[1] + t1[2] * n[2];
-          for (int k = 0; k < 3; k++) t1[k] -= dt * n[k];
-          const double nn = sqrt(t1[0] * t1[0] + t1[1] * t1[1] + t1[2] * t1[2]);
-          for (int k = 0; k < 3; k++) e[15 + k] = t1[k] / nn;
-          e[18] = n[1] * e[17] - n[2] * e[16]; e[19] = n[2] * e[15] - n[0] * e[17]; e[20] = n[0] * e[16] - n[1] * e[15];
-        } else {
-          const int nc = m->hfield_ncol, nr = m->hfield_nrow;
-          e[14] = 1.0; e[15] = nc; e[16] = nr; e[17] = m->hfield_size[0]; e[18] = m->hfield_size[1]; e[19] = m->hfield_size[2];
-          e[20] = (nc - 1) / (2 * m->hfield_size[0]); e[21] = (nr - 1) / (2 * m->hfield_size[1]);
-          if ((rc = upload_f64(c, std::vector<double>(m->hfield_data, m->hfield_data + (size_t)nr * nc), &H.ter.hf))) return rc;
-        }
-      }
-      if ((rc = upload_f64(c, tg, &H.ter.tg))) return rc;
-      H.terrain = 1;
-      H.lds_bytes = (size_t)ldsd_terrain_bytes(nb, nv, m->nq, M.rs, m->max_contacts);      // (check_model held it to 160 KB)
-      if (hipFuncSetAttribute((const void*)fmj_tu_f64_terrain(H.limits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
-        return set_err(FMJ_ERR_HIP, "fmj_create_ex2: LDS request of the fp64 terrain step kernel too large");
-      c->path = PATH_F64;
-      return sync_f64_maps(c);
+    double* e = &rows[(size_t)i++ * F64_TG];
+    const double q00 = q[0] * q[0], q11 = q[1] * q[1], q22 = q[2] * q[2], q33 = q[3] * q[3];
+    e[0] = q00 + q11 - q22 - q33; e[4] = q00 - q11 + q22 - q33; e[8] = q00 - q11 - q22 + q33;
+    e[1] = 2.0 * (q[1] * q[2] - q[0] * q[3]); e[2] = 2.0 * (q[1] * q[3] + q[0] * q[2]);
+    e[3] = 2.0 * (q[1] * q[2] + q[0] * q[3]); e[5] = 2.0 * (q[2] * q[3] - q[0] * q[1]);
+    e[6] = 2.0 * (q[1] * q[3] - q[0] * q[2]); e[7] = 2.0 * (q[2] * q[3] + q[0] * q[1]);
+    for (int k = 0; k < 3; k++) e[9 + k] = m->geom_pos[3 * g + k];
+    e[12] = m->geom_friction[3 * g]; e[13] = g;
+    if (t == FMJ_GEOM_PLANE) {
+      const double n[3] = {e[2], e[5], e[8]};
+      plane_tangents(n, e + 15);
+      continue;
     }
-    H.lds_bytes = (size_t)ldsd_contacts_bytes(nb, nv, m->nq, M.rs, m->max_contacts);      // (check_model held it to 160 KB)
-    if (hipFuncSetAttribute((const void*)fmj_tu_f64_contacts(H.limits), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
-      return set_err(FMJ_ERR_HIP, "fmj_create_ex2: LDS request of the fp64 contacts step kernel too large");
-    c->path = PATH_F64;
-    return sync_f64_maps(c);
+    const int nc = m->hfield_ncol, nr = m->hfield_nrow;
+    e[14] = 1.0; e[15] = nc; e[16] = nr; e[17] = m->hfield_size[0]; e[18] = m->hfield_size[1]; e[19] = m->hfield_size[2];
+    e[20] = (nc - 1) / (2 * m->hfield_size[0]); e[21] = (nr - 1) / (2 * m->hfield_size[1]);
+    if ((rc = upload_f64(c, std::vector<double>(m->hfield_data, m->hfield_data + (size_t)nr * nc), &H.ter.hf))) return rc;
   }
-  if (H.lds_bytes > 160 * 1024) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: fp64 step kernel LDS above 160 KB");     // (cannot happen within the size limits)
-  for (int fused = 0; fused < 2; fused++)
-    if (hipFuncSetAttribute((const void*)f64_kernel(fused, H.limits, H.rk4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)H.lds_bytes) != hipSuccess)
-      return set_err(FMJ_ERR_HIP, "fmj_create_ex: LDS request of the fp64 step kernel too large");
+  return upload_f64(c, rows, terrain ? &H.ter.tg : &H.con.pd);
+}
+
+static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  c->f64 = new F64Host();
+  const F64Kind& K = c->f64->kind = F.f64;
+  const F64Family& fam = f64_families[K.family];
+  int rc;
+  if ((rc = f64_model_tables(c, m, F)) || (rc = f64_solver_and_limit_rows(c, m, F)) ||
+      (fam.contacts && ((rc = f64_geom_table(c, m, F)) || (rc = f64_ground_entries(c, m, F)))))
+    return rc;
+  for (int fused = 0; fused <= (int)fam.fused; fused++)      // (check_model held the bytes to 160 KB)
+    if (hipFuncSetAttribute((const void*)fam.tu(fused, K.limits), hipFuncAttributeMaxDynamicSharedMemorySize, K.lds_bytes) != hipSuccess)
+      return set_err(FMJ_ERR_HIP, fam.lds_refused);
   c->path = PATH_F64;
   return sync_f64_maps(c);      // the default rows; no swimming slots yet
 }
@@ -2811,24 +2823,26 @@ int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj
   if (!m || !out || n_envs <= 0) return set_err(FMJ_ERR_ARG, "fmj_create: NULL model/out or n_envs <= 0");
   *out = nullptr;
   if (ext && ext->size != (int32_t)sizeof(fmj_create_ext)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: fmj_create_ext.size is not sizeof(fmj_create_ext)");
-  if (ext && (ext->flags & ~(int32_t)(FMJ_CREATE_F64_LIMITS | FMJ_CREATE_F64_RK4 | FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_TERRAIN))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: unknown bits in fmj_create_ext.flags");
-  if (ext && (ext->flags & FMJ_CREATE_F64_LIMITS) && !(opts && opts->precision == FMJ_PRECISION_F64))
-    return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_LIMITS needs precision = FMJ_PRECISION_F64 (the limits solve belongs to the fp64 step kernel)");
-  if (ext && (ext->flags & FMJ_CREATE_F64_RK4) && !(opts && opts->precision == FMJ_PRECISION_F64))
-    return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_RK4 needs precision = FMJ_PRECISION_F64 (the in-kernel RK4 belongs to the fp64 step kernel)");
-  if (ext && (ext->flags & FMJ_CREATE_F64_CONTACTS) && !(opts && opts->precision == FMJ_PRECISION_F64))
-    return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_CONTACTS needs precision = FMJ_PRECISION_F64 (the contact solve belongs to the fp64 step kernel)");
-  if (ext && (ext->flags & FMJ_CREATE_F64_TERRAIN) && !((ext->flags & FMJ_CREATE_F64_CONTACTS) && opts && opts->precision == FMJ_PRECISION_F64))
-    return set_err(FMJ_ERR_ARG, "fmj_create_ex2: FMJ_CREATE_F64_TERRAIN needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it widens the fp64 contact solve's narrow phase)");
+  // what fmj_create_ext.flags may hold: the flag, the other bits it needs next to precision = FMJ_PRECISION_F64, and what is said otherwise
+  static const struct { int32_t flag, needs; const char* reason; } f64_flags[] = {
+    {FMJ_CREATE_F64_LIMITS, 0, "fmj_create_ex2: FMJ_CREATE_F64_LIMITS needs precision = FMJ_PRECISION_F64 (the limits solve belongs to the fp64 step kernel)"},
+    {FMJ_CREATE_F64_RK4, 0, "fmj_create_ex2: FMJ_CREATE_F64_RK4 needs precision = FMJ_PRECISION_F64 (the in-kernel RK4 belongs to the fp64 step kernel)"},
+    {FMJ_CREATE_F64_CONTACTS, 0, "fmj_create_ex2: FMJ_CREATE_F64_CONTACTS needs precision = FMJ_PRECISION_F64 (the contact solve belongs to the fp64 step kernel)"},
+    {FMJ_CREATE_F64_TERRAIN, FMJ_CREATE_F64_CONTACTS,
+     "fmj_create_ex2: FMJ_CREATE_F64_TERRAIN needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it widens the fp64 contact solve's narrow phase)"},
+  };
+  const int32_t flags = ext ? ext->flags : 0;
+  int32_t known = 0;
+  for (const auto& f : f64_flags) known |= f.flag;
+  if (flags & ~known) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: unknown bits in fmj_create_ext.flags");
+  for (const auto& f : f64_flags)
+    if ((flags & f.flag) && !((flags & f.needs) == f.needs && opts && opts->precision == FMJ_PRECISION_F64)) return set_err(FMJ_ERR_ARG, f.reason);
   if (opts && opts->size != 8 && opts->size != (int32_t)sizeof(fmj_create_options))
     return set_err(FMJ_ERR_ARG, "fmj_create_ex: fmj_create_options.size is neither sizeof(fmj_create_options) nor 8 (the struct before the kernel fields)");
   const int precision = opts ? opts->precision : FMJ_PRECISION_F32;
   if (precision != FMJ_PRECISION_F32 && precision != FMJ_PRECISION_F64) return set_err(FMJ_ERR_ARG, "fmj_create_ex: precision must be FMJ_PRECISION_F32 or FMJ_PRECISION_F64");
   ModelFacts F;
-  F.f64_limits_ok = ext && (ext->flags & FMJ_CREATE_F64_LIMITS);
-  F.f64_rk4_ok = ext && (ext->flags & FMJ_CREATE_F64_RK4);
-  F.f64_contacts_ok = ext && (ext->flags & FMJ_CREATE_F64_CONTACTS);
-  F.f64_terrain_ok = ext && (ext->flags & FMJ_CREATE_F64_TERRAIN);
+  F.ext_flags = flags;
   if (int rc = resolve_kernel_choice(opts, &F.kernel)) return rc;
   if (int rc = check_model(m, &F, precision)) return rc;
   int ndev = 0;
@@ -2854,7 +2868,7 @@ int fmj_get_sensor_layout(const fmj_ctx* c, fmj_sensor_layout_t* out) {
 int fmj_kernel_info(const fmj_ctx* c, int32_t* lds_bytes_per_env, int32_t* threads_per_env) {
   if (!c) return set_err(FMJ_ERR_ARG, "fmj_kernel_info: NULL ctx");
   // by StepPath: the integrating step packs two envs per wave when it can
-  const size_t lds[5] = {c->lds_bytes, c->lds_bytes_dual2 / 2, c->lds_bytes_cons2 / 2, c->lds_bytes_wide, c->f64 ? c->f64->lds_bytes : 0};
+  const size_t lds[5] = {c->lds_bytes, c->lds_bytes_dual2 / 2, c->lds_bytes_cons2 / 2, c->lds_bytes_wide, c->f64 ? (size_t)c->f64->kind.lds_bytes : 0};
   const int threads[5] = {64, 32, 32, 128, FMJ_F64_LANES};
   if (lds_bytes_per_env) *lds_bytes_per_env = (int32_t)lds[c->path];
   if (threads_per_env) *threads_per_env = threads[c->path];
@@ -3121,7 +3135,7 @@ int fmj_step_fused_ex(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, co
 }
 
 int fmj_step_fused_f64(fmj_ctx* c, const fmj_data* d, const fmj_fused_args* a, const fmj_fused_ext* ext, void* stream) {
-  if (c && c->f64 && c->f64->contacts) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused_f64: an fp64 context with contacts (FMJ_CREATE_F64_CONTACTS) steps through fmj_step: fused contact rows are not built");
+  if (c && c->f64 && !f64_families[c->f64->kind.family].fused) return set_err(FMJ_ERR_UNSUPPORTED, F64_NO_FUSED);
   StepArgs A; int rc = fused_step_args(c, d, a, ext, FMJ_PRECISION_F64, &A); if (rc) return rc;
   if (a->rows_base.contacts) return set_err(FMJ_ERR_ARG, "fmj_step_fused_f64: contact rows: an fp64 model has no collision geoms");
   if (a->rows_ahead) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_step_fused_f64: rows_ahead is not built for the fp64 step kernel (write the rows with fmj_before_step instead)");

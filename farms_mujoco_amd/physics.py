@@ -37,6 +37,30 @@ class _MjData(SimpleNamespace):
         object.__setattr__(self, name, value)
 
 
+# The opt-in keywords of an fp64 context, in the order they are checked; mirrors f64_flags[] of csrc/fmj_hip.hip (include/fmj.h:
+# fmj_create_ex2, fmj_step_fused_f64).  Per keyword: its CREATE_F64_* bit of fmj_create_ext.flags (0: no create flag), the other keywords
+# it needs next to precision='fp64', what the ValueError says it needs, and the keywords it does not go with -> why.
+#   fp64_fused     fused launches go through fmj_step_fused_f64: rows and drag in double, the state rounded to fp32 only where a
+#                  launch ends, so results differ from the per-iteration fp64 path's
+#   fp64_limits    joint limits, solved by the kernel's primal Newton solve: limited swimmers past the sizes of the fp32 constraint path
+#   fp64_rk4       integrator = RK4, the four forward passes of a step inside the kernel, one launch for all steps of fmj_step; with
+#                  fp64_fused such a run fuses too
+#   fp64_contacts  ground contacts (sphere / capsule / box geoms against world planes, pyramidal cone) as more rows of the same Newton
+#                  solve: walking models past the sizes of the fp32 constraint path; fmj_step only, no fused launch, no RK4
+#   fp64_terrain   the contacts context also takes the world's heightfield as ground and cylinder geoms on the animat: its own
+#                  kernels, whose narrow phase carries a normal per contact; opt-in, also on flat ground
+_NEEDS_FP64 = "precision='fp64', not {precision!r}: "
+FP64_OPTIONS = {
+    'fp64_fused': (0, (), _NEEDS_FP64 + 'an fp32 context fuses through fmj_step_fused', {}),
+    'fp64_limits': (_lib.CREATE_F64_LIMITS, (), _NEEDS_FP64 + 'an fp32 context solves limits on its constraint path', {}),
+    'fp64_rk4': (_lib.CREATE_F64_RK4, (), _NEEDS_FP64 + 'an fp32 context integrates RK4 with four launches per step', {}),
+    'fp64_contacts': (_lib.CREATE_F64_CONTACTS, (), _NEEDS_FP64 + 'an fp32 context solves contacts on its constraint path',
+                      {'fp64_fused': 'fused contact rows are not built for the fp64 step', 'fp64_rk4': 'the fp64 contact solve integrates with Euler or implicitfast'}),
+    'fp64_terrain': (_lib.CREATE_F64_TERRAIN, ('fp64_contacts',), "precision='fp64' and fp64_contacts=True (not precision={precision!r}, "
+                     'fp64_contacts={fp64_contacts}): it widens the narrow phase of the fp64 contact solve', {}),
+}
+
+
 class BatchedPhysics:
     """Device-resident mjData for ``n_envs`` copies of one model + the HIP step context."""
 
@@ -45,39 +69,20 @@ class BatchedPhysics:
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
         # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
         # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
-        # fp64_fused: fused launches of an fp64 context go through fmj_step_fused_f64 (opt-in: rows and drag in double, the state
-        # rounded to fp32 only where a launch ends, so results differ from the per-iteration fp64 path's; include/fmj.h).
+        # fp64_*: the opt-in keywords of an fp64 context (FP64_OPTIONS above).
         if precision not in _lib.PRECISIONS:
             raise ValueError(f'precision must be one of {sorted(_lib.PRECISIONS)}, not {precision!r}')
-        if fp64_fused and precision != 'fp64':
-            raise ValueError(f"fp64_fused=True needs precision='fp64', not {precision!r}: an fp32 context fuses through fmj_step_fused")
-        # fp64_limits: the fp64 context takes joint limits, solved by the kernel's primal Newton solve (fmj_create_ex2,
-        # FMJ_CREATE_F64_LIMITS; include/fmj.h) - limited swimmers past the sizes of the fp32 constraint path.
-        if fp64_limits and precision != 'fp64':
-            raise ValueError(f"fp64_limits=True needs precision='fp64', not {precision!r}: an fp32 context solves limits on its constraint path")
-        # fp64_rk4: the fp64 context takes integrator = RK4 and runs the four forward passes of a step inside the kernel, one launch for
-        # all steps of fmj_step (fmj_create_ex2, FMJ_CREATE_F64_RK4; include/fmj.h); with fp64_fused such a run fuses too.
-        if fp64_rk4 and precision != 'fp64':
-            raise ValueError(f"fp64_rk4=True needs precision='fp64', not {precision!r}: an fp32 context integrates RK4 with four launches per step")
-        # fp64_contacts: the fp64 context takes ground contacts (sphere / capsule / box geoms against world planes, pyramidal cone) as
-        # more rows of the same Newton solve (fmj_create_ex2, FMJ_CREATE_F64_CONTACTS; include/fmj.h) - walking models past the
-        # sizes of the fp32 constraint path.  Such a context steps through fmj_step only: no fused launch, no RK4.
-        if fp64_contacts and precision != 'fp64':
-            raise ValueError(f"fp64_contacts=True needs precision='fp64', not {precision!r}: an fp32 context solves contacts on its constraint path")
-        if fp64_contacts and fp64_fused:
-            raise ValueError('fp64_contacts=True does not go with fp64_fused=True: fused contact rows are not built for the fp64 step')
-        if fp64_contacts and fp64_rk4:
-            raise ValueError('fp64_contacts=True does not go with fp64_rk4=True: the fp64 contact solve integrates with Euler or implicitfast')
-        # fp64_terrain: the contacts context also takes the world's heightfield as ground and cylinder geoms on the animat (fmj_create_ex2,
-        # FMJ_CREATE_F64_TERRAIN; include/fmj.h) - its own kernels, whose narrow phase carries a normal per contact: opt-in, also on flat ground.
-        if fp64_terrain and not (precision == 'fp64' and fp64_contacts):
-            raise ValueError(f"fp64_terrain=True needs precision='fp64' and fp64_contacts=True (not precision={precision!r}, fp64_contacts={bool(fp64_contacts)}): "
-                             'it widens the narrow phase of the fp64 contact solve')
-        self.fp64_terrain = bool(fp64_terrain)
-        self.fp64_contacts = bool(fp64_contacts)
-        self.fp64_fused = bool(fp64_fused)
-        self.fp64_limits = bool(fp64_limits)
-        self.fp64_rk4 = bool(fp64_rk4)
+        on = dict(fp64_fused=bool(fp64_fused), fp64_limits=bool(fp64_limits), fp64_rk4=bool(fp64_rk4), fp64_contacts=bool(fp64_contacts),
+                  fp64_terrain=bool(fp64_terrain))
+        ext_flags = 0
+        for name, (flag, needs, needs_text, excludes) in FP64_OPTIONS.items():
+            if on[name] and (precision != 'fp64' or not all(on[n] for n in needs)):
+                raise ValueError(f'{name}=True needs ' + needs_text.format(precision=precision, **on))
+            for other, reason in excludes.items():
+                if on[name] and on[other]:
+                    raise ValueError(f'{name}=True does not go with {other}=True: {reason}')
+            ext_flags |= flag if on[name] else 0
+        vars(self).update(on)      # self.fp64_fused, self.fp64_limits, ...
         if kernel is not None and not isinstance(kernel, KernelOptions):
             raise TypeError(f'kernel must be a KernelOptions or None, not {kernel!r}')
         if not torch.cuda.is_available():
@@ -100,11 +105,10 @@ class BatchedPhysics:
             flags = (k.two_wave * _lib.KERNEL_TWO_WAVE | (not k.two_env) * _lib.KERNEL_ONE_ENV_PER_WAVE |
                      (not k.lean) * _lib.KERNEL_NO_LEAN | (not k.prio) * _lib.KERNEL_NO_PRIO)
             opts = _lib.CCreateOptions(ctypes.sizeof(_lib.CCreateOptions), _lib.PRECISIONS[precision], flags, k.wps or 0)
-            if fp64_limits or fp64_rk4 or fp64_contacts:
+            if ext_flags:
                 if not _lib.has('fmj_create_ex2'):      # an A/B base build (FMJ_SO)
                     raise _lib.FmjError('this libfmj_hip.so has no fmj_create_ex2: fp64_limits=True / fp64_rk4=True / fp64_contacts=True need a current build')
-                ext = _lib.CCreateExt(ctypes.sizeof(_lib.CCreateExt), bool(fp64_limits) * _lib.CREATE_F64_LIMITS | bool(fp64_rk4) * _lib.CREATE_F64_RK4 |
-                                      bool(fp64_contacts) * _lib.CREATE_F64_CONTACTS | bool(fp64_terrain) * _lib.CREATE_F64_TERRAIN)
+                ext = _lib.CCreateExt(ctypes.sizeof(_lib.CCreateExt), ext_flags)
                 rc = self._lib.fmj_create_ex2(ctypes.byref(self._cmodel), self.n_envs, self.device.index or 0,
                                               ctypes.byref(opts), ctypes.byref(ext), ctypes.byref(ctx))
             else:

@@ -10,7 +10,7 @@ import torch
 from .. import _lib
 from ..model import Model
 from ..options import AnimatOptions, ArenaOptions, SimulationOptions
-from ..physics import BatchedPhysics, PhysicsError
+from ..physics import BatchedPhysics, PhysicsError, FP64_OPTIONS
 from .task import ExperimentTask, SwimmingCallback
 
 import logging
@@ -133,9 +133,7 @@ class Simulation:
         n_envs = kwargs.pop('n_envs', 1)
         device = kwargs.pop('device', 'cuda:0')
         self.physics = BatchedPhysics(mjcf_model, n_envs, device, precision=kwargs.pop('precision', 'fp32'), kernel=kwargs.pop('kernel', None),
-                                      fp64_fused=kwargs.pop('fp64_fused', False), fp64_limits=kwargs.pop('fp64_limits', False),
-                                      fp64_rk4=kwargs.pop('fp64_rk4', False), fp64_contacts=kwargs.pop('fp64_contacts', False),
-                                      fp64_terrain=kwargs.pop('fp64_terrain', False))
+                                      **{name: kwargs.pop(name, False) for name in FP64_OPTIONS})
         self.handle_exceptions = kwargs.pop('handle_exceptions', False)
         # dm_control raises PhysicsError inside the offending step; here the device freezes the offending env at that
         # step (include/fmj.h) and the host looks at the status words every `check_every` steps (one sync each)

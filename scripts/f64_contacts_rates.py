@@ -10,35 +10,11 @@ The runs of a model are sampled in turn, ``samples`` times (default 5) after two
 ground); the whole measurement is repeated ``repeats`` times (default 3) on fresh contexts.  Printed per model and repeat: the median
 rate of each run, its spread (min .. max over the samples), the mean contacts per env at the end and the ratio of the two runs; then
 per model the spread of the medians over the repeats."""
-import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-sys.path.insert(0, ROOT)
-
-
-def context(m, n, **kw):
-    import torch
-    import farms_mujoco_amd.model as mm
-    from farms_mujoco_amd.physics import BatchedPhysics
-    qpos, qvel, psi = mm.synthetic_batch(m, n, seed=0)
-    phys = BatchedPhysics(m, n, **kw)
-    phys.data.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32)
-    phys.data.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    return phys, psi
-
-
-def tape_of(m, psi, amp, lag, chunk, offset=None, f=1.0):
-    """ctrl[t, env, a] = offset_a + amp_a sin(2 pi f t + psi_env - lag_a) over one launch (the same tape every launch)."""
-    import torch
-    t = np.arange(chunk)[:, None, None]*m.timestep
-    tape = amp[None, None, :]*np.sin(2*np.pi*f*t + psi[None, :, None] - lag[None, None, :])
-    if offset is not None:
-        tape = tape + offset[None, None, :]
-    return torch.as_tensor(tape, dtype=torch.float32, device='cuda:0').contiguous()
+from f64_rates_common import context, tape_of, centipede_stance, sample, stepping, over_repeats
 
 
 def salamander_runs(n, chunk):
@@ -61,11 +37,7 @@ def centipede_runs(n, chunk):
     w, s = mm.centipede(20, 25, contacts=True), mm.centipede(20, 25)
     w.solver = mm.SOLVERS['newton']; w.solver_iterations = 100
     amp, lag = mm.wave_controller_params(w, amplitude=0.1)
-    stance = np.zeros(w.nu)
-    for a in range(w.nu):
-        name = w.joint_names[int(w.actuator_jntid[a])]
-        if name.startswith('joint_leg_') and name.endswith('_1'):
-            stance[a] = -0.25 if '_L_' in name else 0.25
+    stance = centipede_stance(w)
     pw, psi = context(w, n, precision='fp64', fp64_contacts=True)
     ps, _ = context(s, n, precision='fp64')
     amp_s, lag_s = mm.wave_controller_params(s, amplitude=0.3)
@@ -73,16 +45,8 @@ def centipede_runs(n, chunk):
 
 
 def rates(name, make_runs, n, samples, chunk=100):
-    import torch
     m, runs = make_runs(n, chunk)
-    out = {k: [] for k in runs}
-    for s in range(samples + 2):      # alternating samples; the first two passes warm up
-        for k, (phys, tape) in runs.items():
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            phys.step(chunk, tape)
-            torch.cuda.synchronize(); dt = time.perf_counter() - t0
-            if s > 1:
-                out[k].append(n*chunk/dt)
+    out = sample(stepping(runs, chunk), n, chunk, samples, warmup=2)      # (the animal settles on the ground)
     for phys, _ in runs.values():
         assert int((phys.data.status & 7).abs().sum()) == 0      # (a full contact list is reported, not an error)
     med = {k: float(np.median(v)) for k, v in out.items()}
@@ -99,6 +63,4 @@ if __name__ == '__main__':
     samples = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 3
     for name, make_runs in (('salamander33 walking', salamander_runs), ('centipede(20, 25)', centipede_runs)):
-        meds = [rates(name, make_runs, n, samples) for _ in range(repeats)]
-        print(f'{name}: medians over {repeats} runs: ' +
-              '; '.join(f'{k} {min(m[k] for m in meds)/1e6:.4f} .. {max(m[k] for m in meds)/1e6:.4f}' for k in meds[0]), flush=True)
+        over_repeats(name, lambda: rates(name, make_runs, n, samples), repeats, 4)

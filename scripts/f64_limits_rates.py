@@ -8,14 +8,11 @@ usage: python scripts/f64_limits_rates.py [n_envs] [samples]
 The three are sampled in turn, ``samples`` times (default 5) after one warm-up pass each; printed per model: the median rate of each
 and its spread (min .. max over the samples), the share of the engaged run's env-steps that ended with a limit force, and the two
 ratios to the rate without limits."""
-import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-sys.path.insert(0, ROOT)
+from f64_rates_common import sample
 
 
 def limited(make, lim, margin_even):
@@ -42,18 +39,11 @@ def rates(name, make, n, samples, chunk=100):
             'limits, never engaged': BatchedPhysics(limited(make, 10.0, 0.0), n, precision='fp64', fp64_limits=True),
             'limits engaged': BatchedPhysics(limited(make, 0.1, 0.01), n, precision='fp64', fp64_limits=True)}
     m = runs['no limits'].model
-    out = {k: [] for k in runs}
     engaged = []
     nl, njs = 6*(m.nbody - 1), m.n_sensor_joints
-    for s in range(samples + 1):      # alternating samples; the first pass warms up
-        ctrl = tape(m, n, s*chunk, chunk, runs['no limits'].device)
-        for k, phys in runs.items():
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            phys.step(chunk, ctrl)
-            torch.cuda.synchronize(); dt = time.perf_counter() - t0
-            if s:
-                out[k].append(n*chunk/dt)
-        engaged.append(float((runs['limits engaged'].data.sensordata[:, nl + 2:nl + 3*njs:3] != 0).any(dim=1).float().mean()))
+    out = sample({k: (lambda ctrl, p=p: p.step(chunk, ctrl)) for k, p in runs.items()}, n, chunk, samples,
+                 pass_input=lambda s: tape(m, n, s*chunk, chunk, runs['no limits'].device),
+                 each_pass=lambda s: engaged.append(float((runs['limits engaged'].data.sensordata[:, nl + 2:nl + 3*njs:3] != 0).any(dim=1).float().mean())))
     for phys in runs.values():
         assert int(phys.data.status.abs().sum()) == 0
     assert float(runs['limits, never engaged'].data.sensordata[:, nl + 2:nl + 3*njs:3].abs().max()) == 0

@@ -7,14 +7,11 @@ per step).  usage: python scripts/f64_rk4_rates.py [n_envs] [samples] [repeats]
 The runs of a model are sampled in turn, ``samples`` times (default 5) after one warm-up pass each; the whole measurement is repeated
 ``repeats`` times (default 3) on fresh contexts.  Printed per model and repeat: the median rate of each run and its spread (min .. max
 over the samples) and the ratios of RK4 to Euler; then per model the spread of the medians over the repeats."""
-import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-sys.path.insert(0, ROOT)
+from f64_rates_common import context, sample, over_repeats
 
 
 def with_integrator(make, name):
@@ -25,14 +22,7 @@ def with_integrator(make, name):
 
 
 def plain(m, n, **kw):
-    import torch
-    import farms_mujoco_amd.model as mm
-    from farms_mujoco_amd.physics import BatchedPhysics
-    qpos, qvel, _ = mm.synthetic_batch(m, n, seed=0)
-    phys = BatchedPhysics(m, n, **kw)
-    phys.data.qpos[:] = torch.as_tensor(qpos, dtype=torch.float32)
-    phys.data.qvel[:] = torch.as_tensor(qvel, dtype=torch.float32)
-    return phys
+    return context(m, n, **kw)[0]
 
 
 def swim(m, n, iterations, rk4):
@@ -55,27 +45,19 @@ def swim(m, n, iterations, rk4):
 
 
 def rates(name, make, n, samples, fp32_rk4, chunk=100):
-    import torch
     total = (samples + 1)*chunk
     euler, rk4 = with_integrator(make, 'euler'), with_integrator(make, 'rk4')
     p_eu, p_rk = plain(euler, n, precision='fp64'), plain(rk4, n, precision='fp64', fp64_rk4=True)
     s_eu, s_rk = swim(euler, n, total, False), swim(rk4, n, total, True)
     assert p_rk.kernel_info()['threads_per_env'] == 128
-    runs = {'fp64 Euler': lambda: p_eu.step(chunk), 'fp64 RK4': lambda: p_rk.step(chunk),
-            'fp64 Euler fused': lambda: s_eu.step_fused(chunk), 'fp64 RK4 fused': lambda: s_rk.step_fused(chunk)}
+    runs = {'fp64 Euler': lambda _: p_eu.step(chunk), 'fp64 RK4': lambda _: p_rk.step(chunk),
+            'fp64 Euler fused': lambda _: s_eu.step_fused(chunk), 'fp64 RK4 fused': lambda _: s_rk.step_fused(chunk)}
     checked = [p_eu, p_rk, s_eu.physics, s_rk.physics]
     if fp32_rk4:
         p32 = plain(rk4, n, precision='fp32')
-        runs['fp32 RK4 (8 launches per step)'] = lambda: p32.step(chunk)
+        runs['fp32 RK4 (8 launches per step)'] = lambda _: p32.step(chunk)
         checked.append(p32)
-    out = {k: [] for k in runs}
-    for s in range(samples + 1):      # alternating samples; the first pass warms up
-        for k, go in runs.items():
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            go()
-            torch.cuda.synchronize(); dt = time.perf_counter() - t0
-            if s:
-                out[k].append(n*chunk/dt)
+    out = sample(runs, n, chunk, samples)
     for phys in checked:
         assert int(phys.data.status.abs().sum()) == 0
     med = {k: float(np.median(v)) for k, v in out.items()}
@@ -92,6 +74,4 @@ if __name__ == '__main__':
     samples = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 3
     for name, make, fp32_rk4 in (('salamander33', mm.salamander33, True), ('centipede(20, 25)', lambda: mm.centipede(20, 25), False)):
-        meds = [rates(name, make, n, samples, fp32_rk4) for _ in range(repeats)]
-        print(f'{name}: medians over {repeats} runs: ' +
-              '; '.join(f'{k} {min(m[k] for m in meds)/1e6:.3f} .. {max(m[k] for m in meds)/1e6:.3f}' for k in meds[0]), flush=True)
+        over_repeats(name, lambda: rates(name, make, n, samples, fp32_rk4), repeats, 3)

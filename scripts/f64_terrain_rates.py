@@ -10,17 +10,11 @@ The three runs are sampled in turn, ``samples`` times (default 5) after two warm
 the whole measurement is repeated ``repeats`` times (default 3) on fresh contexts.  Printed per repeat: the median rate of each run,
 its spread (min .. max over the samples), the mean contacts per env at the end and each run's ratio to the first; then the spread of
 the medians over the repeats."""
-import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from f64_contacts_rates import context, tape_of      # noqa: E402
+from f64_rates_common import context, tape_of, centipede_stance, sample, stepping, over_repeats
 
 
 def centipede_runs(n, chunk):
@@ -32,11 +26,7 @@ def centipede_runs(n, chunk):
         return w
     w = walker('plane')
     amp, lag = mm.wave_controller_params(w, amplitude=0.1)
-    stance = np.zeros(w.nu)
-    for a in range(w.nu):
-        name = w.joint_names[int(w.actuator_jntid[a])]
-        if name.startswith('joint_leg_') and name.endswith('_1'):
-            stance[a] = -0.25 if '_L_' in name else 0.25
+    stance = centipede_stance(w)
     runs = {}
     for key, terrain, flag in (('plane, contacts kernel', 'plane', False), ('plane, terrain kernel', 'plane', True),
                                ('heightfield, terrain kernel', 'hfield', True)):
@@ -47,16 +37,8 @@ def centipede_runs(n, chunk):
 
 
 def rates(name, n, samples, chunk=100):
-    import torch
     m, runs = centipede_runs(n, chunk)
-    out = {k: [] for k in runs}
-    for s in range(samples + 2):      # alternating samples; the first two passes warm up
-        for k, (phys, tape) in runs.items():
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            phys.step(chunk, tape)
-            torch.cuda.synchronize(); dt = time.perf_counter() - t0
-            if s > 1:
-                out[k].append(n*chunk/dt)
+    out = sample(stepping(runs, chunk), n, chunk, samples, warmup=2)      # (the animal settles on the ground)
     for phys, _ in runs.values():
         assert int((phys.data.status & 7).abs().sum()) == 0      # (a full contact list is reported, not an error)
     med = {k: float(np.median(v)) for k, v in out.items()}
@@ -72,6 +54,4 @@ if __name__ == '__main__':
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     samples = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 3
-    meds = [rates('centipede(20, 25) walking', n, samples) for _ in range(repeats)]
-    print(f'centipede(20, 25) walking: medians over {repeats} runs: ' +
-          '; '.join(f'{k} {min(m[k] for m in meds)/1e6:.4f} .. {max(m[k] for m in meds)/1e6:.4f}' for k in meds[0]), flush=True)
+    over_repeats('centipede(20, 25) walking', lambda: rates('centipede(20, 25) walking', n, samples), repeats, 4)

@@ -216,3 +216,52 @@ def walk_tape(m, n, T, f=2.0, spine=0.1, legs=0.1, stance=0.25):
         elif nm.endswith('_1'):
             tape[:, :, a] = -stance if '_L_' in nm else stance
     return tape.astype(np.float32)
+
+
+STATE = ('qpos', 'qvel', 'qacc', 'qacc_warmstart', 'sensordata', 'xpos', 'xquat', 'xipos')
+
+
+def _groups(m):
+    import support_f64_step as S
+    g = S._field_groups(m)
+    g['qacc_warmstart'] = g['qacc']
+    return g
+
+
+def _contact_groups():
+    """Columns of one physical kind in a contact record: position, frame, force."""
+    return [np.arange(0, 3), np.arange(3, 12), np.arange(12, 15)]
+
+
+def _contact_excess(got16, ncon_got, ref):
+    """ulp excess of the records (pos, frame, force) of every env's contacts, the groups taken per env over its contacts."""
+    import support_f64_step as S
+    worst = 0.0
+    for e in range(len(ncon_got)):
+        k = int(ref['ncon'][e])
+        if k == 0:
+            continue
+        g, r = got16[e, :k, :15].astype(np.float64), ref['contact'][e, :k]
+        for cols in _contact_groups():
+            worst = max(worst, S.ulp_excess(g[None, :, cols], r[None, :, cols]))
+    return worst
+
+
+def _excess(m, p, ref, forward, ins):
+    import support_f64_step as S
+    import torch
+    torch.cuda.synchronize()
+    assert int(p.data.status.abs().sum()) == 0
+    if forward:
+        ref = dict(ref, qpos=ins['qpos'], qvel=ins['qvel'])
+    groups = _groups(m)
+    fields = [k for k in STATE if not (forward and k == 'qacc_warmstart')]      # (mj_forward saves no warm start)
+    ex = {k: S.ulp_excess(getattr(p.data, k).cpu().numpy(), ref[k], groups[k]) for k in fields}
+    ncon = p.data.ncon.cpu().numpy()
+    assert np.array_equal(ncon, ref['ncon']), (ncon, ref['ncon'])
+    c16 = p.data.contact.cpu().numpy()
+    for e in range(len(ncon)):
+        gg = np.ascontiguousarray(c16[e, :ncon[e], 15]).view(np.int32)
+        assert np.array_equal(gg >> 16, ref['geoms'][e, :ncon[e], 0]) and np.array_equal(gg & 0xffff, ref['geoms'][e, :ncon[e], 1]), e
+    ex['contact'] = _contact_excess(c16, ncon, ref)
+    return ex

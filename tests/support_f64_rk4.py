@@ -12,7 +12,7 @@ FIELDS = ('qpos', 'qvel', 'qacc', 'xpos', 'xquat', 'xipos', 'sensordata')
 
 def rk4_model(name):
     """A model of test_gpu_f64_step.MODELS, unconstrained, integrating with RK4."""
-    import test_gpu_f64_step as S
+    import support_f64_step as S
     m = S._make(name)
     m.integrator = RK4
     return m

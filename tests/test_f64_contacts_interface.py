@@ -2,38 +2,25 @@
 fmj_step_f64_contacts_kernel) as far as it can be checked without a GPU: the flag and what it leaves alone, every acceptance and every
 refusal (decided before the device lookup), the Python arguments, the centipede's walking variant, and the compiler's resource remarks
 for the two new kernels."""
-import copy
 import ctypes
 import inspect
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from support_capi import lib as _lib, create_ex as _create_ex, no_gpu as _no_gpu, F32, F64, FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED, FMJ_ERR_NODEVICE
-from test_f64_limits_interface import _create_ex2
+from support_capi import lib as _lib, create_ex as _create_ex, F32, FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED
+from support_f64_interface import create_ex2 as _create_ex2, accepted as _accepted, SRC, F64_CT, lds_bytes, resource_remarks, within_resources
 from support_f64_contacts import CONTACTS, LIMITS, RK4, GEOM_PLANE, make, boxfoot, set_geoms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F64_CT = 33      # doubles of LDS per contact (csrc/fmj_f64.inc)
-
-
-def _accepted(rc, msg, prec):
-    """Every model check passed: without a GPU the first thing that fails is the device lookup."""
-    return rc == FMJ_ERR_NODEVICE if _no_gpu() else (rc == 0 and prec == F64)
 
 
 def _walker():
     from farms_mujoco_amd.model import salamander33
     return salamander33(contacts=True)
-
-
-def _lds_bytes(nb, nv, nq, rs, max_contacts):
-    """ldsd_contacts_bytes of csrc/fmj_f64.inc: the map, the LIMITS block, F64_CT doubles per contact."""
-    return 8*(((nq + 1) & ~1) + 2*((nv + 1) & ~1) + 2*128*8 + nv*6 + nb*(10 + 10 + 6 + 6 + 4) + nv*rs + 128 + 4 + 20 + F64_CT*max_contacts)
 
 
 def test_the_flag_is_32_and_the_abi_stays():
@@ -112,11 +99,11 @@ def test_the_lds_corner():
     unit = (1.0, 0.0, 0.0, 0.0)
     geoms = [(GEOM_PLANE, 0, (0, 0, 0), (0, 0, 0), unit, 0.0)] + [(2, b, (0.02, 0, 0), (0, 0, 0), unit, 1.0) for b in range(1, 128)]
     set_geoms(m, geoms, 128)
-    need = _lds_bytes(128, 128, 129, 64, 128)
+    need = lds_bytes('contacts', 128, 128, 129, 64, 128)
     assert need <= 160*1024, need
     rc, msg, prec, _ = _create_ex2(m, flags=CONTACTS)
     assert _accepted(rc, msg, prec), (rc, msg)
-    assert _lds_bytes(107, 111, 112, 36, 92) <= 160*1024      # centipede(20, 25, contacts=True)
+    assert lds_bytes('contacts', 107, 111, 112, 36, 92) <= 160*1024      # centipede(20, 25, contacts=True)
 
 
 def test_without_the_flag_the_refusals_stay_word_for_word():
@@ -174,30 +161,10 @@ def test_contacts_kernels_compile_without_scratch(tmp_path):
     """The translation unit of the contacts kernels (-DFMJ_TU_F64=4) with the flags of _lib.build() holds exactly two kernels,
     fmj_step_f64_contacts_kernel<LIMITS>; both keep out of scratch, spill no VGPR, and their LDS at the size limits (nbody = nv = 128,
     dof chain 64, 128 contacts: ldsd_contacts_bytes of fmj_f64.inc) is within 160 KB."""
-    src = os.path.join(ROOT, 'farms_mujoco_amd', 'csrc', 'fmj_hip.hip')
-    flags = ['--offload-arch=gfx950', '-O3', '-fno-slp-vectorize', '-mllvm', '-pragma-unroll-threshold=131072', '-fPIC', '-DFMJ_TU_F64=4']
-    r = subprocess.run(['hipcc'] + flags + ['-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', str(tmp_path/'kf64c.o')],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kern, res = None, {}
-    for line in r.stderr.splitlines():
-        mm = re.search(r'remark:\s+(.*?) \[-Rpass', line)
-        if not mm:
-            continue
-        t = mm.group(1).strip()
-        if t.startswith('Function Name:'):
-            kern = t.split(':', 1)[1].strip()
-            res[kern] = {}
-        elif kern:
-            k, v = t.split(':', 1)
-            res[kern][k.strip()] = v.strip()
+    res = resource_remarks('-DFMJ_TU_F64=4', tmp_path)
     ck = {k: v for k, v in res.items() if re.search(r'fmj_step_f64_contacts_kernelILb[01]EE', k)}
     assert len(res) == 2 and len(ck) == 2, sorted(res)
     from farms_mujoco_amd import _lib as L
-    inc = open(os.path.join(os.path.dirname(src), 'fmj_f64.inc')).read()
+    inc = open(os.path.join(os.path.dirname(SRC), 'fmj_f64.inc')).read()
     assert "'-DFMJ_TU_F64=4'" in inspect.getsource(L.build) and f'#define F64_CT {F64_CT} ' in inc and 'F64_LIMITS_LDS_DOUBLES 20' in inc
-    dyn = _lds_bytes(128, 128, 129, 64, 128)
-    for k, v in ck.items():
-        print(k, v)
-        assert v['ScratchSize [bytes/lane]'] == '0' and v['VGPRs Spill'] == '0', (k, v)
-        assert int(v['LDS Size [bytes/block]']) + dyn <= 160*1024, (k, v, dyn)
+    within_resources(ck, lds_bytes('contacts', 128, 128, 129, 64, 128))

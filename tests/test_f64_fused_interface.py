@@ -6,11 +6,11 @@ import inspect
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
 from support_capi import lib as _lib, FMJ_ERR_ARG
+from support_f64_interface import BUILD_FLAGS, lds_bytes, resource_remarks, within_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -74,34 +74,11 @@ def test_both_fp64_kernels_compile_without_scratch(tmp_path):
     """The fp64 translation unit with the flags of _lib.build() holds two kernels, the plain step and the fused loop; neither uses
     scratch or spills a VGPR, and the static LDS plus the largest dynamic request (ldsd_layout(128, 128, 129, 64) of fmj_f64.inc: the
     fused loop adds nothing to it) fits gfx950's 160 KB per workgroup."""
-    src = os.path.join(ROOT, 'farms_mujoco_amd', 'csrc', 'fmj_hip.hip')
     from farms_mujoco_amd import _lib as L
-    flags = ['--offload-arch=gfx950', '-O3', '-fno-slp-vectorize', '-mllvm', '-pragma-unroll-threshold=131072', '-fPIC']
-    assert repr(flags)[:-1] in inspect.getsource(L.build) and "'-DFMJ_TU_F64'" in inspect.getsource(L.build), 'build() compiles with other flags: restate them here'
-    flags.append('-DFMJ_TU_F64')
-    r = subprocess.run(['hipcc'] + flags + ['-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', str(tmp_path/'kf64.o')],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kern, res = None, {}
-    for line in r.stderr.splitlines():
-        mm = re.search(r'remark:\s+(.*?) \[-Rpass', line)
-        if not mm:
-            continue
-        t = mm.group(1).strip()
-        if t.startswith('Function Name:'):
-            kern = t.split(':', 1)[1].strip()
-            res[kern] = {}
-        elif kern:
-            k, v = t.split(':', 1)
-            res[kern][k.strip()] = v.strip()
+    assert repr(BUILD_FLAGS)[:-1] in inspect.getsource(L.build) and "'-DFMJ_TU_F64'" in inspect.getsource(L.build), 'build() compiles with other flags: restate them in support_f64_interface'
+    res = resource_remarks('-DFMJ_TU_F64', tmp_path)
     assert len(res) == 2 and all('f64' in k for k in res), sorted(res)
-    # ldsd_layout(nb, nv, nq, rs) of fmj_f64.inc, in doubles
-    nb, nv, nq, rs = 128, 128, 129, 64
-    dyn = 8*(((nq + 1) & ~1) + 2*((nv + 1) & ~1) + 2*128*8 + nv*6 + nb*(10 + 10 + 6 + 6 + 4) + nv*rs + 128 + 4)
     layout = open(os.path.join(ROOT, 'farms_mujoco_amd', 'csrc', 'fmj_f64.inc')).read()
     layout = layout[layout.index('inline LdsLayoutD ldsd_layout'):layout.index('L.total_bytes = o * 8;')]
-    assert layout.count('o +=') == 13, 'ldsd_layout changed: restate its sum here'      # the thirteen regions summed above
-    for k, v in res.items():
-        print(k, v)
-        assert v['ScratchSize [bytes/lane]'] == '0' and v['VGPRs Spill'] == '0', (k, v)
-        assert int(v['LDS Size [bytes/block]']) + dyn <= 160*1024, (k, v, dyn)
+    assert layout.count('o +=') == 13, 'ldsd_layout changed: restate its sum in support_f64_interface.lds_bytes'      # the thirteen regions summed there
+    within_resources(res, lds_bytes('plain', 128, 128, 129, 64))

@@ -1,18 +1,16 @@
 """The opt-in fp64 step (fmj_create_ex with FMJ_PRECISION_F64, csrc/fmj_f64.inc) as far as it can be checked without a GPU: the two
 new entry points, what an fp64 context refuses (before the device lookup, with 'fp64' in the message), the Python arguments, and the
 compiler's resource remarks for the kernel (hipcc cross-compiles)."""
-import ctypes
 import inspect
 import os
-import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from support_capi import (lib as _lib, create_ex as _create_ex, no_gpu as _no_gpu, F32, F64, FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED,
                           FMJ_ERR_NODEVICE)
+from support_f64_interface import lds_bytes, resource_remarks, within_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -102,29 +100,9 @@ def test_fp64_kernel_compiles_without_scratch(tmp_path):
     """The fp64 translation unit with the flags of _lib.build(): every fp64 step kernel keeps out of scratch (no private array is
     indexed at run time), spills no VGPR, and its LDS - the largest dynamic request of the size limits plus the static part the
     compiler reports - is within gfx950's 160 KB per workgroup."""
-    src = os.path.join(ROOT, 'farms_mujoco_amd', 'csrc', 'fmj_hip.hip')
-    flags = ['--offload-arch=gfx950', '-O3', '-fno-slp-vectorize', '-mllvm', '-pragma-unroll-threshold=131072', '-fPIC', '-DFMJ_TU_F64']
-    r = subprocess.run(['hipcc'] + flags + ['-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', str(tmp_path/'kf64.o')],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kern, res = None, {}
-    for line in r.stderr.splitlines():
-        mm = re.search(r'remark:\s+(.*?) \[-Rpass', line)
-        if not mm:
-            continue
-        t = mm.group(1).strip()
-        if t.startswith('Function Name:'):
-            kern = t.split(':', 1)[1].strip()
-            res[kern] = {}
-        elif kern:
-            k, v = t.split(':', 1)
-            res[kern][k.strip()] = v.strip()
+    res = resource_remarks('-DFMJ_TU_F64', tmp_path)
     f64 = {k: v for k, v in res.items() if 'f64' in k}
     assert f64 and all('fmj_step_wide_kernel' not in k for k in res), sorted(res)
     assert sorted(res) == sorted(f64), sorted(res)          # the translation unit holds nothing else
     # the kernel's dynamic LDS at the size limits: 128 bodies, 128 dofs (nq 129), rows of 64 doubles (ldsd_layout of fmj_f64.inc)
-    nb, nv, nq, rs = 128, 128, 129, 64
-    dyn = 8*(((nq + 1) & ~1) + 2*((nv + 1) & ~1) + 2*128*8 + nv*6 + nb*(10 + 10 + 6 + 6 + 4) + nv*rs + 128 + 4)
-    for k, v in f64.items():
-        assert v['ScratchSize [bytes/lane]'] == '0' and v['VGPRs Spill'] == '0', (k, v)
-        assert int(v['LDS Size [bytes/block]']) + dyn <= 160*1024, (k, v, dyn)
+    within_resources(f64, lds_bytes('plain', 128, 128, 129, 64))

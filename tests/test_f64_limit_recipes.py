@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import support_limits as L
-from test_gpu_f64_step import ulp_excess, _field_groups
+from support_f64_step import ulp_excess, _field_groups
 
 N, MODELS = L.N, L.RECIPE_MODELS
 recipe_inputs, undamped_inputs = L.recipe_inputs, L.undamped_inputs

@@ -6,37 +6,15 @@ import inspect
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from support_capi import lib as _lib, create_ex as _create_ex, no_gpu as _no_gpu, F32, F64, FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED, FMJ_ERR_NODEVICE
+from support_f64_interface import (create_ex2 as _create_ex2, limited_eel48 as _limited_eel48, LIMITS, SRC, lds_bytes, resource_remarks,
+                                   within_resources)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIMITS = 1      # FMJ_CREATE_F64_LIMITS
-
-
-def _create_ex2(m, precision=F64, flags=LIMITS, size=None, ext=True):
-    """fmj_create_ex2(m, 4 envs, options, ext) and destroy: the return code, the message, the precision and the solver the context reports."""
-    L, so = _lib()
-    c = m.as_c(); ctx = ctypes.c_void_p()
-    opts = L.CCreateOptions(ctypes.sizeof(L.CCreateOptions), precision, 0, 0)
-    e = L.CCreateExt(ctypes.sizeof(L.CCreateExt) if size is None else size, flags)
-    rc = so.fmj_create_ex2(ctypes.byref(c), 4, 0, ctypes.byref(opts), ctypes.byref(e) if ext else None, ctypes.byref(ctx))
-    prec = solver = None
-    if rc == 0:
-        prec = so.fmj_precision(ctx); solver = L.ints(so.fmj_solver_info, ctx)
-        so.fmj_destroy(ctx)
-    return rc, so.fmj_last_error().decode(), prec, solver
-
-
-def _limited_eel48():
-    from farms_mujoco_amd.model import eel
-    m = eel(n_joints=48)
-    m.jnt_limited = np.ones_like(m.jnt_limited)
-    m.jnt_range = np.tile([-0.1, 0.1], (m.njnt, 1)).astype(float)
-    return m
 
 
 def test_entry_point_and_struct_sizes():
@@ -122,29 +100,9 @@ def test_limits_instantiations_compile_without_scratch(tmp_path):
     """The translation unit of the LIMITS instantiations (-DFMJ_TU_F64=2) with the flags of _lib.build() holds two kernels, the plain
     step and the fused loop; both keep out of scratch, spill no VGPR, and their LDS at the size limits (ldsd_total_bytes of
     fmj_f64.inc: F64_LIMITS_LDS_DOUBLES = 20 doubles past ldsd_layout) is within 160 KB."""
-    src = os.path.join(ROOT, 'farms_mujoco_amd', 'csrc', 'fmj_hip.hip')
-    flags = ['--offload-arch=gfx950', '-O3', '-fno-slp-vectorize', '-mllvm', '-pragma-unroll-threshold=131072', '-fPIC', '-DFMJ_TU_F64=2']
-    r = subprocess.run(['hipcc'] + flags + ['-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', str(tmp_path/'kf64.o')],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kern, res = None, {}
-    for line in r.stderr.splitlines():
-        mm = re.search(r'remark:\s+(.*?) \[-Rpass', line)
-        if not mm:
-            continue
-        t = mm.group(1).strip()
-        if t.startswith('Function Name:'):
-            kern = t.split(':', 1)[1].strip()
-            res[kern] = {}
-        elif kern:
-            k, v = t.split(':', 1)
-            res[kern][k.strip()] = v.strip()
+    res = resource_remarks('-DFMJ_TU_F64=2', tmp_path)
     lim = {k: v for k, v in res.items() if re.search(r'fmj_step_f64_kernelILb[01]ELb1EE', k)}      # <FUSED, LIMITS = true>
     assert len(res) == 2 and len(lim) == 2, sorted(res)
     from farms_mujoco_amd import _lib as L
-    assert "'-DFMJ_TU_F64=2'" in inspect.getsource(L.build) and 'F64_LIMITS_LDS_DOUBLES 20' in open(os.path.join(os.path.dirname(src), 'fmj_f64.inc')).read()
-    nb, nv, nq, rs = 128, 128, 129, 64
-    dyn = 8*(((nq + 1) & ~1) + 2*((nv + 1) & ~1) + 2*128*8 + nv*6 + nb*(10 + 10 + 6 + 6 + 4) + nv*rs + 128 + 4 + 20)
-    for k, v in lim.items():
-        assert v['ScratchSize [bytes/lane]'] == '0' and v['VGPRs Spill'] == '0', (k, v)
-        assert int(v['LDS Size [bytes/block]']) + dyn <= 160*1024, (k, v, dyn)
+    assert "'-DFMJ_TU_F64=2'" in inspect.getsource(L.build) and 'F64_LIMITS_LDS_DOUBLES 20' in open(os.path.join(os.path.dirname(SRC), 'fmj_f64.inc')).read()
+    within_resources(lim, lds_bytes('limits', 128, 128, 129, 64))

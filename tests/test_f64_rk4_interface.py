@@ -6,26 +6,20 @@ import inspect
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
-from support_capi import lib as _lib, create_ex as _create_ex, no_gpu as _no_gpu, F32, F64, FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED, FMJ_ERR_NODEVICE
-from test_f64_limits_interface import _create_ex2, _limited_eel48
+from support_capi import lib as _lib, create_ex as _create_ex, F32, FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED
+from support_f64_interface import (create_ex2 as _create_ex2, limited_eel48 as _limited_eel48, accepted as _accepted, LIMITS, RK4, SRC,
+                                   lds_bytes, resource_remarks, within_resources)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIMITS, RK4 = 1, 8      # FMJ_CREATE_F64_LIMITS, FMJ_CREATE_F64_RK4
 
 
 def _rk4(m):
     from farms_mujoco_amd.model import INTEGRATORS
     m.integrator = INTEGRATORS['rk4']
     return m
-
-
-def _accepted(rc, msg, prec):
-    """Every model check passed: without a GPU the first thing that fails is the device lookup."""
-    return rc == FMJ_ERR_NODEVICE if _no_gpu() else (rc == 0 and prec == F64)
 
 
 def test_the_flag_is_8_and_the_abi_stays():
@@ -110,31 +104,10 @@ def test_rk4_kernels_compile_without_scratch(tmp_path):
     """The translation unit of the RK4 kernels (-DFMJ_TU_F64=3) with the flags of _lib.build() holds exactly four kernels,
     fmj_step_f64_rk4_kernel<FUSED, LIMITS>; all keep out of scratch, spill no VGPR, and their LDS at the size limits (ldsd_total_bytes
     with limits + F64_RK4_LDS_DOUBLES(nu) of fmj_f64.inc, nu = 128: 2 nu doubles and 12 rows of one double per lane) is within 160 KB."""
-    src = os.path.join(ROOT, 'farms_mujoco_amd', 'csrc', 'fmj_hip.hip')
-    flags = ['--offload-arch=gfx950', '-O3', '-fno-slp-vectorize', '-mllvm', '-pragma-unroll-threshold=131072', '-fPIC', '-DFMJ_TU_F64=3']
-    r = subprocess.run(['hipcc'] + flags + ['-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', str(tmp_path/'kf64r.o')],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kern, res = None, {}
-    for line in r.stderr.splitlines():
-        mm = re.search(r'remark:\s+(.*?) \[-Rpass', line)
-        if not mm:
-            continue
-        t = mm.group(1).strip()
-        if t.startswith('Function Name:'):
-            kern = t.split(':', 1)[1].strip()
-            res[kern] = {}
-        elif kern:
-            k, v = t.split(':', 1)
-            res[kern][k.strip()] = v.strip()
+    res = resource_remarks('-DFMJ_TU_F64=3', tmp_path)
     rk = {k: v for k, v in res.items() if re.search(r'fmj_step_f64_rk4_kernelILb[01]ELb[01]EE', k)}
     assert len(res) == 4 and len(rk) == 4, sorted(res)
     from farms_mujoco_amd import _lib as L
-    inc = open(os.path.join(os.path.dirname(src), 'fmj_f64.inc')).read()
+    inc = open(os.path.join(os.path.dirname(SRC), 'fmj_f64.inc')).read()
     assert "'-DFMJ_TU_F64=3'" in inspect.getsource(L.build) and 'F64_RK4_LDS_DOUBLES(nu) (2 * (nu) + F64_RK4_ROWS * FMJ_F64_LANES)' in inc and 'F64_RK4_ROWS = 12' in inc and 'F64_LIMITS_LDS_DOUBLES 20' in inc
-    nb, nv, nq, rs, nu = 128, 128, 129, 64, 128
-    dyn = 8*(((nq + 1) & ~1) + 2*((nv + 1) & ~1) + 2*128*8 + nv*6 + nb*(10 + 10 + 6 + 6 + 4) + nv*rs + 128 + 4 + 20 + 2*nu + 12*128)
-    for k, v in rk.items():
-        print(k, v)
-        assert v['ScratchSize [bytes/lane]'] == '0' and v['VGPRs Spill'] == '0', (k, v)
-        assert int(v['LDS Size [bytes/block]']) + dyn <= 160*1024, (k, v, dyn)
+    within_resources(rk, lds_bytes('rk4', 128, 128, 129, 64, nu=128))

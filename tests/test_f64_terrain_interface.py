@@ -7,28 +7,17 @@ import inspect
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from support_capi import lib as _lib, no_gpu as _no_gpu, F32, F64, FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED, FMJ_ERR_NODEVICE
-from test_f64_limits_interface import _create_ex2
+from support_capi import lib as _lib, F32, FMJ_ERR_ARG, FMJ_ERR_UNSUPPORTED
+from support_f64_interface import (create_ex2 as _create_ex2, accepted as _accepted, SRC, BUILD_FLAGS, F64_CT, F64_TN, lds_bytes, resource_remarks,
+                                   within_resources)
 from support_f64_contacts import CONTACTS, LIMITS, RK4, GEOM_PLANE, GEOM_SPHERE, set_geoms
 from support_f64_terrain import TERRAIN, GEOM_CYLINDER, GEOM_HFIELD, make, flags_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F64_CT, F64_TN = 33, 3      # doubles of LDS per contact: the contacts kernels' record, the terrain kernels' normal past it (csrc/fmj_f64.inc)
-
-
-def _accepted(rc, msg, prec):
-    """Every model check passed: without a GPU the first thing that fails is the device lookup."""
-    return rc == FMJ_ERR_NODEVICE if _no_gpu() else (rc == 0 and prec == F64)
-
-
-def _lds_bytes(nb, nv, nq, rs, max_contacts):
-    """ldsd_terrain_bytes of csrc/fmj_f64.inc: the map, the LIMITS block, F64_CT + F64_TN doubles per contact."""
-    return 8*(((nq + 1) & ~1) + 2*((nv + 1) & ~1) + 2*128*8 + nv*6 + nb*(10 + 10 + 6 + 6 + 4) + nv*rs + 128 + 4 + 20 + (F64_CT + F64_TN)*max_contacts)
 
 
 def _three():
@@ -126,7 +115,7 @@ def test_the_lds_corner_names_its_bytes():
         assert (m.nbody, m.nv, m.nq) == (128, 128, 129)
         set_geoms(m, [(GEOM_PLANE, 0, (0, 0, 0), (0, 0, 0), unit, 0.0)] + [(GEOM_SPHERE, b, (0.02, 0, 0), (0, 0, 0), unit, 1.0) for b in range(1, 128)],
                   max_contacts)
-        need = _lds_bytes(128, 128, 129, 64, max_contacts)
+        need = lds_bytes('terrain', 128, 128, 129, 64, max_contacts)
         assert (need <= 160*1024) == fits, (max_contacts, need)
         rc, msg, prec, _ = _create_ex2(m, flags=CONTACTS | TERRAIN)
         if fits:
@@ -135,7 +124,7 @@ def test_the_lds_corner_names_its_bytes():
             assert rc == FMJ_ERR_UNSUPPORTED and 'FMJ_CREATE_F64_TERRAIN' in msg and str(need) in msg and 'LDS' in msg, (rc, msg, need)
             rc, msg, prec, _ = _create_ex2(m, flags=CONTACTS)
             assert _accepted(rc, msg, prec), (rc, msg)
-    assert _lds_bytes(107, 111, 112, 36, 92) <= 160*1024      # centipede(20, 25, contacts=True, terrain='hfield')
+    assert lds_bytes('terrain', 107, 111, 112, 36, 92) <= 160*1024      # centipede(20, 25, contacts=True, terrain='hfield')
 
 
 def test_python_takes_fp64_terrain():
@@ -193,33 +182,14 @@ def test_terrain_kernels_compile_without_scratch(tmp_path):
     """The translation unit of the terrain kernels (-DFMJ_TU_F64=5) with the flags of _lib.build() holds exactly two kernels,
     fmj_step_f64_terrain_kernel<LIMITS>; both keep out of scratch, spill no VGPR, and their LDS at the largest model the create check
     admits (nbody = nv = 128, dof chain 64, 120 contacts: ldsd_terrain_bytes of fmj_f64.inc) is within 160 KB."""
-    src = os.path.join(ROOT, 'farms_mujoco_amd', 'csrc', 'fmj_hip.hip')
-    flags = ['--offload-arch=gfx950', '-O3', '-fno-slp-vectorize', '-mllvm', '-pragma-unroll-threshold=131072', '-fPIC', '-DFMJ_TU_F64=5']
-    r = subprocess.run(['hipcc'] + flags + ['-Rpass-analysis=kernel-resource-usage', '-c', src, '-o', str(tmp_path/'kf64t.o')],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    kern, res = None, {}
-    for line in r.stderr.splitlines():
-        mm = re.search(r'remark:\s+(.*?) \[-Rpass', line)
-        if not mm:
-            continue
-        t = mm.group(1).strip()
-        if t.startswith('Function Name:'):
-            kern = t.split(':', 1)[1].strip()
-            res[kern] = {}
-        elif kern:
-            k, v = t.split(':', 1)
-            res[kern][k.strip()] = v.strip()
+    res = resource_remarks('-DFMJ_TU_F64=5', tmp_path)
     ck = {k: v for k, v in res.items() if re.search(r'fmj_step_f64_terrain_kernelILb[01]EE', k)}
     assert len(res) == 2 and len(ck) == 2, sorted(res)
     from farms_mujoco_amd import _lib as L
-    inc = open(os.path.join(os.path.dirname(src), 'fmj_f64.inc')).read()
-    assert repr(flags[:-1])[:-1] in inspect.getsource(L.build) and "'-DFMJ_TU_F64=5'" in inspect.getsource(L.build)
+    inc = open(os.path.join(os.path.dirname(SRC), 'fmj_f64.inc')).read()
+    assert repr(BUILD_FLAGS)[:-1] in inspect.getsource(L.build) and "'-DFMJ_TU_F64=5'" in inspect.getsource(L.build)
     assert f'#define F64_CT {F64_CT} ' in inc and f'#define F64_TN {F64_TN} ' in inc and 'F64_LIMITS_LDS_DOUBLES 20' in inc
     assert 'kf64t:-DFMJ_TU_F64=5' in open(os.path.join(ROOT, 'scripts', 'device_listing.sh')).read()
-    dyn = _lds_bytes(128, 128, 129, 64, 120)
-    assert dyn <= 160*1024 < _lds_bytes(128, 128, 129, 64, 121)
-    for k, v in ck.items():
-        print(k, v)
-        assert v['ScratchSize [bytes/lane]'] == '0' and v['VGPRs Spill'] == '0', (k, v)
-        assert int(v['LDS Size [bytes/block]']) + dyn <= 160*1024, (k, v, dyn)
+    dyn = lds_bytes('terrain', 128, 128, 129, 64, 120)
+    assert dyn <= 160*1024 < lds_bytes('terrain', 128, 128, 129, 64, 121)
+    within_resources(ck, dyn)

@@ -209,7 +209,7 @@ def test_network_drives_the_two_wave_kernel_through_the_api(oracle):
 def test_network_drives_the_fp64_fused_step_through_the_api(oracle):
     """The same on eel(48) with precision='fp64', fp64_fused=True, with the helpers and bounds of the ctrl-tape case of
     tests/test_gpu_f64_fused.py (test_ctrl_tape_one_row_per_iteration)."""
-    import test_gpu_f64_fused as F
+    import support_f64_fused as F
     n, steps = 4, 40
     twins = _Twins(n)
     sim = F._sim('eel48', n, steps, controller_of=twins)

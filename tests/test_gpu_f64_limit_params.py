@@ -14,7 +14,7 @@ import pytest
 from parity_metrics import relerr
 from wide_trees import dof_depth
 import support_limits as L
-from test_gpu_f64_step import ulp_excess, _field_groups
+from support_f64_step import ulp_excess, _field_groups
 
 pytestmark = pytest.mark.gpu
 

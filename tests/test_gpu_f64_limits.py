@@ -16,7 +16,7 @@ import pytest
 from parity_metrics import relerr
 from support_sims import swim_sim, wave_at, load_batch
 from support_limits import (limited as _limited, scalar_q as _scalar_q, engaged_inputs as _engaged_inputs, phys as _phys,
-                            rows_engaged as _rows_engaged, excess as _excess, tape as _tape)
+                            rows_engaged as _rows_engaged, excess as _excess, tape as _tape, ENGAGED_SEEDS as SEEDS)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,9 +24,6 @@ N = 4
 FMJ_WARN_BADQVEL = 2
 TREES = ('shape1', 'shape4', 'shape6', 'shape10')      # wide_trees.WIDE_SHAPES: 128 / 127 / 68 / 65 dofs, dof chains of 64 / 20 / 40 / 30
 MODELS = ('salamander33', 'eel48', 'centipede_20_25') + TREES
-# the seed of each model's inputs: the first of 100, 101, ... (0, 1, ... for the larger models) at which the oracle finds, in every
-# env, at least 5 rows with a force and a candidate row without one (the test asserts both before it looks at the device)
-SEEDS = {'salamander33': 104, 'eel48': 100, 'centipede_20_25': 2, 'shape1': 3, 'shape4': 4, 'shape6': 5, 'shape10': 6}
 
 
 @pytest.mark.parametrize('integrator', ['euler', 'implicitfast'])
@@ -151,7 +148,7 @@ def test_through_the_simulation(oracle, fused):
     """eel(48) with recipe A's limits, wave controller and drag, 40 iterations: per-iteration (fp64_limits=True) and in one fused launch
     (fp64_fused=True as well), against oracle.run_fused with the measures and bounds of the unconstrained cases in
     test_gpu_f64_step.py (per-iteration) and test_gpu_f64_fused.py (fused)."""
-    import test_gpu_f64_fused as F
+    import support_f64_fused as F
     T = 40
     m = _limited('eel48', 0.1, 0.01)
     kw = dict(fp64_fused=True) if fused else {}

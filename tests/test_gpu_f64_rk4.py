@@ -24,12 +24,12 @@ LIMITED = ('salamander33', 'eel48', 'centipede_20_25', 'shape6')
 
 def _case(name, limits):
     """The model, its inputs (tree_inputs / engaged_inputs with the seeds of test_gpu_f64_step.py / test_gpu_f64_limits.py)."""
-    import test_gpu_f64_step as S
-    import test_gpu_f64_limits as LM
+    import support_f64_step as S
+    from support_limits import ENGAGED_SEEDS
     from support_models import tree_inputs
     if limits:
         m = rk4_limited(name)
-        return m, _engaged_inputs(m, N, LM.SEEDS[name])
+        return m, _engaged_inputs(m, N, ENGAGED_SEEDS[name])
     m = rk4_model(name)
     return m, tree_inputs(m, N, S.MODELS.index(name))
 
@@ -37,7 +37,7 @@ def _case(name, limits):
 @pytest.mark.parametrize('name,limits', [(n, False) for n in PLAIN] + [(n, True) for n in LIMITED])
 def test_one_step_and_forward_to_the_ulp(oracle, name, limits):
     import torch
-    import test_gpu_f64_step as S
+    import support_f64_step as S
     from support_limits import rows_engaged
     m, inputs = _case(name, limits)
     groups = S._field_groups(m)
@@ -82,7 +82,7 @@ def test_one_step_and_forward_to_the_ulp(oracle, name, limits):
 def test_forward_debug_rows_are_m(oracle):
     """fmj_forward_debug on an RK4 context: H_rows is M (no h B on the diagonal), qfrc_smooth as ever."""
     import torch
-    import test_gpu_f64_step as S
+    import support_f64_step as S
     from wide_trees import dof_depth
     m, inputs = _case('salamander33', False)
     assert np.abs(m.dof_damping).max() > 0
@@ -199,7 +199,7 @@ def test_trajectory_against_the_state_rounding_floor(oracle):
 
 
 def _limited_swim(T, fused):
-    import test_gpu_f64_fused as F
+    import support_f64_fused as F
     m = rk4_limited('eel48', 0.1, 0.01)
     assert m.timestep == 1e-3
     kw = dict(fp64_fused=True) if fused else {}
@@ -214,7 +214,7 @@ def _limited_swim(T, fused):
 def test_through_the_simulation(oracle, fused):
     """eel(48) with recipe A's limits, wave controller, drag and a current, 40 RK4 iterations: per-iteration (fmj_before_step +
     fmj_step(1)) and in one fused launch, against oracle.run_fused with the measures and bounds of test_gpu_f64_limits.py."""
-    import test_gpu_f64_fused as F
+    import support_f64_fused as F
     T = 40
     sim, m = _limited_swim(T, fused)
     assert sim.physics.rk4 and sim.physics.fp64_rk4 and sim.physics.has_constraints
@@ -237,7 +237,7 @@ def test_through_the_simulation(oracle, fused):
 
 def test_a_tree_past_64_dofs_fused(oracle):
     """centipede(20, 25), unlimited, RK4, fused: the two-wave sizes."""
-    import test_gpu_f64_fused as F
+    import support_f64_fused as F
     T = 40
     m = rk4_model('centipede_20_25')
     assert m.timestep == 1e-3 and m.nv > 64
@@ -253,7 +253,7 @@ def test_a_tree_past_64_dofs_fused(oracle):
 
 def test_fused_chunks_resume_bitwise(tmp_path):
     """Two fused launches of 20 iterations, and the same with save_state / load_state into a fresh simulation between them."""
-    import test_gpu_f64_fused as F
+    import support_f64_fused as F
     T = 40
     a, _ = _limited_swim(T, True)
     assert a.step_fused(20) == 20 and a.step_fused(20) == 20
@@ -297,9 +297,9 @@ def test_step_3_against_three_steps_of_1(oracle):
 
 def test_a_nan_freezes_one_env_and_leaves_the_rest_alone():
     import torch
-    import test_gpu_f64_limits as LM
+    from support_limits import ENGAGED_SEEDS
     m = rk4_limited('eel48')
-    qpos, qvel, ctrl, xf, qs = _engaged_inputs(m, N, LM.SEEDS['eel48'])
+    qpos, qvel, ctrl, xf, qs = _engaged_inputs(m, N, ENGAGED_SEEDS['eel48'])
     clean, _ = _phys(m, N, qpos, qvel, ctrl, xf, qs, limits=True)
     clean.step(3)
     bad_v = qvel.copy(); bad_v[2, m.nv - 1] = np.nan

@@ -14,7 +14,7 @@ from parity_metrics import relerr
 import support_f64_contacts as C
 import support_f64_terrain as T
 from support_f64_terrain import N
-from test_gpu_f64_contacts import STATE, _groups, _contact_excess, _excess
+from support_f64_contacts import STATE, _groups, _contact_excess, _excess
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize('integrator', ['euler', 'implicitfast'])
 @pytest.mark.parametrize('name', T.MODELS)
 def test_one_step_and_forward_to_the_ulp(oracle, name, integrator):
-    import test_gpu_f64_step as S
+    import support_f64_step as S
     m = T.make(name, integrator)
     ins = T.inputs(m, N, T.SEEDS[name])
     ok, ref, what = T.conditions_of(oracle, name, m, ins)
@@ -121,7 +121,7 @@ def test_trajectory_against_the_state_rounding_floor(oracle):
 
 
 def test_a_full_contact_list_is_truncated_and_reported(oracle):
-    import test_gpu_f64_step as S
+    import support_f64_step as S
     import torch
     name = 'centipede_hfield_cyl'
     m = T.make(name)
