@@ -58,6 +58,16 @@
 // against the plane under the cylinder's centre).  The normal travels in the exchange record (pos, dist, normal, geom and ground entry
 // in one double), the tangents come from it by add_contact's rule per contact (a plane's are its host-computed constants), and the
 // normal stays in LDS (F64_TN doubles per contact past the records) for the record store of the launch's last step.
+//
+// fmj_step_f64_elliptic_kernel<LIMITS> (fmj_create_ex2 with FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_ELLIPTIC and a model whose cone is
+// elliptic; the terrain kernels' text with F64_STEP_ELLIPTIC 1 on top, helpers in fmj_f64_elliptic.inc) solves the contacts under the
+// elliptic cone: three rows per contact (normal, tangent 1, tangent 2: oracle make_constraints), whose share of the Newton matrix is
+// J_c' Hc J_c with the 3 x 3 Hessian Hc of the cone's cost at the iterate (oracle cone_zone, newton_direction) - three rows on one
+// ancestor chain, so the pattern of M holds as it does for the four pyramid rows.  The cost of a contact on the cone's surface (the
+// middle zone) is not quadratic: an unchanged set of zones proves the minimiser only when no contact of the env is in that zone, and
+// the solve otherwise ends by the oracle's rule (improvement or gradient below the tolerance).  The regulariser of the tangents does
+// not depend on the friction (R_n / impratio), so a friction of 1e-5 is no stiffer than any other.  Arguments and LDS are the terrain
+// kernels' (the record keeps its stride), and so is the narrow phase: one family for flat ground and terrain.
 
 #define FMJ_F64_LANES 128
 #define F64_BD 28      // doubles per body: pos(3) mass, quat(4), ipos(3) subtree mass, iquat(4), inertia(3) -, axis(3) qpos0, jnt_pos(3) stiffness
@@ -69,7 +79,7 @@
 #define F64_GD 24      // doubles per geom of a contacts context: size(3), pos(3), quat(4), friction, invweight0 of its body + the world's, then F64_LM doubles laid out as a limit row's (margin 0, the geom's solref / solimp)
 #define F64_GI 4       // ints per geom: type, body, last dof of the body's chain (-1: none), -
 #define F64_PD 16      // doubles per plane: normal(3), point(3), tangents(6) (oracle add_contact's frame), friction, geom index
-#define F64_CT 33      // doubles of LDS per contact: W of the four rows (24), D of the active rows (4), a row scalar for J' (4), body
+#define F64_CT 33      // doubles of LDS per contact: W of the four rows (24), D of the active rows (4), a row scalar for J' (4), body (the elliptic kernels: fmj_f64_elliptic.inc)
 #define F64_TG 24      // doubles per ground entry of a terrain context: frame (9, row-major), point(3), friction, geom index, kind (0 plane, 1 heightfield), then a plane's tangents (6) or a heightfield's ncol, nrow, x / y radius, z scale, cells per metre in x / y
 #define F64_TN 3       // doubles of LDS per contact that the terrain kernels add past the F64_CT records: the contact's normal
 
@@ -337,6 +347,7 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
 #define F64_STEP_RK4 0
 #define F64_STEP_CONTACTS 0
 #define F64_STEP_TERRAIN 0
+#define F64_STEP_ELLIPTIC 0
 #include "fmj_f64_step.inc"
 #undef F64_STEP_KERNEL
 #undef F64_STEP_RK4
@@ -372,12 +383,33 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
 #undef F64_STEP_CONTACTS
 #undef F64_STEP_TERRAIN
 #endif
+#undef F64_STEP_ELLIPTIC
+#if FMJ_TU_F64 == 6
+#include "fmj_f64_contacts.inc"
+#include "fmj_f64_terrain.inc"
+#include "fmj_f64_elliptic.inc"
+#define F64_STEP_KERNEL fmj_step_f64_elliptic_kernel
+#define F64_STEP_RK4 0
+#define F64_STEP_CONTACTS 1
+#define F64_STEP_TERRAIN 1
+#define F64_STEP_ELLIPTIC 1
+#include "fmj_f64_step.inc"
+#undef F64_STEP_KERNEL
+#undef F64_STEP_RK4
+#undef F64_STEP_CONTACTS
+#undef F64_STEP_TERRAIN
+#undef F64_STEP_ELLIPTIC
+#endif
 
 // -DFMJ_TU_F64: the two instantiations without limits; -DFMJ_TU_F64=2: the two LIMITS instantiations, a translation unit of their own;
 // -DFMJ_TU_F64=3: the four RK4 instantiations, one more; -DFMJ_TU_F64=4: the two contacts kernels, one more; -DFMJ_TU_F64=5: the two
-// terrain kernels, one more.  Every getter takes (fused, limits); a unit without fused builds, or with one setting of LIMITS, does not read that argument.
+// terrain kernels, one more; -DFMJ_TU_F64=6: the two elliptic kernels, one more.  Every getter takes (fused, limits); a unit without fused builds, or with one setting of LIMITS, does not read that argument.
 // (a getter names only its own unit's instantiations: naming another would instantiate it here)
-#if FMJ_TU_F64 == 5
+#if FMJ_TU_F64 == 6
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_elliptic(int /*fused: no fused builds*/, int limits) {
+  return limits ? (void*)fmj_step_f64_elliptic_kernel<true> : (void*)fmj_step_f64_elliptic_kernel<false>;
+}
+#elif FMJ_TU_F64 == 5
 extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_terrain(int /*fused: no fused builds*/, int limits) {
   return limits ? (void*)fmj_step_f64_terrain_kernel<true> : (void*)fmj_step_f64_terrain_kernel<false>;
 }

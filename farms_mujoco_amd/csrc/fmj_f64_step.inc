@@ -7,6 +7,8 @@
 // `CONTACTS` condition is a compile-time constant, and CONS = LIMITS || CONTACTS is LIMITS in the other two texts.
 // With F64_STEP_TERRAIN 1 on top of that it is fmj_step_f64_terrain_kernel<LIMITS> (a sixth argument, F64Terrain; dynamic LDS is
 // ldsd_terrain_bytes): the ground entries are planes and the heightfield, the animat may carry cylinders, and a contact has its own normal.
+// With F64_STEP_ELLIPTIC 1 on top of both it is fmj_step_f64_elliptic_kernel<LIMITS> (the terrain kernels' arguments and LDS): a contact
+// is three rows under the elliptic cone (fmj_f64_elliptic.inc); every `#if F64_STEP_ELLIPTIC` keeps the pyramid's statements in its #else.
 #if F64_STEP_TERRAIN
 template <bool LIMITS>
 __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model FM, const StepArgs A, const F64Fused U, const F64Limits LM, const F64Contacts CM,
@@ -288,10 +290,19 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
     bool is_c = false;
     d3 c_pos = dmk(0.0, 0.0, 0.0);
     int c_geom = 0, c_plane = 0, c_ld = 0, c_dep = 0;
+#if F64_STEP_ELLIPTIC
+    // three rows per contact: normal, tangent 1, tangent 2.  c_mu: the friction of the tangents (fr), c_mi: fr / sqrt(impratio) (mu),
+    // c_D: 1 / R of the normal row, c_zone: the cone zone at the iterate
+    double c_mu = 0.0, c_mi = 0.0, c_D = 0.0, c_ar0 = 0.0, c_ar1 = 0.0, c_ar2 = 0.0;
+    double c_ja0 = 0.0, c_ja1 = 0.0, c_ja2 = 0.0, c_jp0 = 0.0, c_jp1 = 0.0, c_jp2 = 0.0;      // J a - aref, J p
+    double c_f0 = 0.0, c_f1 = 0.0, c_f2 = 0.0;
+    int c_zone = 0;
+#else
     double c_mu = 0.0, c_D = 0.0, c_ar0 = 0.0, c_ar1 = 0.0, c_ar2 = 0.0, c_ar3 = 0.0;
     double c_ja0 = 0.0, c_ja1 = 0.0, c_ja2 = 0.0, c_ja3 = 0.0, c_jp0 = 0.0, c_jp1 = 0.0, c_jp2 = 0.0, c_jp3 = 0.0;      // J a - aref, J p
     double c_f0 = 0.0, c_f1 = 0.0, c_f2 = 0.0, c_f3 = 0.0;
     bool c_a0 = false, c_a1 = false, c_a2 = false, c_a3 = false;
+#endif
     d6 cbuf = {dmk(0.0, 0.0, 0.0), dmk(0.0, 0.0, 0.0)};      // lane = dof: the contact stiffness of its row
     {
       double* XP = XCH; double* XL = XCH + FMJ_F64_LANES * 8;
@@ -356,6 +367,25 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
 #endif
         const d3 off = dsub(c_pos, com);
         const d6 V = f64_chain_sum(CD, QV, FM.danc, rs, c_ld, c_dep);
+#if F64_STEP_ELLIPTIC
+        // oracle make_constraints, elliptic branch: one row per axis of the contact frame, unscaled by the friction; diagApprox is the
+        // bodies' invweight0 alone; only the normal row has a position (the tangents' aref has K = 0); the tangents' regulariser
+        // R_t = R_n mu^2 / fr^2 with mu = fr / sqrt(impratio) enters the solve as D0 fr^2 / mu^2 (f64_cone_zone)
+        const double diag = cg[11];
+        double* ct = CT + lane * F64_CT;
+        double imp, K, B;
+        f64_row_impedance(cg + 12, h, dist, imp, K, B);      // (margin 0)
+        const double R = fmax(F64_MINVAL, (1.0 - imp) * diag / imp);
+#define F64_CONTACT_ROW(r_, u_, ar_, pos_) do { \
+          const d6 W_ = {dcross(off, u_), u_}; \
+          dput6(ct + 6 * (r_), W_); \
+          ar_ = -B * d6dot(W_, V) - (pos_); } while (0)
+        F64_CONTACT_ROW(0, n, c_ar0, K * imp * dist); F64_CONTACT_ROW(1, t1, c_ar1, 0.0); F64_CONTACT_ROW(2, t2, c_ar2, 0.0);
+#undef F64_CONTACT_ROW
+        c_mi = c_mu * (1.0 / CM.sqrt_impratio);
+        c_D = 1.0 / R;
+        ct[32] = (double)cb;
+#else
         const double diag = cg[11] + c_mu * c_mu * cg[11];
         double* ct = CT + lane * F64_CT;
         double imp, K, B;
@@ -371,6 +401,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         const double mi = c_mu / CM.sqrt_impratio;      // all rows of a contact share R = 2 mu^2 R_first, mu scaled by 1 / sqrt(impratio)
         c_D = 1.0 / fmax(F64_MINVAL, 2.0 * mi * mi * R);
         ct[32] = (double)cb;
+#endif
       }
     }
 #endif
@@ -523,6 +554,9 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
     if (!CONS || phase == 2) break;
     // ---- limits: the Newton iteration on the primal problem (oracle solve_primal, unilateral rows); every branch below is uniform
     bool stop;
+#if F64_STEP_ELLIPTIC
+    bool small_gain = false;
+#endif
     if (phase == 0) {                       // x = a_s: the first iterate, where M (a - a_s) = 0
       nt_as = nt_a = x; nt_r = 0.0;
       phase = 1;
@@ -534,8 +568,12 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
       if (is_c) {                           // J a_s - aref
         const d6 S = f64_chain_sum(CD, XW, FM.danc, rs, c_ld, c_dep);
         const double* ct = CT + lane * F64_CT;
+#if F64_STEP_ELLIPTIC
+        c_ja0 = d6dot(dget6(ct), S) - c_ar0; c_ja1 = d6dot(dget6(ct + 6), S) - c_ar1; c_ja2 = d6dot(dget6(ct + 12), S) - c_ar2;
+#else
         c_ja0 = d6dot(dget6(ct), S) - c_ar0; c_ja1 = d6dot(dget6(ct + 6), S) - c_ar1;
         c_ja2 = d6dot(dget6(ct + 12), S) - c_ar2; c_ja3 = d6dot(dget6(ct + 18), S) - c_ar3;
+#endif
       }
 #endif
     } else {                                // x = (M + D_S)^-1 g: the search direction p = -x and M p = -g - D_S p
@@ -548,11 +586,23 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
       if (is_c) {
         const d6 S = f64_chain_sum(CD, XW, FM.danc, rs, c_ld, c_dep);
         double* ct = CT + lane * F64_CT;
+#if F64_STEP_ELLIPTIC
+        c_jp0 = d6dot(dget6(ct), S); c_jp1 = d6dot(dget6(ct + 6), S); c_jp2 = d6dot(dget6(ct + 12), S);
+        // the row scalars of J' Hc J p: (Hc J p)_a, with the Hc of the iterate the matrix was built from (the record's)
+        const double r0 = ct[18] * c_jp0 + ct[19] * c_jp1 + ct[20] * c_jp2, r1 = ct[19] * c_jp0 + ct[21] * c_jp1 + ct[22] * c_jp2;
+        const double r2 = ct[20] * c_jp0 + ct[22] * c_jp1 + ct[23] * c_jp2;
+        ct[24] = r0; ct[25] = r1; ct[26] = r2;
+#else
         c_jp0 = d6dot(dget6(ct), S); c_jp1 = d6dot(dget6(ct + 6), S); c_jp2 = d6dot(dget6(ct + 12), S); c_jp3 = d6dot(dget6(ct + 18), S);
         ct[28] = c_a0 ? c_D * c_jp0 : 0.0; ct[29] = c_a1 ? c_D * c_jp1 : 0.0; ct[30] = c_a2 ? c_D * c_jp2 : 0.0; ct[31] = c_a3 ? c_D * c_jp3 : 0.0;
+#endif
       }
       __syncthreads();
+#if F64_STEP_ELLIPTIC
+      if (isd) { d6 fs, unused; f64_elliptic_subtree(CT, ncon, d_b0, d_b1, cd, false, fs, unused); cMp = d6dot(cd, fs); }
+#else
       if (isd) { d6 fs, unused; f64_contact_subtree(CT, ncon, d_b0, d_b1, cd, false, fs, unused); cMp = d6dot(cd, fs); }
+#endif
       const double Mp = -nt_g - dadd * sp - cMp;
 #else
       const double sp = -x, Mp = -nt_g - dadd * sp;
@@ -567,7 +617,15 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         const double x_lo = j_lo + alpha * sp, x_hi = j_hi - alpha * sp;
         if (c_lo && x_lo < 0.0) { c += 0.5 * D_lo * x_lo * x_lo; e0 += D_lo * x_lo * sp; e1 += D_lo * sp * sp; }
         if (c_hi && x_hi < 0.0) { c += 0.5 * D_hi * x_hi * x_hi; e0 -= D_hi * x_hi * sp; e1 += D_hi * sp * sp; }
-#if F64_STEP_CONTACTS
+#if F64_STEP_ELLIPTIC
+        if (is_c) {      // oracle ls_eval, the elliptic block: the cone at jar + alpha J p
+          double cc, g0, g1, g2, h00, h01, h02, h11, h12, h22;
+          f64_cone_zone(c_ja0 + alpha * c_jp0, c_ja1 + alpha * c_jp1, c_ja2 + alpha * c_jp2, c_D, c_mi, c_mu, cc, g0, g1, g2, h00, h01, h02, h11, h12, h22);
+          c += cc;
+          e0 -= g0 * c_jp0; e0 -= g1 * c_jp1; e0 -= g2 * c_jp2;
+          e1 += h00 * c_jp0 * c_jp0 + h11 * c_jp1 * c_jp1 + h22 * c_jp2 * c_jp2 + 2.0 * (h01 * c_jp0 * c_jp1 + h02 * c_jp0 * c_jp2 + h12 * c_jp1 * c_jp2);
+        }
+#elif F64_STEP_CONTACTS
         if (is_c) {
 #define F64_LS_ROW(ja_, jp_) do { const double x_ = (ja_) + alpha * (jp_); \
             if (x_ < 0.0) { c += 0.5 * c_D * x_ * x_; e0 += c_D * x_ * (jp_); e1 += c_D * (jp_) * (jp_); } } while (0)
@@ -582,11 +640,17 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         return pt;
       };
       double alpha = 0.0;
+#if F64_STEP_ELLIPTIC
+      double ls_c0 = 0.0, ls_c = 0.0;       // the cost at alpha = 0 and at the step taken (the oracle's oldcost and cost)
+#endif
       if (!(snorm < F64_MINVAL)) {          // primal_linesearch
         const F64LsPt p0 = ls_eval(0.0);
         F64LsPt p1 = ls_eval(-p0.d0 / p0.d1);
         if (p0.cost < p1.cost) p1 = p0;
         alpha = p1.alpha;
+#if F64_STEP_ELLIPTIC
+        ls_c0 = p0.cost; ls_c = p1.cost;
+#endif
         if (!(fabs(p1.d0) < gtol)) {
           int it = 0;
           bool done = false;
@@ -598,6 +662,9 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
             if (fabs(p1.d0) < gtol) { done = true; break; }
           }
           alpha = p1.alpha;
+#if F64_STEP_ELLIPTIC
+          ls_c = p1.cost;
+#endif
           if (!done && !(it >= LM.ls_iterations || p1.d0 * dir <= 0.0)) {
             F64LsPt lo = dir > 0.0 ? p2 : p1, hi = dir > 0.0 ? p1 : p2;      // phi'(lo) < 0 < phi'(hi): the minimiser is bracketed
             F64LsPt best = fabs(lo.d0) < fabs(hi.d0) ? lo : hi;
@@ -612,11 +679,17 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
               if (hi.alpha - lo.alpha <= 1e-16 * fabs(hi.alpha)) break;
             }
             alpha = (done || best.cost < p0.cost) ? best.alpha : 0.0;
+#if F64_STEP_ELLIPTIC
+            ls_c = (done || best.cost < p0.cost) ? best.cost : p0.cost;
+#endif
           }
         }
       }
       nt_a += alpha * sp; nt_r += alpha * Mp;
-#if F64_STEP_CONTACTS
+#if F64_STEP_ELLIPTIC
+      c_ja0 += alpha * c_jp0; c_ja1 += alpha * c_jp1; c_ja2 += alpha * c_jp2;
+      small_gain = LM.scale * (ls_c0 - ls_c) < LM.tolerance;      // the oracle's improvement (solve_primal)
+#elif F64_STEP_CONTACTS
       c_ja0 += alpha * c_jp0; c_ja1 += alpha * c_jp1; c_ja2 += alpha * c_jp2; c_ja3 += alpha * c_jp3;
 #endif
       nt_iter++;
@@ -625,7 +698,25 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
     // the rows at the iterate (primal_update): active set, forces, J' f, gradient
     const double j_lo = nt_a - ar_lo, j_hi = -nt_a - ar_hi;
     const bool n_lo = c_lo && j_lo < 0.0, n_hi = c_hi && j_hi < 0.0;
-#if F64_STEP_CONTACTS
+#if F64_STEP_ELLIPTIC
+    bool changed = n_lo != act_lo || n_hi != act_hi;
+    bool middle = false;
+    double qfc_con = 0.0;
+    {      // oracle rows_update: the cone's zone, forces and Hessian at the iterate
+      int nz = 0;
+      double cc, h00 = 0.0, h01 = 0.0, h02 = 0.0, h11 = 0.0, h12 = 0.0, h22 = 0.0;
+      if (is_c) nz = f64_cone_zone(c_ja0, c_ja1, c_ja2, c_D, c_mi, c_mu, cc, c_f0, c_f1, c_f2, h00, h01, h02, h11, h12, h22);
+      changed = changed || nz != c_zone;
+      c_zone = nz; middle = nz == 2;
+      if (is_c) {      // (the last readers of these slots passed a workgroup sum since)
+        double* ct = CT + lane * F64_CT;
+        ct[18] = h00; ct[19] = h01; ct[20] = h02; ct[21] = h11; ct[22] = h12; ct[23] = h22;
+        ct[24] = c_f0; ct[25] = c_f1; ct[26] = c_f2; ct[27] = (double)nz;
+      }
+      __syncthreads();
+      if (isd) { d6 fs; f64_elliptic_subtree(CT, ncon, d_b0, d_b1, cd, true, fs, cbuf); qfc_con = d6dot(cd, fs); }      // J' f, and the next matrix
+    }
+#elif F64_STEP_CONTACTS
     bool changed = n_lo != act_lo || n_hi != act_hi;
     double qfc_con = 0.0;
     {
@@ -654,8 +745,15 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
     {
       double g2 = nt_g * nt_g, u1 = 0.0, u2 = 0.0, u3 = 0.0;
       WG_SUM4(g2, u1, u2, u3);
+#if F64_STEP_ELLIPTIC
+      // unchanged zones end the solve only where the cost is piecewise quadratic: with no contact of the env in the middle zone, whose
+      // cost is not quadratic.  Beside it the oracle's rule (solve_primal): the improvement or the gradient below the tolerance
+      const int zf = wg_or((changed ? 1 : 0) | (middle ? 2 : 0), FLX + 2);
+      if (zf == 0 || small_gain || LM.scale * sqrt(g2) < LM.tolerance) stop = true;
+#else
       // an unchanged active set: the iterate minimises the quadratic of that set (after a_s: no row is active, a_s is the minimiser)
       if (wg_or(changed ? 1 : 0, FLX + 2) == 0 || LM.scale * sqrt(g2) < LM.tolerance) stop = true;
+#endif
     }
     if (stop) {                             // dual_finish + euler(): M + h B with qfrc_smooth + qfrc_constraint, where anything is damped
       if (RK4 || (lflags & 2) == 0) { x = nt_a; break; }
@@ -779,7 +877,11 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         o[3] = (float)cp[0]; o[4] = (float)cp[1]; o[5] = (float)cp[2];
         for (int k = 0; k < 6; k++) o[6 + k] = (float)cp[6 + k];
 #endif
+#if F64_STEP_ELLIPTIC
+        o[12] = (float)c_f0; o[13] = (float)c_f1; o[14] = (float)c_f2;      // the rows are the frame's axes (oracle export_contacts)
+#else
         o[12] = (float)(c_f0 + c_f1 + c_f2 + c_f3); o[13] = (float)(c_mu * (c_f0 - c_f1)); o[14] = (float)(c_mu * (c_f2 - c_f3));
+#endif
         o[15] = __int_as_float(((int)cp[13] << 16) | c_geom);
       }
       if (lane == 0) A.ncon[env] = ncon;

@@ -1527,13 +1527,14 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 // Build layout: this file is compiled once per register row length with -DFMJ_TU_MAXD=<4..64> (only the step-kernel
 // instantiations of that MAXD and a getter for their host stubs), once per row length of the two-wave kernel with
 // -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64, once for its LIMITS instantiations with -DFMJ_TU_F64=2
-// once for its RK4 kernels with -DFMJ_TU_F64=3, once for its contacts kernels with -DFMJ_TU_F64=4 and once for its terrain kernels with
-// -DFMJ_TU_F64=5 (kernels and getters: fmj_f64.inc + fmj_f64_step.inc, the last two with fmj_f64_contacts.inc, the last with
-// fmj_f64_terrain.inc too), and once without any of them (standalone operators and all host code), in parallel, and the objects are
-// linked into one libfmj_hip.so (farms_mujoco_amd/_lib.py).
+// once for its RK4 kernels with -DFMJ_TU_F64=3, once for its contacts kernels with -DFMJ_TU_F64=4, once for its terrain kernels with
+// -DFMJ_TU_F64=5 and once for its elliptic kernels with -DFMJ_TU_F64=6 (kernels and getters: fmj_f64.inc + fmj_f64_step.inc, the last
+// three with fmj_f64_contacts.inc, the last two with fmj_f64_terrain.inc too, the last with fmj_f64_elliptic.inc), and once without
+// any of them (standalone operators and all host code), in parallel, and the objects are linked into one libfmj_hip.so
+// (farms_mujoco_amd/_lib.py).
 // Every csrc/*.inc is part of this one source (the build and build_id() depend on all of them):
 //   fmj_cons_rows.inc, fmj_newton.inc          constraint rows and solvers of fmj_step_kernel<.., CONS = true>
-//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc (+ fmj_f64_step.inc, fmj_f64_contacts.inc, fmj_f64_terrain.inc)      the other step kernels
+//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc (+ fmj_f64_step.inc, fmj_f64_contacts.inc, fmj_f64_terrain.inc, fmj_f64_elliptic.inc)      the other step kernels
 //   fmj_stage_{carry_in,step_head,k,c,v,f,q,m,dbg_h,euler_check,euler_commit,euler_root}.inc      stages shared by fmj_step_kernel and fmj_step_wide_kernel
 //   fmj_stage2_{k,c,v,f,s}.inc                 stages shared by fmj_step_dual2_kernel and fmj_step_cons2_kernel
 //   fmj_narrow.inc                             collision helpers (device functions, CONTACT_RECORD), included once ahead of the kernels
@@ -1838,6 +1839,7 @@ void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu
 void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
 void* fmj_tu_f64(int, int); void* fmj_tu_f64_limits(int, int); void* fmj_tu_f64_rk4(int, int); void* fmj_tu_f64_contacts(int, int); void* fmj_tu_f64_terrain(int, int);
+void* fmj_tu_f64_elliptic(int, int);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -1852,7 +1854,7 @@ static int launch(const char* what, step_kernel_t k, int blocks, int threads, si
 }
 
 // ---- the fp64 kernel families (fmj_f64.inc): what the host knows of one, from the create flags to the launch.  A new family is a row.
-enum F64FamilyId { F64_PLAIN, F64_LIMITS, F64_RK4, F64_CONTACTS, F64_TERRAIN };
+enum F64FamilyId { F64_PLAIN, F64_LIMITS, F64_RK4, F64_CONTACTS, F64_TERRAIN, F64_ELLIPTIC };
 static const struct F64Family {
   void* (*tu)(int fused, int limits);   // its translation unit's getter
   bool fused;                           // fused builds exist (fmj_step_fused_f64)
@@ -1867,6 +1869,8 @@ static const struct F64Family {
    "fmj_create_ex2: LDS request of the fp64 contacts step kernel too large"},
   {fmj_tu_f64_terrain, false, true, "the fp64 contact solve on terrain (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_TERRAIN)",
    "fmj_create_ex2: LDS request of the fp64 terrain step kernel too large"},
+  {fmj_tu_f64_elliptic, false, true, "the fp64 contact solve under the elliptic cone (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_ELLIPTIC)",
+   "fmj_create_ex2: LDS request of the fp64 elliptic step kernel too large"},
 };
 // which kernels an fp64 context runs, decided once (check_model): every launch runs f64_families[family].tu(fused, limits)
 struct F64Kind {
@@ -1876,7 +1880,7 @@ struct F64Kind {
   bool solves() const { return limits || (family >= 0 && f64_families[family].contacts); }      // the kernel's Newton solve runs: limit or contact rows
 };
 static int f64_lds_bytes(int family, int limits, int nb, int nv, int nq, int rs, int max_contacts, int nu) {
-  if (family == F64_TERRAIN) return ldsd_terrain_bytes(nb, nv, nq, rs, max_contacts);
+  if (family == F64_TERRAIN || family == F64_ELLIPTIC) return ldsd_terrain_bytes(nb, nv, nq, rs, max_contacts);      // (the elliptic record keeps the stride)
   if (family == F64_CONTACTS) return ldsd_contacts_bytes(nb, nv, nq, rs, max_contacts);
   return ldsd_total_bytes(nb, nv, nq, rs, limits) + (family == F64_RK4 ? F64_RK4_LDS_DOUBLES(nu) * 8 : 0);
 }
@@ -2082,12 +2086,14 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
         if (t == FMJ_GEOM_CYLINDER && !asked(FMJ_CREATE_F64_TERRAIN)) return no("cylinder geoms");
         if (t == FMJ_GEOM_MESH) return no("mesh geoms");
       }
-      if (m->cone != FMJ_CONE_PYRAMIDAL) return no("elliptic cone (pyramidal only)");
+      // FMJ_CREATE_F64_ELLIPTIC: the elliptic cone on kernels of its own (fmj_f64_elliptic.inc)
+      const bool elliptic = asked(FMJ_CREATE_F64_ELLIPTIC) && m->cone == FMJ_CONE_ELLIPTIC;
+      if (m->cone != FMJ_CONE_PYRAMIDAL && !elliptic) return no("elliptic cone (pyramidal only)");
       if (m->noslip_iterations > 0) return no("noslip post-pass (noslip_iterations > 0)");
       if (m->integrator == FMJ_INT_RK4) return no("RK4 (Euler or implicitfast only, also with FMJ_CREATE_F64_RK4)");
       if (m->max_contacts > FMJ_F64_LANES) return no("lane for every contact: max_contacts > 128");
       if (m->ngeom > FMJ_F64_LANES) return no("lane for every geom: more than 128 geoms");
-      if (m->max_contacts >= 1 && low_friction_ground_contact(m))
+      if (m->max_contacts >= 1 && !elliptic && low_friction_ground_contact(m))      // (the elliptic cone's regulariser does not depend on the friction)
         return no("primal solve for a ground contact whose friction / sqrt(impratio) can fall below 1e-3 (rows too stiff for it: the fp32 constraint path solves such a model on the dual problem)");
       if (m->solver_iterations < 0 || !(m->solver_tolerance >= 0)) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
       for (int g = 0; g < m->ngeom; g++) {
@@ -2097,13 +2103,14 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
         if (a < 1) return no("rows for a collision geom on a body without dofs");
       }
       contacts = true; cons = 0;
+      if (elliptic) F->f64.family = F64_ELLIPTIC;
     }
     if (cons) return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex: the fp64 step has no constraint solver: the model has ") +
                              (any_limit ? "joint limits" : m->npair > 0 ? "explicit contact pairs" : "contact geoms"));
     if (asked(FMJ_CREATE_F64_LIMITS)) for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) F->f64.limits = 1;
     if (F->f64.limits && (m->solver_iterations < 0 || !(m->solver_tolerance >= 0))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
     if (m->integrator == FMJ_INT_RK4 && !asked(FMJ_CREATE_F64_RK4)) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
-    F->f64.family = contacts ? (asked(FMJ_CREATE_F64_TERRAIN) ? F64_TERRAIN : F64_CONTACTS) : m->integrator == FMJ_INT_RK4 ? F64_RK4 : F->f64.limits ? F64_LIMITS : F64_PLAIN;
+    F->f64.family = F->f64.family == F64_ELLIPTIC ? F64_ELLIPTIC : contacts ? (asked(FMJ_CREATE_F64_TERRAIN) ? F64_TERRAIN : F64_CONTACTS) : m->integrator == FMJ_INT_RK4 ? F64_RK4 : F->f64.limits ? F64_LIMITS : F64_PLAIN;
   }
   if (big && cons) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: nbody or nv above 64 with limits, contacts or pairs (one wavefront per environment on the constraint path)");
   if (cons && m->solver != FMJ_SOLVER_PGS && m->solver != FMJ_SOLVER_NEWTON && m->solver != FMJ_SOLVER_CG) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: solver must be FMJ_SOLVER_PGS, FMJ_SOLVER_CG or FMJ_SOLVER_NEWTON");
@@ -2747,7 +2754,7 @@ static int f64_geom_table(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
 // samples in double); a plane's tangents are add_contact's in both
 static int f64_ground_entries(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
   F64Host& H = *c->f64;
-  const bool terrain = F.f64.family == F64_TERRAIN;
+  const bool terrain = F.f64.family == F64_TERRAIN || F.f64.family == F64_ELLIPTIC;      // (the elliptic kernels are built from the terrain text)
   std::vector<double> rows((size_t)F.nplane * (terrain ? F64_TG : F64_PD), 0.0);
   int rc, i = 0;
   for (int g = 0; g < m->ngeom; g++) {
@@ -2830,6 +2837,8 @@ int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj
     {FMJ_CREATE_F64_CONTACTS, 0, "fmj_create_ex2: FMJ_CREATE_F64_CONTACTS needs precision = FMJ_PRECISION_F64 (the contact solve belongs to the fp64 step kernel)"},
     {FMJ_CREATE_F64_TERRAIN, FMJ_CREATE_F64_CONTACTS,
      "fmj_create_ex2: FMJ_CREATE_F64_TERRAIN needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it widens the fp64 contact solve's narrow phase)"},
+    {FMJ_CREATE_F64_ELLIPTIC, FMJ_CREATE_F64_CONTACTS,
+     "fmj_create_ex2: FMJ_CREATE_F64_ELLIPTIC needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it lets the fp64 contact solve take the elliptic cone)"},
   };
   const int32_t flags = ext ? ext->flags : 0;
   int32_t known = 0;

@@ -49,15 +49,21 @@ class _MjData(SimpleNamespace):
 #                  solve: walking models past the sizes of the fp32 constraint path; fmj_step only, no fused launch, no RK4
 #   fp64_terrain   the contacts context also takes the world's heightfield as ground and cylinder geoms on the animat: its own
 #                  kernels, whose narrow phase carries a normal per contact; opt-in, also on flat ground
+#   fp64_elliptic  the contacts context also takes a model whose cone is elliptic (three rows per contact, kernels of their own); a
+#                  pyramidal model runs what it runs without the keyword.  The elliptic cone's regulariser does not depend on the
+#                  friction, so a model with friction-0 feet (1e-5 after the clamp), which the pyramid refuses, is accepted
 _NEEDS_FP64 = "precision='fp64', not {precision!r}: "
+_CONTACTS_EXCLUDE = {'fp64_fused': 'fused contact rows are not built for the fp64 step', 'fp64_rk4': 'the fp64 contact solve integrates with Euler or implicitfast'}
 FP64_OPTIONS = {
     'fp64_fused': (0, (), _NEEDS_FP64 + 'an fp32 context fuses through fmj_step_fused', {}),
     'fp64_limits': (_lib.CREATE_F64_LIMITS, (), _NEEDS_FP64 + 'an fp32 context solves limits on its constraint path', {}),
     'fp64_rk4': (_lib.CREATE_F64_RK4, (), _NEEDS_FP64 + 'an fp32 context integrates RK4 with four launches per step', {}),
     'fp64_contacts': (_lib.CREATE_F64_CONTACTS, (), _NEEDS_FP64 + 'an fp32 context solves contacts on its constraint path',
-                      {'fp64_fused': 'fused contact rows are not built for the fp64 step', 'fp64_rk4': 'the fp64 contact solve integrates with Euler or implicitfast'}),
+                      _CONTACTS_EXCLUDE),
     'fp64_terrain': (_lib.CREATE_F64_TERRAIN, ('fp64_contacts',), "precision='fp64' and fp64_contacts=True (not precision={precision!r}, "
                      'fp64_contacts={fp64_contacts}): it widens the narrow phase of the fp64 contact solve', {}),
+    'fp64_elliptic': (_lib.CREATE_F64_ELLIPTIC, ('fp64_contacts',), "precision='fp64' and fp64_contacts=True (not precision={precision!r}, "
+                      'fp64_contacts={fp64_contacts}): it lets the fp64 contact solve take the elliptic cone', _CONTACTS_EXCLUDE),
 }
 
 
@@ -65,7 +71,8 @@ class BatchedPhysics:
     """Device-resident mjData for ``n_envs`` copies of one model + the HIP step context."""
 
     def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None, fp64_fused: bool = False,
-                 fp64_limits: bool = False, fp64_rk4: bool = False, fp64_contacts: bool = False, fp64_terrain: bool = False):
+                 fp64_limits: bool = False, fp64_rk4: bool = False, fp64_contacts: bool = False, fp64_terrain: bool = False,
+                 fp64_elliptic: bool = False):
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
         # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
         # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
@@ -73,7 +80,7 @@ class BatchedPhysics:
         if precision not in _lib.PRECISIONS:
             raise ValueError(f'precision must be one of {sorted(_lib.PRECISIONS)}, not {precision!r}')
         on = dict(fp64_fused=bool(fp64_fused), fp64_limits=bool(fp64_limits), fp64_rk4=bool(fp64_rk4), fp64_contacts=bool(fp64_contacts),
-                  fp64_terrain=bool(fp64_terrain))
+                  fp64_terrain=bool(fp64_terrain), fp64_elliptic=bool(fp64_elliptic))
         ext_flags = 0
         for name, (flag, needs, needs_text, excludes) in FP64_OPTIONS.items():
             if on[name] and (precision != 'fp64' or not all(on[n] for n in needs)):
@@ -294,7 +301,8 @@ class BatchedPhysics:
             # which text of csrc/fmj_f64_step.inc every launch of the context runs: an fp64 context reports contacts (fmj_constraint_info's
             # max_contacts) only where its model has ground contacts and the contact solve was asked for
             contacts = self.fp64_contacts and _lib.ints(self._lib.fmj_constraint_info, self._ctx)[1] > 0
-            info['fp64_step_kernel'] = ('fmj_step_f64_terrain_kernel' if contacts and self.fp64_terrain else 'fmj_step_f64_contacts_kernel' if contacts else
+            elliptic = contacts and self.fp64_elliptic and int(getattr(self.model, 'cone', 0)) == 1      # (FMJ_CONE_ELLIPTIC; one family on flat ground and terrain)
+            info['fp64_step_kernel'] = ('fmj_step_f64_elliptic_kernel' if elliptic else 'fmj_step_f64_terrain_kernel' if contacts and self.fp64_terrain else 'fmj_step_f64_contacts_kernel' if contacts else
                                         'fmj_step_f64_rk4_kernel' if self.fp64_rk4 and self.rk4 else 'fmj_step_f64_kernel')
         if _lib.has('fmj_dual_build_info'):     # absent only from an A/B base build (FMJ_SO)
             # the two-env step kernel's build (include/fmj.h: fmj_dual_build_info): register tier, whether fused launches of the

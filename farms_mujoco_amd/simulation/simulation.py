@@ -110,7 +110,8 @@ class Simulation:
     ``fp64_contacts`` (with 'fp64': the context takes ground contacts, more rows of the same Newton solve; not with ``fp64_fused`` or ``fp64_rk4``: ``run()``
     takes the per-iteration path), ``fp64_terrain`` (with 'fp64' and ``fp64_contacts``: the contact solve also takes the heightfield as ground and
     cylinder geoms, on kernels of its own; a shard of a :class:`~farms_mujoco_amd.sharding.ShardedSimulation` gets it like the other kernel
-    arguments, from its factory), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
+    arguments, from its factory), ``fp64_elliptic`` (with 'fp64' and ``fp64_contacts``: the contact solve also takes a model whose cone is
+    elliptic, on kernels of its own - and with it a model whose feet have no friction), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
     kernels this simulation's context runs).  ``legacy_step`` is accepted for signature
     compatibility; the step is always the full mj_step (legacy_step=False semantics, simulation.py:36-37).
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here

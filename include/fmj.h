@@ -385,8 +385,19 @@ int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
  * heightfield with fewer than 2 x 2 samples or no table and one on a body other than the world (fmj_create's words); the LDS limit
  * names this context's bytes (24 more per contact: nbody = nv = 128 with a dof chain of 64 fits up to 120 contacts).  The context runs
  * its own kernels (fmj_step_f64_terrain_kernel) on any model it accepts, flat ground included - opt-in because the general narrow
- * phase is not free to a flat-ground user; what it covers and leaves in fmj_data is what a contacts context does. */
-enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8, FMJ_CREATE_F64_CONTACTS = 32, FMJ_CREATE_F64_TERRAIN = 128 };
+ * phase is not free to a flat-ground user; what it covers and leaves in fmj_data is what a contacts context does.
+ * FMJ_CREATE_F64_ELLIPTIC (without FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64: FMJ_ERR_ARG, before the device lookup;
+ * bit 256 is not assigned either): a contacts context that also accepts cone = FMJ_CONE_ELLIPTIC.  It says what the context may
+ * take: a pyramidal model gives the context it gives without the flag, to the same bits.  An elliptic model runs kernels of its own
+ * (fmj_step_f64_elliptic_kernel): a contact is three rows (normal, tangent 1, tangent 2) of the same primal Newton solve, its share of
+ * the Newton matrix J_c' Hc J_c with the 3 x 3 Hessian of the cone's cost - three rows on one ancestor chain, so the pattern of M
+ * holds.  The regulariser of the tangent rows does not depend on the friction (R_n / impratio), so the refusal of a contact whose
+ * friction / sqrt(impratio) can fall below 1e-3 does not apply to an elliptic model: a model whose geoms have no friction at all
+ * (1e-5 after the clamp) is accepted.  Heightfield and cylinder geoms still need FMJ_CREATE_F64_TERRAIN (the elliptic kernels hold
+ * the terrain kernels' narrow phase, so one family serves both, and the LDS limit is the terrain context's); explicit pairs, meshes,
+ * noslip, RK4 and fused launches stay refused with the same words.  fmj_data.contact holds the force in the contact frame directly
+ * (normal, tangent 1, tangent 2); fmj_solver_info reports Newton; everything else is what a contacts context covers and leaves. */
+enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8, FMJ_CREATE_F64_CONTACTS = 32, FMJ_CREATE_F64_TERRAIN = 128, FMJ_CREATE_F64_ELLIPTIC = 512 };
 typedef struct fmj_create_ext {
   int32_t size;           /* = sizeof(fmj_create_ext); anything else: FMJ_ERR_ARG */
   int32_t flags;          /* FMJ_CREATE_*, or 0 */
