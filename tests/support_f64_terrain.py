@@ -166,10 +166,11 @@ def lowest(m, qpos):
     return candidates(m, qpos)[0].min()
 
 
-def inputs(m, n, seed, depth=None, tilt=None):
+def inputs(m, n, seed, depth=None, tilt=None, xy=(0.0, 0.0)):
     """support_f64_contacts.inputs over terrain: random joint positions (+-0.15; three joints of a limited model at or past their upper
     limit), a tilted root, qvel normal x 0.3, ctrl uniform +-0.3, and the root lowered until the deepest candidate point is ``depth``
-    below the ground under it (a few passes: the ground's normal is not vertical).  Rounded to fp32."""
+    below the ground under it (a few passes: the ground's normal is not vertical).  ``xy``: where on the ground the root is put.  Rounded
+    to fp32."""
     if depth is None:
         depth = DEPTHS[m.name]
     if tilt is None:
@@ -187,7 +188,7 @@ def inputs(m, n, seed, depth=None, tilt=None):
     for e in range(n):
         ax = rng.normal(size=3); ax /= np.linalg.norm(ax); ang = rng.uniform(-tilt, tilt)
         qpos[e, 3:7] = [np.cos(ang/2), *(np.sin(ang/2)*ax)]
-        qpos[e, :2] = rng.uniform(-0.05, 0.05, 2)      # off the grid lines through the origin, where the models spawn
+        qpos[e, :2] = np.asarray(xy, float) + rng.uniform(-0.05, 0.05, 2)      # off the grid lines through the origin, where the models spawn
         qpos[e, 2] = 1.0
         for _ in range(6):
             qpos[e, 2] -= lowest(m, qpos[e]) + depth
