@@ -68,6 +68,13 @@
 // the solve otherwise ends by the oracle's rule (improvement or gradient below the tolerance).  The regulariser of the tangents does
 // not depend on the friction (R_n / impratio), so a friction of 1e-5 is no stiffer than any other.  Arguments and LDS are the terrain
 // kernels' (the record keeps its stride), and so is the narrow phase: one family for flat ground and terrain.
+//
+// fmj_step_f64_mesh_kernel<LIMITS> and fmj_step_f64_mesh_elliptic_kernel<LIMITS> (fmj_create_ex2 with FMJ_CREATE_F64_CONTACTS |
+// FMJ_CREATE_F64_MESH and a model with a FMJ_GEOM_MESH geom; the terrain kernels' text, or the elliptic kernels', with F64_STEP_MESH 1
+// on top, helper in fmj_f64_mesh.inc) add the convex mesh branch of collide_plane to the narrow phase: up to four contacts at the
+// deepest penetrating vertices of the geom, each with the normal of the ground under its own vertex.  The vertices are a double table
+// in global memory (a seventh argument, F64Mesh) that the geom's lane reads; LDS is the terrain kernels'.  Once a contact is in its
+// slot of the exchange list nothing tells it from any other: the rest of the step is the terrain (elliptic) kernels' unchanged.
 
 #define FMJ_F64_LANES 128
 #define F64_BD 28      // doubles per body: pos(3) mass, quat(4), ipos(3) subtree mass, iquat(4), inertia(3) -, axis(3) qpos0, jnt_pos(3) stiffness
@@ -128,6 +135,12 @@ struct F64Contacts {
 struct F64Terrain {
   const double* tg;             // [F64Contacts.nplane][F64_TG] the ground entries in geom order
   const double* hf;             // [nrow][ncol] the heightfield's samples (NULL without one)
+};
+
+// What only the mesh kernels read (a seventh argument of theirs)
+struct F64Mesh {
+  const double* mv;             // [nmeshvert][3] the vertices of every mesh geom in its geom's frame, unrounded
+  const int* gv;                // [F64Contacts.ngeom][2] a geom's first vertex and vertex count (0, 0: no mesh)
 };
 
 // LDS map, in doubles (ints at the end)
@@ -348,6 +361,7 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
 #define F64_STEP_CONTACTS 0
 #define F64_STEP_TERRAIN 0
 #define F64_STEP_ELLIPTIC 0
+#define F64_STEP_MESH 0
 #include "fmj_f64_step.inc"
 #undef F64_STEP_KERNEL
 #undef F64_STEP_RK4
@@ -400,12 +414,46 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
 #undef F64_STEP_TERRAIN
 #undef F64_STEP_ELLIPTIC
 #endif
+#undef F64_STEP_MESH
+#if FMJ_TU_F64 == 7 || FMJ_TU_F64 == 8
+#include "fmj_f64_contacts.inc"
+#include "fmj_f64_terrain.inc"
+#if FMJ_TU_F64 == 8
+#include "fmj_f64_elliptic.inc"
+#define F64_STEP_KERNEL fmj_step_f64_mesh_elliptic_kernel
+#define F64_STEP_ELLIPTIC 1
+#else
+#define F64_STEP_KERNEL fmj_step_f64_mesh_kernel
+#define F64_STEP_ELLIPTIC 0
+#endif
+#include "fmj_f64_mesh.inc"
+#define F64_STEP_RK4 0
+#define F64_STEP_CONTACTS 1
+#define F64_STEP_TERRAIN 1
+#define F64_STEP_MESH 1
+#include "fmj_f64_step.inc"
+#undef F64_STEP_KERNEL
+#undef F64_STEP_RK4
+#undef F64_STEP_CONTACTS
+#undef F64_STEP_TERRAIN
+#undef F64_STEP_ELLIPTIC
+#undef F64_STEP_MESH
+#endif
 
 // -DFMJ_TU_F64: the two instantiations without limits; -DFMJ_TU_F64=2: the two LIMITS instantiations, a translation unit of their own;
 // -DFMJ_TU_F64=3: the four RK4 instantiations, one more; -DFMJ_TU_F64=4: the two contacts kernels, one more; -DFMJ_TU_F64=5: the two
-// terrain kernels, one more; -DFMJ_TU_F64=6: the two elliptic kernels, one more.  Every getter takes (fused, limits); a unit without fused builds, or with one setting of LIMITS, does not read that argument.
+// terrain kernels, one more; -DFMJ_TU_F64=6: the two elliptic kernels, one more; -DFMJ_TU_F64=7 and =8: the two mesh kernels and the
+// two mesh-elliptic kernels, one more each.  Every getter takes (fused, limits); a unit without fused builds, or with one setting of LIMITS, does not read that argument.
 // (a getter names only its own unit's instantiations: naming another would instantiate it here)
-#if FMJ_TU_F64 == 6
+#if FMJ_TU_F64 == 8
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_mesh_elliptic(int /*fused: no fused builds*/, int limits) {
+  return limits ? (void*)fmj_step_f64_mesh_elliptic_kernel<true> : (void*)fmj_step_f64_mesh_elliptic_kernel<false>;
+}
+#elif FMJ_TU_F64 == 7
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_mesh(int /*fused: no fused builds*/, int limits) {
+  return limits ? (void*)fmj_step_f64_mesh_kernel<true> : (void*)fmj_step_f64_mesh_kernel<false>;
+}
+#elif FMJ_TU_F64 == 6
 extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_elliptic(int /*fused: no fused builds*/, int limits) {
   return limits ? (void*)fmj_step_f64_elliptic_kernel<true> : (void*)fmj_step_f64_elliptic_kernel<false>;
 }

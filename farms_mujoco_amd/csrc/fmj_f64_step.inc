@@ -9,7 +9,15 @@
 // ldsd_terrain_bytes): the ground entries are planes and the heightfield, the animat may carry cylinders, and a contact has its own normal.
 // With F64_STEP_ELLIPTIC 1 on top of both it is fmj_step_f64_elliptic_kernel<LIMITS> (the terrain kernels' arguments and LDS): a contact
 // is three rows under the elliptic cone (fmj_f64_elliptic.inc); every `#if F64_STEP_ELLIPTIC` keeps the pyramid's statements in its #else.
-#if F64_STEP_TERRAIN
+// With F64_STEP_MESH 1 on top of the terrain or the elliptic text it is fmj_step_f64_mesh_kernel<LIMITS> / fmj_step_f64_mesh_elliptic_kernel
+// <LIMITS> (a seventh argument, F64Mesh): the narrow phase takes convex mesh geoms (fmj_f64_mesh.inc); every `#if F64_STEP_MESH` keeps
+// the terrain kernels' statements in its #else.
+#if F64_STEP_MESH
+template <bool LIMITS>
+__global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model FM, const StepArgs A, const F64Fused U, const F64Limits LM, const F64Contacts CM,
+                                                                 const F64Terrain TM, const F64Mesh MM) {
+  constexpr bool FUSED = false;
+#elif F64_STEP_TERRAIN
 template <bool LIMITS>
 __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model FM, const StepArgs A, const F64Fused U, const F64Limits LM, const F64Contacts CM,
                                                                  const F64Terrain TM) {
@@ -69,6 +77,9 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
   const double* gdp = CM.gd + (size_t)gl * F64_GD;
   const int g_type = isg ? CM.gi[gl * F64_GI] : -1, g_body = CM.gi[gl * F64_GI + 1];
   const int d_b0 = isd ? d_body : 1, d_b1 = isd ? d_body + FM.bi[(size_t)d_body * F64_BI + 4] - 1 : 0;
+#endif
+#if F64_STEP_MESH
+  const int g_v0 = MM.gv[2 * gl], g_nvert = isg ? MM.gv[2 * gl + 1] : 0;      // lane = geom: its vertices (none: no mesh)
 #endif
 
   // ---- load the state: widened once
@@ -311,7 +322,9 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         XP[lane * 8 + 4] = xq.w; XP[lane * 8 + 5] = xq.x; XP[lane * 8 + 6] = xq.y; XP[lane * 8 + 7] = xq.z;
       }
       __syncthreads();
-#if F64_STEP_TERRAIN
+#if F64_STEP_MESH
+      const bool animat = g_type == FMJ_GEOM_SPHERE || g_type == FMJ_GEOM_CAPSULE || g_type == FMJ_GEOM_BOX || g_type == FMJ_GEOM_CYLINDER || g_type == FMJ_GEOM_MESH;
+#elif F64_STEP_TERRAIN
       const bool animat = g_type == FMJ_GEOM_SPHERE || g_type == FMJ_GEOM_CAPSULE || g_type == FMJ_GEOM_BOX || g_type == FMJ_GEOM_CYLINDER;
 #else
       const bool animat = g_type == FMJ_GEOM_SPHERE || g_type == FMJ_GEOM_CAPSULE || g_type == FMJ_GEOM_BOX;
@@ -321,7 +334,13 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
       int ntot = 0;
 #pragma unroll 1
       for (int p = 0; p < CM.nplane; p++) {
-#if F64_STEP_TERRAIN
+#if F64_STEP_MESH
+        const double* tgp = TM.tg + (size_t)p * F64_TG;
+        const int cnt = animat ? f64_mesh_contacts(gdp, g_type, gbp, gbq, tgp, TM.hf, MM.mv, g_v0, g_nvert, lane, p, 0, 0, nullptr) : 0;
+        int tot;
+        const int base = ntot + wg_scan_excl(cnt, FLX + 4, tot);
+        if (cnt > 0 && base < CM.max_contacts) f64_mesh_contacts(gdp, g_type, gbp, gbq, tgp, TM.hf, MM.mv, g_v0, g_nvert, lane, p, base, CM.max_contacts, XL);
+#elif F64_STEP_TERRAIN
         const double* tgp = TM.tg + (size_t)p * F64_TG;
         const int cnt = animat ? f64_terrain_contacts(gdp, g_type, gbp, gbq, tgp, TM.hf, lane, p, 0, 0, nullptr) : 0;
         int tot;

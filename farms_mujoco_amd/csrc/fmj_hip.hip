@@ -1528,13 +1528,14 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 // instantiations of that MAXD and a getter for their host stubs), once per row length of the two-wave kernel with
 // -DFMJ_TU_WIDE=<32|64>, once for the fp64 step kernel with -DFMJ_TU_F64, once for its LIMITS instantiations with -DFMJ_TU_F64=2
 // once for its RK4 kernels with -DFMJ_TU_F64=3, once for its contacts kernels with -DFMJ_TU_F64=4, once for its terrain kernels with
-// -DFMJ_TU_F64=5 and once for its elliptic kernels with -DFMJ_TU_F64=6 (kernels and getters: fmj_f64.inc + fmj_f64_step.inc, the last
-// three with fmj_f64_contacts.inc, the last two with fmj_f64_terrain.inc too, the last with fmj_f64_elliptic.inc), and once without
+// -DFMJ_TU_F64=5, once for its elliptic kernels with -DFMJ_TU_F64=6 and once each for its mesh and mesh-elliptic kernels with
+// -DFMJ_TU_F64=7 and =8 (kernels and getters: fmj_f64.inc + fmj_f64_step.inc, from =4 on with fmj_f64_contacts.inc, from =5 on with
+// fmj_f64_terrain.inc too, =6 and =8 with fmj_f64_elliptic.inc, =7 and =8 with fmj_f64_mesh.inc), and once without
 // any of them (standalone operators and all host code), in parallel, and the objects are linked into one libfmj_hip.so
 // (farms_mujoco_amd/_lib.py).
 // Every csrc/*.inc is part of this one source (the build and build_id() depend on all of them):
 //   fmj_cons_rows.inc, fmj_newton.inc          constraint rows and solvers of fmj_step_kernel<.., CONS = true>
-//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc (+ fmj_f64_step.inc, fmj_f64_contacts.inc, fmj_f64_terrain.inc, fmj_f64_elliptic.inc)      the other step kernels
+//   fmj_dual2.inc, fmj_cons2.inc (+ fmj_cons2_rows.inc), fmj_wide.inc, fmj_f64.inc (+ fmj_f64_step.inc, fmj_f64_contacts.inc, fmj_f64_terrain.inc, fmj_f64_elliptic.inc, fmj_f64_mesh.inc)      the other step kernels
 //   fmj_stage_{carry_in,step_head,k,c,v,f,q,m,dbg_h,euler_check,euler_commit,euler_root}.inc      stages shared by fmj_step_kernel and fmj_step_wide_kernel
 //   fmj_stage2_{k,c,v,f,s}.inc                 stages shared by fmj_step_dual2_kernel and fmj_step_cons2_kernel
 //   fmj_narrow.inc                             collision helpers (device functions, CONTACT_RECORD), included once ahead of the kernels
@@ -1839,7 +1840,7 @@ void* fmj_tu_kernel_36(int, int); void* fmj_tu_kernel_40(int, int); void* fmj_tu
 void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu_kernel_60(int, int); void* fmj_tu_kernel_64(int, int);
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
 void* fmj_tu_f64(int, int); void* fmj_tu_f64_limits(int, int); void* fmj_tu_f64_rk4(int, int); void* fmj_tu_f64_contacts(int, int); void* fmj_tu_f64_terrain(int, int);
-void* fmj_tu_f64_elliptic(int, int);
+void* fmj_tu_f64_elliptic(int, int); void* fmj_tu_f64_mesh(int, int); void* fmj_tu_f64_mesh_elliptic(int, int);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -1854,7 +1855,7 @@ static int launch(const char* what, step_kernel_t k, int blocks, int threads, si
 }
 
 // ---- the fp64 kernel families (fmj_f64.inc): what the host knows of one, from the create flags to the launch.  A new family is a row.
-enum F64FamilyId { F64_PLAIN, F64_LIMITS, F64_RK4, F64_CONTACTS, F64_TERRAIN, F64_ELLIPTIC };
+enum F64FamilyId { F64_PLAIN, F64_LIMITS, F64_RK4, F64_CONTACTS, F64_TERRAIN, F64_ELLIPTIC, F64_MESH, F64_MESH_ELLIPTIC };
 static const struct F64Family {
   void* (*tu)(int fused, int limits);   // its translation unit's getter
   bool fused;                           // fused builds exist (fmj_step_fused_f64)
@@ -1871,7 +1872,14 @@ static const struct F64Family {
    "fmj_create_ex2: LDS request of the fp64 terrain step kernel too large"},
   {fmj_tu_f64_elliptic, false, true, "the fp64 contact solve under the elliptic cone (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_ELLIPTIC)",
    "fmj_create_ex2: LDS request of the fp64 elliptic step kernel too large"},
+  {fmj_tu_f64_mesh, false, true, "the fp64 contact solve with mesh geoms (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_MESH)",
+   "fmj_create_ex2: LDS request of the fp64 mesh step kernel too large"},
+  {fmj_tu_f64_mesh_elliptic, false, true,
+   "the fp64 contact solve with mesh geoms under the elliptic cone (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_MESH | FMJ_CREATE_F64_ELLIPTIC)",
+   "fmj_create_ex2: LDS request of the fp64 mesh-elliptic step kernel too large"},
 };
+// the families built from the terrain kernels' text: their ground entries are F64_TG rows and their LDS is ldsd_terrain_bytes
+static bool f64_terrain_text(int family) { return family == F64_TERRAIN || family == F64_ELLIPTIC || family == F64_MESH || family == F64_MESH_ELLIPTIC; }
 // which kernels an fp64 context runs, decided once (check_model): every launch runs f64_families[family].tu(fused, limits)
 struct F64Kind {
   int family = -1;                      // an F64FamilyId; -1: not an fp64 context
@@ -1880,7 +1888,7 @@ struct F64Kind {
   bool solves() const { return limits || (family >= 0 && f64_families[family].contacts); }      // the kernel's Newton solve runs: limit or contact rows
 };
 static int f64_lds_bytes(int family, int limits, int nb, int nv, int nq, int rs, int max_contacts, int nu) {
-  if (family == F64_TERRAIN || family == F64_ELLIPTIC) return ldsd_terrain_bytes(nb, nv, nq, rs, max_contacts);      // (the elliptic record keeps the stride)
+  if (f64_terrain_text(family)) return ldsd_terrain_bytes(nb, nv, nq, rs, max_contacts);      // (the elliptic record keeps the stride)
   if (family == F64_CONTACTS) return ldsd_contacts_bytes(nb, nv, nq, rs, max_contacts);
   return ldsd_total_bytes(nb, nv, nq, rs, limits) + (family == F64_RK4 ? F64_RK4_LDS_DOUBLES(nu) * 8 : 0);
 }
@@ -1893,6 +1901,7 @@ struct F64Host {
   F64Limits lim = {};            // the Newton solve's settings; lm: the limit rows of a context with kind.limits
   F64Contacts con = {};          // families with contacts
   F64Terrain ter = {};           // the terrain family
+  F64Mesh mesh = {};             // the mesh families
   std::vector<double> h_ad;      // actuator table mirror (fmj_set_actuator_forcerange)
   std::vector<int> h_asrc;
   std::vector<int> h_bi, h_di;   // body / dof table mirrors: the rows and swimming slots of the fused loop (fmj_set_readout_maps, fmj_set_swimming)
@@ -1920,7 +1929,7 @@ static int launch_step(fmj_ctx* c, bool fused, const StepArgs& A, void* stream, 
     if (fam.contacts && (!A.qacc_warmstart || !A.contact || !A.ncon))
       return set_err(FMJ_ERR_ARG, "fmj_data: qacc_warmstart, contact and ncon are required for models with limits / contacts");
     F64Fused U = f64_fused ? *f64_fused : F64Fused{};      // (the plain step reads none of it)
-    void* args[6] = {&H.fm, (void*)&A, &U, &H.lim, &H.con, &H.ter};      // every kernel reads its own prefix
+    void* args[7] = {&H.fm, (void*)&A, &U, &H.lim, &H.con, &H.ter, &H.mesh};      // every kernel reads its own prefix
     (void)hipLaunchKernel(fam.tu(fused, H.kind.limits), dim3(c->n_envs), dim3(FMJ_F64_LANES), args, (size_t)H.kind.lds_bytes, (hipStream_t)stream);
     if (hipError_t e = hipGetLastError()) return set_err(FMJ_ERR_HIP, std::string(fam.contacts ? "fp64 contacts step kernel launch: " : "fp64 step kernel launch: ") + hipGetErrorString(e));
     return FMJ_OK;
@@ -2084,7 +2093,7 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
         const int t = m->geom_type[g];
         if (t == FMJ_GEOM_HFIELD && !asked(FMJ_CREATE_F64_TERRAIN)) return no("heightfield geoms");
         if (t == FMJ_GEOM_CYLINDER && !asked(FMJ_CREATE_F64_TERRAIN)) return no("cylinder geoms");
-        if (t == FMJ_GEOM_MESH) return no("mesh geoms");
+        if (t == FMJ_GEOM_MESH && !asked(FMJ_CREATE_F64_MESH)) return no("mesh geoms");
       }
       // FMJ_CREATE_F64_ELLIPTIC: the elliptic cone on kernels of its own (fmj_f64_elliptic.inc)
       const bool elliptic = asked(FMJ_CREATE_F64_ELLIPTIC) && m->cone == FMJ_CONE_ELLIPTIC;
@@ -2103,14 +2112,17 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
         if (a < 1) return no("rows for a collision geom on a body without dofs");
       }
       contacts = true; cons = 0;
-      if (elliptic) F->f64.family = F64_ELLIPTIC;
+      // FMJ_CREATE_F64_MESH: a model with a mesh geom runs the mesh kernels (fmj_f64_mesh.inc), any other what it ran without the flag
+      const bool mesh = asked(FMJ_CREATE_F64_MESH) && F->any_mesh;
+      if (mesh) F->f64.family = elliptic ? F64_MESH_ELLIPTIC : F64_MESH;
+      else if (elliptic) F->f64.family = F64_ELLIPTIC;
     }
     if (cons) return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex: the fp64 step has no constraint solver: the model has ") +
                              (any_limit ? "joint limits" : m->npair > 0 ? "explicit contact pairs" : "contact geoms"));
     if (asked(FMJ_CREATE_F64_LIMITS)) for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) F->f64.limits = 1;
     if (F->f64.limits && (m->solver_iterations < 0 || !(m->solver_tolerance >= 0))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
     if (m->integrator == FMJ_INT_RK4 && !asked(FMJ_CREATE_F64_RK4)) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
-    F->f64.family = F->f64.family == F64_ELLIPTIC ? F64_ELLIPTIC : contacts ? (asked(FMJ_CREATE_F64_TERRAIN) ? F64_TERRAIN : F64_CONTACTS) : m->integrator == FMJ_INT_RK4 ? F64_RK4 : F->f64.limits ? F64_LIMITS : F64_PLAIN;
+    F->f64.family = F->f64.family >= F64_ELLIPTIC ? F->f64.family : contacts ? (asked(FMJ_CREATE_F64_TERRAIN) ? F64_TERRAIN : F64_CONTACTS) : m->integrator == FMJ_INT_RK4 ? F64_RK4 : F->f64.limits ? F64_LIMITS : F64_PLAIN;
   }
   if (big && cons) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: nbody or nv above 64 with limits, contacts or pairs (one wavefront per environment on the constraint path)");
   if (cons && m->solver != FMJ_SOLVER_PGS && m->solver != FMJ_SOLVER_NEWTON && m->solver != FMJ_SOLVER_CG) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: solver must be FMJ_SOLVER_PGS, FMJ_SOLVER_CG or FMJ_SOLVER_NEWTON");
@@ -2754,7 +2766,7 @@ static int f64_geom_table(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
 // samples in double); a plane's tangents are add_contact's in both
 static int f64_ground_entries(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
   F64Host& H = *c->f64;
-  const bool terrain = F.f64.family == F64_TERRAIN || F.f64.family == F64_ELLIPTIC;      // (the elliptic kernels are built from the terrain text)
+  const bool terrain = f64_terrain_text(F.f64.family);      // (the elliptic and the mesh kernels are built from the terrain text)
   std::vector<double> rows((size_t)F.nplane * (terrain ? F64_TG : F64_PD), 0.0);
   int rc, i = 0;
   for (int g = 0; g < m->ngeom; g++) {
@@ -2790,13 +2802,25 @@ static int f64_ground_entries(fmj_ctx* c, const fmj_model* m, const ModelFacts& 
   return upload_f64(c, rows, terrain ? &H.ter.tg : &H.con.pd);
 }
 
+// (e) the mesh families: the vertices of the mesh geoms, unrounded, and each geom's first vertex and count (check_model held every
+// range inside mesh_vert; a geom of another type gets 0, 0)
+static int f64_mesh_vertices(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
+  if (F.f64.family != F64_MESH && F.f64.family != F64_MESH_ELLIPTIC) return FMJ_OK;
+  F64Host& H = *c->f64;
+  std::vector<int> gv((size_t)m->ngeom * 2, 0);
+  for (int g = 0; g < m->ngeom; g++)
+    if (m->geom_type[g] == FMJ_GEOM_MESH) { gv[2 * g] = m->geom_vertadr[g]; gv[2 * g + 1] = m->geom_vertnum[g]; }
+  if (int rc = upload_f64(c, std::vector<double>(m->mesh_vert, m->mesh_vert + 3 * (size_t)m->nmeshvert), &H.mesh.mv)) return rc;
+  return upload_f64(c, gv, &H.mesh.gv);
+}
+
 static int build_f64(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) {
   c->f64 = new F64Host();
   const F64Kind& K = c->f64->kind = F.f64;
   const F64Family& fam = f64_families[K.family];
   int rc;
   if ((rc = f64_model_tables(c, m, F)) || (rc = f64_solver_and_limit_rows(c, m, F)) ||
-      (fam.contacts && ((rc = f64_geom_table(c, m, F)) || (rc = f64_ground_entries(c, m, F)))))
+      (fam.contacts && ((rc = f64_geom_table(c, m, F)) || (rc = f64_ground_entries(c, m, F)) || (rc = f64_mesh_vertices(c, m, F)))))
     return rc;
   for (int fused = 0; fused <= (int)fam.fused; fused++)      // (check_model held the bytes to 160 KB)
     if (hipFuncSetAttribute((const void*)fam.tu(fused, K.limits), hipFuncAttributeMaxDynamicSharedMemorySize, K.lds_bytes) != hipSuccess)
@@ -2839,6 +2863,8 @@ int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj
      "fmj_create_ex2: FMJ_CREATE_F64_TERRAIN needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it widens the fp64 contact solve's narrow phase)"},
     {FMJ_CREATE_F64_ELLIPTIC, FMJ_CREATE_F64_CONTACTS,
      "fmj_create_ex2: FMJ_CREATE_F64_ELLIPTIC needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it lets the fp64 contact solve take the elliptic cone)"},
+    {FMJ_CREATE_F64_MESH, FMJ_CREATE_F64_CONTACTS,
+     "fmj_create_ex2: FMJ_CREATE_F64_MESH needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it lets the fp64 contact solve take convex mesh geoms)"},
   };
   const int32_t flags = ext ? ext->flags : 0;
   int32_t known = 0;

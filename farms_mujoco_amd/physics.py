@@ -49,6 +49,9 @@ class _MjData(SimpleNamespace):
 #                  solve: walking models past the sizes of the fp32 constraint path; fmj_step only, no fused launch, no RK4
 #   fp64_terrain   the contacts context also takes the world's heightfield as ground and cylinder geoms on the animat: its own
 #                  kernels, whose narrow phase carries a normal per contact; opt-in, also on flat ground
+#   fp64_mesh      the contacts context also takes convex mesh geoms on the animat (what Simulation.from_sdf makes of every mesh
+#                  collision): up to four contacts at a mesh's deepest vertices, on kernels of their own; a model without a mesh
+#                  runs what it runs without the keyword
 #   fp64_elliptic  the contacts context also takes a model whose cone is elliptic (three rows per contact, kernels of their own); a
 #                  pyramidal model runs what it runs without the keyword.  The elliptic cone's regulariser does not depend on the
 #                  friction, so a model with friction-0 feet (1e-5 after the clamp), which the pyramid refuses, is accepted
@@ -62,6 +65,8 @@ FP64_OPTIONS = {
                       _CONTACTS_EXCLUDE),
     'fp64_terrain': (_lib.CREATE_F64_TERRAIN, ('fp64_contacts',), "precision='fp64' and fp64_contacts=True (not precision={precision!r}, "
                      'fp64_contacts={fp64_contacts}): it widens the narrow phase of the fp64 contact solve', {}),
+    'fp64_mesh': (_lib.CREATE_F64_MESH, ('fp64_contacts',), "precision='fp64' and fp64_contacts=True (not precision={precision!r}, "
+                  'fp64_contacts={fp64_contacts}): it lets the fp64 contact solve take convex mesh geoms', _CONTACTS_EXCLUDE),
     'fp64_elliptic': (_lib.CREATE_F64_ELLIPTIC, ('fp64_contacts',), "precision='fp64' and fp64_contacts=True (not precision={precision!r}, "
                       'fp64_contacts={fp64_contacts}): it lets the fp64 contact solve take the elliptic cone', _CONTACTS_EXCLUDE),
 }
@@ -72,7 +77,7 @@ class BatchedPhysics:
 
     def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None, fp64_fused: bool = False,
                  fp64_limits: bool = False, fp64_rk4: bool = False, fp64_contacts: bool = False, fp64_terrain: bool = False,
-                 fp64_elliptic: bool = False):
+                 fp64_elliptic: bool = False, fp64_mesh: bool = False):
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
         # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
         # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
@@ -80,7 +85,7 @@ class BatchedPhysics:
         if precision not in _lib.PRECISIONS:
             raise ValueError(f'precision must be one of {sorted(_lib.PRECISIONS)}, not {precision!r}')
         on = dict(fp64_fused=bool(fp64_fused), fp64_limits=bool(fp64_limits), fp64_rk4=bool(fp64_rk4), fp64_contacts=bool(fp64_contacts),
-                  fp64_terrain=bool(fp64_terrain), fp64_elliptic=bool(fp64_elliptic))
+                  fp64_terrain=bool(fp64_terrain), fp64_elliptic=bool(fp64_elliptic), fp64_mesh=bool(fp64_mesh))
         ext_flags = 0
         for name, (flag, needs, needs_text, excludes) in FP64_OPTIONS.items():
             if on[name] and (precision != 'fp64' or not all(on[n] for n in needs)):
@@ -302,7 +307,9 @@ class BatchedPhysics:
             # max_contacts) only where its model has ground contacts and the contact solve was asked for
             contacts = self.fp64_contacts and _lib.ints(self._lib.fmj_constraint_info, self._ctx)[1] > 0
             elliptic = contacts and self.fp64_elliptic and int(getattr(self.model, 'cone', 0)) == 1      # (FMJ_CONE_ELLIPTIC; one family on flat ground and terrain)
-            info['fp64_step_kernel'] = ('fmj_step_f64_elliptic_kernel' if elliptic else 'fmj_step_f64_terrain_kernel' if contacts and self.fp64_terrain else 'fmj_step_f64_contacts_kernel' if contacts else
+            mesh = contacts and self.fp64_mesh and bool((np.asarray(self.model.geom_type) == 7).any())      # (FMJ_GEOM_MESH: kernels of their own)
+            info['fp64_step_kernel'] = ('fmj_step_f64_mesh_elliptic_kernel' if mesh and elliptic else 'fmj_step_f64_mesh_kernel' if mesh else
+                                        'fmj_step_f64_elliptic_kernel' if elliptic else 'fmj_step_f64_terrain_kernel' if contacts and self.fp64_terrain else 'fmj_step_f64_contacts_kernel' if contacts else
                                         'fmj_step_f64_rk4_kernel' if self.fp64_rk4 and self.rk4 else 'fmj_step_f64_kernel')
         if _lib.has('fmj_dual_build_info'):     # absent only from an A/B base build (FMJ_SO)
             # the two-env step kernel's build (include/fmj.h: fmj_dual_build_info): register tier, whether fused launches of the

@@ -111,7 +111,8 @@ class Simulation:
     takes the per-iteration path), ``fp64_terrain`` (with 'fp64' and ``fp64_contacts``: the contact solve also takes the heightfield as ground and
     cylinder geoms, on kernels of its own; a shard of a :class:`~farms_mujoco_amd.sharding.ShardedSimulation` gets it like the other kernel
     arguments, from its factory), ``fp64_elliptic`` (with 'fp64' and ``fp64_contacts``: the contact solve also takes a model whose cone is
-    elliptic, on kernels of its own - and with it a model whose feet have no friction), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
+    elliptic, on kernels of its own - and with it a model whose feet have no friction), ``fp64_mesh`` (with 'fp64' and ``fp64_contacts``: the
+    contact solve also takes convex mesh geoms, which is what :meth:`from_sdf` makes of every mesh collision), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
     kernels this simulation's context runs).  ``legacy_step`` is accepted for signature
     compatibility; the step is always the full mj_step (legacy_step=False semantics, simulation.py:36-37).
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here

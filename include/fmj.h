@@ -396,8 +396,20 @@ int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
  * (1e-5 after the clamp) is accepted.  Heightfield and cylinder geoms still need FMJ_CREATE_F64_TERRAIN (the elliptic kernels hold
  * the terrain kernels' narrow phase, so one family serves both, and the LDS limit is the terrain context's); explicit pairs, meshes,
  * noslip, RK4 and fused launches stay refused with the same words.  fmj_data.contact holds the force in the contact frame directly
- * (normal, tangent 1, tangent 2); fmj_solver_info reports Newton; everything else is what a contacts context covers and leaves. */
-enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8, FMJ_CREATE_F64_CONTACTS = 32, FMJ_CREATE_F64_TERRAIN = 128, FMJ_CREATE_F64_ELLIPTIC = 512 };
+ * (normal, tangent 1, tangent 2); fmj_solver_info reports Newton; everything else is what a contacts context covers and leaves.
+ * FMJ_CREATE_F64_MESH (without FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64: FMJ_ERR_ARG, before the device lookup;
+ * bit 1024 is not assigned either): a contacts context that also accepts FMJ_GEOM_MESH geoms on the animat.  It says what the
+ * context may take: a model without a mesh geom gives the context it gives without the flag, to the same bits.  A model with one
+ * runs kernels of its own (fmj_step_f64_mesh_kernel; fmj_step_f64_mesh_elliptic_kernel for cone = FMJ_CONE_ELLIPTIC with
+ * FMJ_CREATE_F64_ELLIPTIC also given): a mesh against a ground entry gives up to four contacts at its deepest penetrating vertices,
+ * deepest first, equal depths in vertex order, each with the normal of the ground under its own vertex, and nothing when the ground
+ * under the geom's origin is farther than the bounding radius geom_size[2] (the rule of every path; mesh_vert is read unrounded, a
+ * geom may have any number of vertices).  The kernels hold the terrain kernels' narrow phase and the LDS limit is the terrain
+ * context's, but heightfield and cylinder geoms still need FMJ_CREATE_F64_TERRAIN and an elliptic model FMJ_CREATE_F64_ELLIPTIC;
+ * explicit pairs (with or without meshes), noslip, RK4, fused launches and a pyramidal model with low-friction feet stay refused
+ * with the same words. */
+enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8, FMJ_CREATE_F64_CONTACTS = 32, FMJ_CREATE_F64_TERRAIN = 128, FMJ_CREATE_F64_ELLIPTIC = 512,
+       FMJ_CREATE_F64_MESH = 2048 };
 typedef struct fmj_create_ext {
   int32_t size;           /* = sizeof(fmj_create_ext); anything else: FMJ_ERR_ARG */
   int32_t flags;          /* FMJ_CREATE_*, or 0 */
