@@ -85,6 +85,7 @@ CREATE_F64_CONTACTS = 32   # FMJ_CREATE_F64_CONTACTS (bit 16 is not assigned)
 CREATE_F64_TERRAIN = 128   # FMJ_CREATE_F64_TERRAIN (bit 64 is not assigned)
 CREATE_F64_ELLIPTIC = 512  # FMJ_CREATE_F64_ELLIPTIC (bit 256 is not assigned)
 CREATE_F64_MESH = 2048     # FMJ_CREATE_F64_MESH (bit 1024 is not assigned)
+CREATE_F64_CONTACTS_RK4 = 8192      # FMJ_CREATE_F64_CONTACTS_RK4 (bit 4096 is not assigned)
 PRECISIONS = {'fp32': 0, 'fp64': 1}      # FMJ_PRECISION_* of include/fmj.h
 KERNEL_TWO_WAVE, KERNEL_ONE_ENV_PER_WAVE, KERNEL_NO_LEAN, KERNEL_NO_PRIO = 1, 2, 4, 8      # FMJ_KERNEL_* of include/fmj.h ("Kernel selection" at fmj_create_ex)
 
@@ -189,7 +190,9 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: str = Non
                     (os.path.join(objdir, 'kf64t.o'), ['-DFMJ_TU_F64=5']),   # its terrain kernels (FMJ_CREATE_F64_TERRAIN; csrc/fmj_f64_terrain.inc)
                     (os.path.join(objdir, 'kf64e.o'), ['-DFMJ_TU_F64=6']),   # its elliptic kernels (FMJ_CREATE_F64_ELLIPTIC; csrc/fmj_f64_elliptic.inc)
                     (os.path.join(objdir, 'kf64m.o'), ['-DFMJ_TU_F64=7']),   # its mesh kernels (FMJ_CREATE_F64_MESH; csrc/fmj_f64_mesh.inc)
-                    (os.path.join(objdir, 'kf64me.o'), ['-DFMJ_TU_F64=8'])]  # its mesh kernels under the elliptic cone
+                    (os.path.join(objdir, 'kf64me.o'), ['-DFMJ_TU_F64=8']),  # its mesh kernels under the elliptic cone
+                    (os.path.join(objdir, 'kf64tr.o'), ['-DFMJ_TU_F64=9']),  # its terrain kernels with RK4 inside (FMJ_CREATE_F64_CONTACTS_RK4)
+                    (os.path.join(objdir, 'kf64er.o'), ['-DFMJ_TU_F64=10'])]  # its elliptic kernels with RK4 inside
         if dev:
             todo = [j for j in jobs if not j[1] or int(j[1][0].split('=')[1]) in dev or not os.path.exists(j[0])] + f64_jobs
             jobs += f64_jobs

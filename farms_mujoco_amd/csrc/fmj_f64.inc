@@ -75,6 +75,14 @@
 // deepest penetrating vertices of the geom, each with the normal of the ground under its own vertex.  The vertices are a double table
 // in global memory (a seventh argument, F64Mesh) that the geom's lane reads; LDS is the terrain kernels'.  Once a contact is in its
 // slot of the exchange list nothing tells it from any other: the rest of the step is the terrain (elliptic) kernels' unchanged.
+//
+// fmj_step_f64_terrain_rk4_kernel<LIMITS> and fmj_step_f64_elliptic_rk4_kernel<LIMITS> (fmj_create_ex2 with FMJ_CREATE_F64_CONTACTS |
+// FMJ_CREATE_F64_CONTACTS_RK4 and a model that integrates with RK4; the terrain kernels' text, or the elliptic kernels', with
+// F64_STEP_RK4 1 on top) run the four passes of mj_RungeKutta with contacts (oracle rk4): every pass runs the narrow phase at its own
+// poses and solves its own limit and contact rows with H = M; the step leaves the first pass's sensors and the fourth pass's poses,
+// qacc (the next warm start) and contact list, FMJ_WARN_CONTACTFULL is the OR over the passes, and a check that fails in any pass
+// undoes the step before any of it - the contact list included - is stored.  The stage state (F64_RK4_LDS_DOUBLES) lies past the
+// contacts' normals: dynamic LDS is ldsd_terrain_bytes + F64_RK4_LDS_DOUBLES(nu) * 8.  Planes need no FMJ_CREATE_F64_TERRAIN.
 
 #define FMJ_F64_LANES 128
 #define F64_BD 28      // doubles per body: pos(3) mass, quat(4), ipos(3) subtree mass, iquat(4), inertia(3) -, axis(3) qpos0, jnt_pos(3) stiffness
@@ -439,13 +447,45 @@ __device__ __forceinline__ void f64_integrate_free(double* qp, d3 p0, dq q0, con
 #undef F64_STEP_ELLIPTIC
 #undef F64_STEP_MESH
 #endif
+#if FMJ_TU_F64 == 9 || FMJ_TU_F64 == 10
+#include "fmj_f64_contacts.inc"
+#include "fmj_f64_terrain.inc"
+#if FMJ_TU_F64 == 10
+#include "fmj_f64_elliptic.inc"
+#define F64_STEP_KERNEL fmj_step_f64_elliptic_rk4_kernel
+#define F64_STEP_ELLIPTIC 1
+#else
+#define F64_STEP_KERNEL fmj_step_f64_terrain_rk4_kernel
+#define F64_STEP_ELLIPTIC 0
+#endif
+#define F64_STEP_RK4 1
+#define F64_STEP_CONTACTS 1
+#define F64_STEP_TERRAIN 1
+#define F64_STEP_MESH 0
+#include "fmj_f64_step.inc"
+#undef F64_STEP_KERNEL
+#undef F64_STEP_RK4
+#undef F64_STEP_CONTACTS
+#undef F64_STEP_TERRAIN
+#undef F64_STEP_ELLIPTIC
+#undef F64_STEP_MESH
+#endif
 
 // -DFMJ_TU_F64: the two instantiations without limits; -DFMJ_TU_F64=2: the two LIMITS instantiations, a translation unit of their own;
 // -DFMJ_TU_F64=3: the four RK4 instantiations, one more; -DFMJ_TU_F64=4: the two contacts kernels, one more; -DFMJ_TU_F64=5: the two
 // terrain kernels, one more; -DFMJ_TU_F64=6: the two elliptic kernels, one more; -DFMJ_TU_F64=7 and =8: the two mesh kernels and the
-// two mesh-elliptic kernels, one more each.  Every getter takes (fused, limits); a unit without fused builds, or with one setting of LIMITS, does not read that argument.
+// two mesh-elliptic kernels, one more each; -DFMJ_TU_F64=9 and =10: the two terrain kernels with the RK4 pass loop and the two elliptic
+// ones, one more each.  Every getter takes (fused, limits); a unit without fused builds, or with one setting of LIMITS, does not read that argument.
 // (a getter names only its own unit's instantiations: naming another would instantiate it here)
-#if FMJ_TU_F64 == 8
+#if FMJ_TU_F64 == 10
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_elliptic_rk4(int /*fused: no fused builds*/, int limits) {
+  return limits ? (void*)fmj_step_f64_elliptic_rk4_kernel<true> : (void*)fmj_step_f64_elliptic_rk4_kernel<false>;
+}
+#elif FMJ_TU_F64 == 9
+extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_terrain_rk4(int /*fused: no fused builds*/, int limits) {
+  return limits ? (void*)fmj_step_f64_terrain_rk4_kernel<true> : (void*)fmj_step_f64_terrain_rk4_kernel<false>;
+}
+#elif FMJ_TU_F64 == 8
 extern "C" __attribute__((visibility("hidden"))) void* fmj_tu_f64_mesh_elliptic(int /*fused: no fused builds*/, int limits) {
   return limits ? (void*)fmj_step_f64_mesh_elliptic_kernel<true> : (void*)fmj_step_f64_mesh_elliptic_kernel<false>;
 }

@@ -2,7 +2,7 @@
 // and the helpers): with F64_STEP_RK4 0 it is fmj_step_f64_kernel (one forward pass and the semi-implicit Euler commit per step), with
 // F64_STEP_RK4 1 fmj_step_f64_rk4_kernel (the pass loop below runs four times per step; dynamic LDS is ldsd_total_bytes +
 // F64_RK4_LDS_DOUBLES(nu)).  Every `RK4` condition is a compile-time constant: the first kernel compiles to what it was before the loop.
-// With F64_STEP_CONTACTS 1 it is fmj_step_f64_contacts_kernel<LIMITS> (never fused, never RK4; a fifth argument, F64Contacts; dynamic
+// With F64_STEP_CONTACTS 1 it is fmj_step_f64_contacts_kernel<LIMITS> (never fused; a fifth argument, F64Contacts; dynamic
 // LDS is ldsd_contacts_bytes): ground contacts as four more unilateral rows each in the Newton solve of the LIMITS build.  Every
 // `CONTACTS` condition is a compile-time constant, and CONS = LIMITS || CONTACTS is LIMITS in the other two texts.
 // With F64_STEP_TERRAIN 1 on top of that it is fmj_step_f64_terrain_kernel<LIMITS> (a sixth argument, F64Terrain; dynamic LDS is
@@ -12,6 +12,9 @@
 // With F64_STEP_MESH 1 on top of the terrain or the elliptic text it is fmj_step_f64_mesh_kernel<LIMITS> / fmj_step_f64_mesh_elliptic_kernel
 // <LIMITS> (a seventh argument, F64Mesh): the narrow phase takes convex mesh geoms (fmj_f64_mesh.inc); every `#if F64_STEP_MESH` keeps
 // the terrain kernels' statements in its #else.
+// With F64_STEP_RK4 1 on top of the terrain or the elliptic text it is fmj_step_f64_terrain_rk4_kernel<LIMITS> / fmj_step_f64_elliptic_rk4_kernel
+// <LIMITS> (dynamic LDS is ldsd_terrain_bytes + F64_RK4_LDS_DOUBLES(nu)): every pass runs the narrow phase and the solve; the contact
+// list is stored with the fourth pass's commit (fmj_f64_contact_store.inc).
 #if F64_STEP_MESH
 template <bool LIMITS>
 __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model FM, const StepArgs A, const F64Fused U, const F64Limits LM, const F64Contacts CM,
@@ -44,7 +47,11 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
   double* MX = ldsd + L.MX; double* HR = ldsd + L.HR; double* XW = ldsd + L.XW;
   int* FLG = (int*)(ldsd + L.FLG);
   double* SUM = ldsd + L.total_bytes / 8; int* FLX = (int*)(SUM + 16);      // LIMITS only: past the map (ldsd_total_bytes)
+#if F64_STEP_CONTACTS && F64_STEP_RK4
+  double* RKS = ldsd + ldsd_terrain_bytes(nb, nv, nq, rs, CM.max_contacts) / 8;      // RK4 with contacts (terrain text): past the records and the normals
+#else
   double* RKS = ldsd + ldsd_total_bytes(nb, nv, nq, rs, LIMITS) / 8;      // RK4 only: past the map and the LIMITS block (F64_RK4_LDS_DOUBLES)
+#endif
 #if F64_STEP_CONTACTS
   double* CT = ldsd + ldsd_total_bytes(nb, nv, nq, rs, 1) / 8;            // the contact records (F64_CT doubles each), past the LIMITS block
 #endif
@@ -824,7 +831,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
         const d3 rk_ang = dmk(rk[F64_RK4_ANG * FMJ_F64_LANES], rk[(F64_RK4_ANG + 1) * FMJ_F64_LANES], rk[(F64_RK4_ANG + 2) * FMJ_F64_LANES]);
         if (isd) {
           XA[lane] = my_qacc;
-          if (LIMITS) { ws_qacc = my_qacc; if (FUSED) cy_limfrc = rk_lim0 * U.inv_torques; }
+          if (CONS) { ws_qacc = my_qacc; if (FUSED) cy_limfrc = rk_lim0 * U.inv_torques; }
         }
         if (last && lane < nb) {
           float* p = A.xpos + (size_t)env * nb * 3 + lane * 3; p[0] = (float)xp.x; p[1] = (float)xp.y; p[2] = (float)xp.z;
@@ -845,6 +852,11 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
             if (FUSED && A.controller == 1 && A.ctrl_out) A.ctrl_out[(size_t)env * nu + src] = (float)RKS[nu + src];
           }
         }
+#if F64_STEP_CONTACTS
+        if (last) {      // the contact list of the step's fourth pass (fmj_forward: of its only pass), past the freeze decision above
+#include "fmj_f64_contact_store.inc"
+        }
+#endif
         // fused: the next before_step's links row and drag (fmj_before_step after an RK4 fmj_step reads the same out of fmj_data)
         if (F64_EMIT_NEXT) f64_emit_links_and_drag(U, A, env, nit, isb, link_row, swim_slot, xp, xq, xi, rk_lin, rk_ang, xf0, xf1, xf2, xf3, xf4, xf5);
         steps_done++;
@@ -879,31 +891,7 @@ __global__ void __launch_bounds__(FMJ_F64_LANES) F64_STEP_KERNEL(const F64Model 
     }
 #if F64_STEP_CONTACTS
     if (last && !frozen) {      // the contact list of the launch's last pass: pos, frame, force in the contact frame (mju_decodePyramid), geom1 << 16 | geom2
-      if (is_c) {
-#if F64_STEP_TERRAIN
-        const double* cp = TM.tg + (size_t)c_plane * F64_TG;
-        float* o = A.contact + ((size_t)env * CM.max_contacts + lane) * 16;
-        o[0] = (float)c_pos.x; o[1] = (float)c_pos.y; o[2] = (float)c_pos.z;
-        const d3 n = dmk(CN[lane * F64_TN], CN[lane * F64_TN + 1], CN[lane * F64_TN + 2]);
-        d3 t1 = dmk(cp[15], cp[16], cp[17]), t2 = dmk(cp[18], cp[19], cp[20]);
-        if (cp[14] != 0.0) f64_contact_frame(n, t1, t2);
-        o[3] = (float)n.x; o[4] = (float)n.y; o[5] = (float)n.z;
-        o[6] = (float)t1.x; o[7] = (float)t1.y; o[8] = (float)t1.z; o[9] = (float)t2.x; o[10] = (float)t2.y; o[11] = (float)t2.z;
-#else
-        const double* cp = CM.pd + (size_t)c_plane * F64_PD;
-        float* o = A.contact + ((size_t)env * CM.max_contacts + lane) * 16;
-        o[0] = (float)c_pos.x; o[1] = (float)c_pos.y; o[2] = (float)c_pos.z;
-        o[3] = (float)cp[0]; o[4] = (float)cp[1]; o[5] = (float)cp[2];
-        for (int k = 0; k < 6; k++) o[6 + k] = (float)cp[6 + k];
-#endif
-#if F64_STEP_ELLIPTIC
-        o[12] = (float)c_f0; o[13] = (float)c_f1; o[14] = (float)c_f2;      // the rows are the frame's axes (oracle export_contacts)
-#else
-        o[12] = (float)(c_f0 + c_f1 + c_f2 + c_f3); o[13] = (float)(c_mu * (c_f0 - c_f1)); o[14] = (float)(c_mu * (c_f2 - c_f3));
-#endif
-        o[15] = __int_as_float(((int)cp[13] << 16) | c_geom);
-      }
-      if (lane == 0) A.ncon[env] = ncon;
+#include "fmj_f64_contact_store.inc"
     }
 #endif
     if (!frozen) steps_done++;

@@ -1530,7 +1530,8 @@ static_assert(FMJ_JOINT_POSITION == 0 && FMJ_JOINT_VELOCITY == 1 && FMJ_JOINT_TO
 // once for its RK4 kernels with -DFMJ_TU_F64=3, once for its contacts kernels with -DFMJ_TU_F64=4, once for its terrain kernels with
 // -DFMJ_TU_F64=5, once for its elliptic kernels with -DFMJ_TU_F64=6 and once each for its mesh and mesh-elliptic kernels with
 // -DFMJ_TU_F64=7 and =8 (kernels and getters: fmj_f64.inc + fmj_f64_step.inc, from =4 on with fmj_f64_contacts.inc, from =5 on with
-// fmj_f64_terrain.inc too, =6 and =8 with fmj_f64_elliptic.inc, =7 and =8 with fmj_f64_mesh.inc), and once without
+// fmj_f64_terrain.inc too, =6 and =8 with fmj_f64_elliptic.inc, =7 and =8 with fmj_f64_mesh.inc), once each for the terrain and the
+// elliptic kernels with the RK4 pass loop with -DFMJ_TU_F64=9 and =10, and once without
 // any of them (standalone operators and all host code), in parallel, and the objects are linked into one libfmj_hip.so
 // (farms_mujoco_amd/_lib.py).
 // Every csrc/*.inc is part of this one source (the build and build_id() depend on all of them):
@@ -1841,6 +1842,7 @@ void* fmj_tu_kernel_52(int, int); void* fmj_tu_kernel_56(int, int); void* fmj_tu
 void* fmj_tu_wide_32(int); void* fmj_tu_wide_64(int);
 void* fmj_tu_f64(int, int); void* fmj_tu_f64_limits(int, int); void* fmj_tu_f64_rk4(int, int); void* fmj_tu_f64_contacts(int, int); void* fmj_tu_f64_terrain(int, int);
 void* fmj_tu_f64_elliptic(int, int); void* fmj_tu_f64_mesh(int, int); void* fmj_tu_f64_mesh_elliptic(int, int);
+void* fmj_tu_f64_terrain_rk4(int, int); void* fmj_tu_f64_elliptic_rk4(int, int);
 }
 static void* (*const tu_kernels[16])(int, int) = {
   fmj_tu_kernel_4, fmj_tu_kernel_8, fmj_tu_kernel_12, fmj_tu_kernel_16, fmj_tu_kernel_20, fmj_tu_kernel_24, fmj_tu_kernel_28, fmj_tu_kernel_32,
@@ -1855,7 +1857,7 @@ static int launch(const char* what, step_kernel_t k, int blocks, int threads, si
 }
 
 // ---- the fp64 kernel families (fmj_f64.inc): what the host knows of one, from the create flags to the launch.  A new family is a row.
-enum F64FamilyId { F64_PLAIN, F64_LIMITS, F64_RK4, F64_CONTACTS, F64_TERRAIN, F64_ELLIPTIC, F64_MESH, F64_MESH_ELLIPTIC };
+enum F64FamilyId { F64_PLAIN, F64_LIMITS, F64_RK4, F64_CONTACTS, F64_TERRAIN, F64_ELLIPTIC, F64_MESH, F64_MESH_ELLIPTIC, F64_TERRAIN_RK4, F64_ELLIPTIC_RK4 };
 static const struct F64Family {
   void* (*tu)(int fused, int limits);   // its translation unit's getter
   bool fused;                           // fused builds exist (fmj_step_fused_f64)
@@ -1877,9 +1879,18 @@ static const struct F64Family {
   {fmj_tu_f64_mesh_elliptic, false, true,
    "the fp64 contact solve with mesh geoms under the elliptic cone (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_MESH | FMJ_CREATE_F64_ELLIPTIC)",
    "fmj_create_ex2: LDS request of the fp64 mesh-elliptic step kernel too large"},
+  {fmj_tu_f64_terrain_rk4, false, true, "the fp64 contact solve with RK4 (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_CONTACTS_RK4)",
+   "fmj_create_ex2: LDS request of the fp64 terrain RK4 step kernel too large"},
+  {fmj_tu_f64_elliptic_rk4, false, true,
+   "the fp64 contact solve with RK4 under the elliptic cone (FMJ_CREATE_F64_CONTACTS | FMJ_CREATE_F64_CONTACTS_RK4 | FMJ_CREATE_F64_ELLIPTIC)",
+   "fmj_create_ex2: LDS request of the fp64 elliptic RK4 step kernel too large"},
 };
+// the families whose kernel runs the four RK4 passes itself: F64_RK4_LDS_DOUBLES past their map, no stage buffers, no stage launches
+static bool f64_rk4_inside(int family) { return family == F64_RK4 || family == F64_TERRAIN_RK4 || family == F64_ELLIPTIC_RK4; }
 // the families built from the terrain kernels' text: their ground entries are F64_TG rows and their LDS is ldsd_terrain_bytes
-static bool f64_terrain_text(int family) { return family == F64_TERRAIN || family == F64_ELLIPTIC || family == F64_MESH || family == F64_MESH_ELLIPTIC; }
+static bool f64_terrain_text(int family) {
+  return family == F64_TERRAIN || family == F64_ELLIPTIC || family == F64_MESH || family == F64_MESH_ELLIPTIC || family == F64_TERRAIN_RK4 || family == F64_ELLIPTIC_RK4;
+}
 // which kernels an fp64 context runs, decided once (check_model): every launch runs f64_families[family].tu(fused, limits)
 struct F64Kind {
   int family = -1;                      // an F64FamilyId; -1: not an fp64 context
@@ -1888,7 +1899,8 @@ struct F64Kind {
   bool solves() const { return limits || (family >= 0 && f64_families[family].contacts); }      // the kernel's Newton solve runs: limit or contact rows
 };
 static int f64_lds_bytes(int family, int limits, int nb, int nv, int nq, int rs, int max_contacts, int nu) {
-  if (f64_terrain_text(family)) return ldsd_terrain_bytes(nb, nv, nq, rs, max_contacts);      // (the elliptic record keeps the stride)
+  if (f64_terrain_text(family))      // (the elliptic record keeps the stride; the RK4 block lies past the contacts' normals)
+    return ldsd_terrain_bytes(nb, nv, nq, rs, max_contacts) + (f64_rk4_inside(family) ? F64_RK4_LDS_DOUBLES(nu) * 8 : 0);
   if (family == F64_CONTACTS) return ldsd_contacts_bytes(nb, nv, nq, rs, max_contacts);
   return ldsd_total_bytes(nb, nv, nq, rs, limits) + (family == F64_RK4 ? F64_RK4_LDS_DOUBLES(nu) * 8 : 0);
 }
@@ -2099,7 +2111,10 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
       const bool elliptic = asked(FMJ_CREATE_F64_ELLIPTIC) && m->cone == FMJ_CONE_ELLIPTIC;
       if (m->cone != FMJ_CONE_PYRAMIDAL && !elliptic) return no("elliptic cone (pyramidal only)");
       if (m->noslip_iterations > 0) return no("noslip post-pass (noslip_iterations > 0)");
-      if (m->integrator == FMJ_INT_RK4) return no("RK4 (Euler or implicitfast only, also with FMJ_CREATE_F64_RK4)");
+      // FMJ_CREATE_F64_CONTACTS_RK4: the four passes inside the terrain / elliptic text, on kernels of their own
+      const bool rk4 = m->integrator == FMJ_INT_RK4;
+      if (rk4 && !asked(FMJ_CREATE_F64_CONTACTS_RK4)) return no("RK4 (Euler or implicitfast only, also with FMJ_CREATE_F64_RK4)");
+      if (rk4 && F->any_mesh) return no("RK4 with mesh geoms (Euler or implicitfast only, also with FMJ_CREATE_F64_MESH)");
       if (m->max_contacts > FMJ_F64_LANES) return no("lane for every contact: max_contacts > 128");
       if (m->ngeom > FMJ_F64_LANES) return no("lane for every geom: more than 128 geoms");
       if (m->max_contacts >= 1 && !elliptic && low_friction_ground_contact(m))      // (the elliptic cone's regulariser does not depend on the friction)
@@ -2114,14 +2129,15 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
       contacts = true; cons = 0;
       // FMJ_CREATE_F64_MESH: a model with a mesh geom runs the mesh kernels (fmj_f64_mesh.inc), any other what it ran without the flag
       const bool mesh = asked(FMJ_CREATE_F64_MESH) && F->any_mesh;
-      if (mesh) F->f64.family = elliptic ? F64_MESH_ELLIPTIC : F64_MESH;
+      if (rk4) F->f64.family = elliptic ? F64_ELLIPTIC_RK4 : F64_TERRAIN_RK4;
+      else if (mesh) F->f64.family = elliptic ? F64_MESH_ELLIPTIC : F64_MESH;
       else if (elliptic) F->f64.family = F64_ELLIPTIC;
     }
     if (cons) return set_err(FMJ_ERR_UNSUPPORTED, std::string("fmj_create_ex: the fp64 step has no constraint solver: the model has ") +
                              (any_limit ? "joint limits" : m->npair > 0 ? "explicit contact pairs" : "contact geoms"));
     if (asked(FMJ_CREATE_F64_LIMITS)) for (int j = 0; j < nj; j++) if (m->jnt_limited[j] && m->jnt_type[j] != FMJ_JNT_FREE) F->f64.limits = 1;
     if (F->f64.limits && (m->solver_iterations < 0 || !(m->solver_tolerance >= 0))) return set_err(FMJ_ERR_ARG, "fmj_create_ex2: solver_iterations / solver_tolerance must not be negative");
-    if (m->integrator == FMJ_INT_RK4 && !asked(FMJ_CREATE_F64_RK4)) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
+    if (m->integrator == FMJ_INT_RK4 && !asked(FMJ_CREATE_F64_RK4) && !f64_rk4_inside(F->f64.family)) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create_ex: the fp64 step integrates with Euler or implicitfast, not RK4");
     F->f64.family = F->f64.family >= F64_ELLIPTIC ? F->f64.family : contacts ? (asked(FMJ_CREATE_F64_TERRAIN) ? F64_TERRAIN : F64_CONTACTS) : m->integrator == FMJ_INT_RK4 ? F64_RK4 : F->f64.limits ? F64_LIMITS : F64_PLAIN;
   }
   if (big && cons) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: nbody or nv above 64 with limits, contacts or pairs (one wavefront per environment on the constraint path)");
@@ -2139,7 +2155,7 @@ static int check_model(const fmj_model* m, ModelFacts* F, int precision) {
   if (m->noslip_iterations < 0 || !(m->noslip_tolerance >= 0)) return set_err(FMJ_ERR_ARG, "fmj_create: noslip_iterations / noslip_tolerance must not be negative");
   if (m->integrator != FMJ_INT_EULER && m->integrator != FMJ_INT_IMPLICITFAST && m->integrator != FMJ_INT_RK4)
     return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: integrator must be FMJ_INT_EULER, FMJ_INT_IMPLICITFAST or FMJ_INT_RK4 (implicit keeps the Coriolis derivatives, a non-symmetric matrix outside this path's tree-sparse factorisation)");
-  if (big && m->integrator == FMJ_INT_RK4 && F->f64.family != F64_RK4) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: RK4 on a model with more than 64 bodies or dofs (its stage kernel holds one dof per lane of one wavefront)");
+  if (big && m->integrator == FMJ_INT_RK4 && !f64_rk4_inside(F->f64.family)) return set_err(FMJ_ERR_UNSUPPORTED, "fmj_create: RK4 on a model with more than 64 bodies or dofs (its stage kernel holds one dof per lane of one wavefront)");
   if (cons && (m->ngeom > nplane || m->npair > 0) && !any_limit && m->max_contacts < 1) return set_err(FMJ_ERR_ARG, "fmj_create: max_contacts must be >= 1 with collision geoms");
   if ((m->npair > 0 || (nplane > 0 && m->ngeom > nplane)) && m->max_contacts < 1) return set_err(FMJ_ERR_ARG, "fmj_create: max_contacts must be >= 1 with collision geoms");
   // structure checks: single tree rooted at body 1, DFS pre-order, <= 1 joint per body
@@ -2231,7 +2247,7 @@ static void describe_model(fmj_ctx* c, const fmj_model* m, const ModelFacts& F) 
   DevModel& D = c->dm;
   c->solver_requested = (F.cons || F.f64.solves()) ? m->solver : FMJ_SOLVER_PGS;
   c->nbody = nb; c->nv = nv; c->nu = m->nu; c->njnt = nj;
-  c->rk4 = m->integrator == FMJ_INT_RK4 && F.f64.family != F64_RK4;      // (an fp64 RK4 context runs its passes inside the kernel: no stage buffers, no stage launches)
+  c->rk4 = m->integrator == FMJ_INT_RK4 && !f64_rk4_inside(F.f64.family);      // (an fp64 RK4 context runs its passes inside the kernel: no stage buffers, no stage launches)
   D.nbody = nb; D.nv = nv; D.nq = m->nq; D.nu = m->nu; D.njnt = nj; D.nM = m->nM;
   D.max_bdepth = F.jump_rounds;       // pointer-jumping rounds
   D.max_subsize = F.max_sub;
@@ -2865,6 +2881,8 @@ int fmj_create_ex2(const fmj_model* m, int32_t n_envs, int32_t device, const fmj
      "fmj_create_ex2: FMJ_CREATE_F64_ELLIPTIC needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it lets the fp64 contact solve take the elliptic cone)"},
     {FMJ_CREATE_F64_MESH, FMJ_CREATE_F64_CONTACTS,
      "fmj_create_ex2: FMJ_CREATE_F64_MESH needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it lets the fp64 contact solve take convex mesh geoms)"},
+    {FMJ_CREATE_F64_CONTACTS_RK4, FMJ_CREATE_F64_CONTACTS,
+     "fmj_create_ex2: FMJ_CREATE_F64_CONTACTS_RK4 needs FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64 (it lets the fp64 contact solve integrate with RK4)"},
   };
   const int32_t flags = ext ? ext->flags : 0;
   int32_t known = 0;

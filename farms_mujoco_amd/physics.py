@@ -46,7 +46,8 @@ class _MjData(SimpleNamespace):
 #   fp64_rk4       integrator = RK4, the four forward passes of a step inside the kernel, one launch for all steps of fmj_step; with
 #                  fp64_fused such a run fuses too
 #   fp64_contacts  ground contacts (sphere / capsule / box geoms against world planes, pyramidal cone) as more rows of the same Newton
-#                  solve: walking models past the sizes of the fp32 constraint path; fmj_step only, no fused launch, no RK4
+#                  solve: walking models past the sizes of the fp32 constraint path; fmj_step only, no fused launch, RK4 only with
+#                  fp64_contacts_rk4
 #   fp64_terrain   the contacts context also takes the world's heightfield as ground and cylinder geoms on the animat: its own
 #                  kernels, whose narrow phase carries a normal per contact; opt-in, also on flat ground
 #   fp64_mesh      the contacts context also takes convex mesh geoms on the animat (what Simulation.from_sdf makes of every mesh
@@ -55,6 +56,10 @@ class _MjData(SimpleNamespace):
 #   fp64_elliptic  the contacts context also takes a model whose cone is elliptic (three rows per contact, kernels of their own); a
 #                  pyramidal model runs what it runs without the keyword.  The elliptic cone's regulariser does not depend on the
 #                  friction, so a model with friction-0 feet (1e-5 after the clamp), which the pyramid refuses, is accepted
+#   fp64_contacts_rk4  the contacts context also takes integrator = RK4 on a walking model: the four passes of a step, each with its own
+#                  narrow phase and solve, inside kernels of their own (terrain text, also on planes); an Euler or implicitfast model
+#                  runs what it runs without the keyword.  It is not fp64_rk4, which admits RK4 on a model without contacts and still
+#                  does not go with fp64_contacts; RK4 with mesh geoms stays refused
 _NEEDS_FP64 = "precision='fp64', not {precision!r}: "
 _CONTACTS_EXCLUDE = {'fp64_fused': 'fused contact rows are not built for the fp64 step', 'fp64_rk4': 'the fp64 contact solve integrates with Euler or implicitfast'}
 FP64_OPTIONS = {
@@ -67,6 +72,8 @@ FP64_OPTIONS = {
                      'fp64_contacts={fp64_contacts}): it widens the narrow phase of the fp64 contact solve', {}),
     'fp64_mesh': (_lib.CREATE_F64_MESH, ('fp64_contacts',), "precision='fp64' and fp64_contacts=True (not precision={precision!r}, "
                   'fp64_contacts={fp64_contacts}): it lets the fp64 contact solve take convex mesh geoms', _CONTACTS_EXCLUDE),
+    'fp64_contacts_rk4': (_lib.CREATE_F64_CONTACTS_RK4, ('fp64_contacts',), "precision='fp64' and fp64_contacts=True (not precision={precision!r}, "
+                          'fp64_contacts={fp64_contacts}): it lets the fp64 contact solve integrate with RK4', _CONTACTS_EXCLUDE),
     'fp64_elliptic': (_lib.CREATE_F64_ELLIPTIC, ('fp64_contacts',), "precision='fp64' and fp64_contacts=True (not precision={precision!r}, "
                       'fp64_contacts={fp64_contacts}): it lets the fp64 contact solve take the elliptic cone', _CONTACTS_EXCLUDE),
 }
@@ -77,7 +84,7 @@ class BatchedPhysics:
 
     def __init__(self, model: Model, n_envs: int, device='cuda:0', precision: str = 'fp32', kernel=None, fp64_fused: bool = False,
                  fp64_limits: bool = False, fp64_rk4: bool = False, fp64_contacts: bool = False, fp64_terrain: bool = False,
-                 fp64_elliptic: bool = False, fp64_mesh: bool = False):
+                 fp64_elliptic: bool = False, fp64_mesh: bool = False, fp64_contacts_rk4: bool = False):
         # precision='fp64': the fp64 step kernel (fmj_create_ex, include/fmj.h) - unconstrained models, Euler / implicitfast; the
         # tensors of physics.data stay fp32.  kernel: a KernelOptions (options.py) states this context's kernel selection in full;
         # None leaves it to the library, which then also hears the FMJ_* variables (include/fmj.h, "Kernel selection").
@@ -85,7 +92,8 @@ class BatchedPhysics:
         if precision not in _lib.PRECISIONS:
             raise ValueError(f'precision must be one of {sorted(_lib.PRECISIONS)}, not {precision!r}')
         on = dict(fp64_fused=bool(fp64_fused), fp64_limits=bool(fp64_limits), fp64_rk4=bool(fp64_rk4), fp64_contacts=bool(fp64_contacts),
-                  fp64_terrain=bool(fp64_terrain), fp64_elliptic=bool(fp64_elliptic), fp64_mesh=bool(fp64_mesh))
+                  fp64_terrain=bool(fp64_terrain), fp64_elliptic=bool(fp64_elliptic), fp64_mesh=bool(fp64_mesh),
+                  fp64_contacts_rk4=bool(fp64_contacts_rk4))
         ext_flags = 0
         for name, (flag, needs, needs_text, excludes) in FP64_OPTIONS.items():
             if on[name] and (precision != 'fp64' or not all(on[n] for n in needs)):
@@ -144,7 +152,8 @@ class BatchedPhysics:
             sensordata=z(n, m.nsensordata), qacc=z(n, m.nv), time=z(n), status=z(n, dtype=torch.int32))
         self.has_constraints = bool(np.any(m.jnt_limited)) or m.ngeom > 0
         # FMJ_INT_RK4: fmj_step runs four forward launches per step and fmj_step_fused refuses - or, in an fp64_rk4 context, the fp64
-        # kernel runs the four passes itself (one launch for all steps; fmj_step_fused_f64 fuses)
+        # kernel runs the four passes itself (one launch for all steps; fmj_step_fused_f64 fuses); so does an fp64_contacts_rk4 context
+        # on a walking model, through fmj_step alone
         self.rk4 = int(getattr(m, 'integrator', 0)) == 1
         self.max_contacts = max(int(m.max_contacts), 1)
         self.data.qacc_warmstart = z(n, m.nv)
@@ -308,7 +317,9 @@ class BatchedPhysics:
             contacts = self.fp64_contacts and _lib.ints(self._lib.fmj_constraint_info, self._ctx)[1] > 0
             elliptic = contacts and self.fp64_elliptic and int(getattr(self.model, 'cone', 0)) == 1      # (FMJ_CONE_ELLIPTIC; one family on flat ground and terrain)
             mesh = contacts and self.fp64_mesh and bool((np.asarray(self.model.geom_type) == 7).any())      # (FMJ_GEOM_MESH: kernels of their own)
-            info['fp64_step_kernel'] = ('fmj_step_f64_mesh_elliptic_kernel' if mesh and elliptic else 'fmj_step_f64_mesh_kernel' if mesh else
+            rk4 = contacts and self.fp64_contacts_rk4 and self.rk4      # (the four passes inside the terrain / elliptic text; no mesh builds)
+            info['fp64_step_kernel'] = ('fmj_step_f64_elliptic_rk4_kernel' if rk4 and elliptic else 'fmj_step_f64_terrain_rk4_kernel' if rk4 else
+                                        'fmj_step_f64_mesh_elliptic_kernel' if mesh and elliptic else 'fmj_step_f64_mesh_kernel' if mesh else
                                         'fmj_step_f64_elliptic_kernel' if elliptic else 'fmj_step_f64_terrain_kernel' if contacts and self.fp64_terrain else 'fmj_step_f64_contacts_kernel' if contacts else
                                         'fmj_step_f64_rk4_kernel' if self.fp64_rk4 and self.rk4 else 'fmj_step_f64_kernel')
         if _lib.has('fmj_dual_build_info'):     # absent only from an A/B base build (FMJ_SO)

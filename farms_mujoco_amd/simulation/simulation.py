@@ -112,7 +112,9 @@ class Simulation:
     cylinder geoms, on kernels of its own; a shard of a :class:`~farms_mujoco_amd.sharding.ShardedSimulation` gets it like the other kernel
     arguments, from its factory), ``fp64_elliptic`` (with 'fp64' and ``fp64_contacts``: the contact solve also takes a model whose cone is
     elliptic, on kernels of its own - and with it a model whose feet have no friction), ``fp64_mesh`` (with 'fp64' and ``fp64_contacts``: the
-    contact solve also takes convex mesh geoms, which is what :meth:`from_sdf` makes of every mesh collision), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
+    contact solve also takes convex mesh geoms, which is what :meth:`from_sdf` makes of every mesh collision), ``fp64_contacts_rk4`` (with
+    'fp64' and ``fp64_contacts``: the contact solve also takes ``integrator='RK4'`` on a walking model, the four passes of a step inside
+    kernels of their own; ``run()`` takes the per-iteration path; not with mesh geoms), ``kernel`` (a :class:`~farms_mujoco_amd.options.KernelOptions`: which step
     kernels this simulation's context runs).  ``legacy_step`` is accepted for signature
     compatibility; the step is always the full mj_step (legacy_step=False semantics, simulation.py:36-37).
     Unlike dm_control's Environment, whose first ``step()`` only resets, ``run()`` here

@@ -366,7 +366,7 @@ int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
  * on body b is non-zero only on the dofs of b's ancestor chain, so J' D J fills only entries (i, j) with j an ancestor of i, the pattern
  * of M, and the tree-sparse factorisation stays exact.  Refused with FMJ_ERR_UNSUPPORTED before the device lookup, "fp64" and the
  * thing named in the message: explicit pairs (they couple two chains), heightfield, cylinder and mesh geoms, the elliptic cone,
- * noslip_iterations > 0, RK4 (also with FMJ_CREATE_F64_RK4), max_contacts > 128 or more than 128 geoms (one lane each), a geom on a
+ * noslip_iterations > 0, RK4 (also with FMJ_CREATE_F64_RK4; FMJ_CREATE_F64_CONTACTS_RK4 below admits it), max_contacts > 128 or more than 128 geoms (one lane each), a geom on a
  * body without dofs, a contact whose friction / sqrt(impratio) can fall below 1e-3 (fmj_solver_info's rule: too stiff for a primal
  * solve) and a model whose LDS at these sizes exceeds 160 KB (the bytes are named: nbody = nv = 128 with a dof chain of 64 and 128
  * contacts fits).  Without the flag every refusal is what it was.  The solver is the Newton solve whatever the model names
@@ -395,7 +395,7 @@ int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
  * friction / sqrt(impratio) can fall below 1e-3 does not apply to an elliptic model: a model whose geoms have no friction at all
  * (1e-5 after the clamp) is accepted.  Heightfield and cylinder geoms still need FMJ_CREATE_F64_TERRAIN (the elliptic kernels hold
  * the terrain kernels' narrow phase, so one family serves both, and the LDS limit is the terrain context's); explicit pairs, meshes,
- * noslip, RK4 and fused launches stay refused with the same words.  fmj_data.contact holds the force in the contact frame directly
+ * noslip, RK4 (without FMJ_CREATE_F64_CONTACTS_RK4) and fused launches stay refused with the same words.  fmj_data.contact holds the force in the contact frame directly
  * (normal, tangent 1, tangent 2); fmj_solver_info reports Newton; everything else is what a contacts context covers and leaves.
  * FMJ_CREATE_F64_MESH (without FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64: FMJ_ERR_ARG, before the device lookup;
  * bit 1024 is not assigned either): a contacts context that also accepts FMJ_GEOM_MESH geoms on the animat.  It says what the
@@ -406,10 +406,27 @@ int fmj_precision(const fmj_ctx* ctx);     /* FMJ_PRECISION_* of the context */
  * under the geom's origin is farther than the bounding radius geom_size[2] (the rule of every path; mesh_vert is read unrounded, a
  * geom may have any number of vertices).  The kernels hold the terrain kernels' narrow phase and the LDS limit is the terrain
  * context's, but heightfield and cylinder geoms still need FMJ_CREATE_F64_TERRAIN and an elliptic model FMJ_CREATE_F64_ELLIPTIC;
- * explicit pairs (with or without meshes), noslip, RK4, fused launches and a pyramidal model with low-friction feet stay refused
- * with the same words. */
+ * explicit pairs (with or without meshes), noslip, RK4 (with mesh geoms also under FMJ_CREATE_F64_CONTACTS_RK4), fused launches and a pyramidal model with low-friction feet stay refused
+ * with the same words.
+ * FMJ_CREATE_F64_CONTACTS_RK4 (without FMJ_CREATE_F64_CONTACTS and precision = FMJ_PRECISION_F64: FMJ_ERR_ARG, before the device
+ * lookup; bit 4096 is not assigned either): a contacts context that also accepts integrator = FMJ_INT_RK4 on a model with ground
+ * contacts, at the fp64 kernel's sizes.  It neither needs nor is implied by FMJ_CREATE_F64_RK4 (which admits RK4 on a model without
+ * contacts): without this flag such a model stays refused with the same words, and a model that does not integrate with RK4 gives
+ * the context it gives without the flag, to the same bits.  The four passes of mj_RungeKutta run inside kernels of their own
+ * (fmj_step_f64_terrain_rk4_kernel; fmj_step_f64_elliptic_rk4_kernel for cone = FMJ_CONE_ELLIPTIC with FMJ_CREATE_F64_ELLIPTIC also
+ * given), built from the terrain kernels' text, so planes need no FMJ_CREATE_F64_TERRAIN while heightfield and cylinder geoms still do.
+ * Every pass runs the narrow phase at its own poses and solves its own limit and contact rows with H = M (no implicit damping).  The
+ * solve of every pass starts from that pass's unconstrained acceleration and reads no warm start (as on every fp64 context), so it
+ * agrees with mj_RungeKutta, whose passes start from the step's incoming qacc_warmstart, through the convergence of both solves.  A
+ * step leaves sensordata (jointlimitfrc and actuator forces included) of its first pass and xpos / xquat / xipos, qacc, qacc_warmstart,
+ * fmj_data.contact and ncon of its fourth; FMJ_WARN_CONTACTFULL is the OR over the four passes and does not freeze; fmj_forward is the
+ * first pass alone, with its own contact list.  A freeze check that fails in any pass undoes the step before anything of it is stored:
+ * the contact list and ncon keep what the last completed launch left.  The LDS limit names this context's bytes: the terrain
+ * context's plus 8 (2 nu + 1536) for the stage state (nbody = nv = nu = 128 with a dof chain of 64 fits up to 70 contacts).  Stay
+ * refused, by name: an RK4 model with a mesh geom (also with FMJ_CREATE_F64_MESH), explicit pairs, noslip, fused launches
+ * (fmj_step_fused_f64) and a pyramidal model with low-friction feet. */
 enum { FMJ_CREATE_F64_LIMITS = 1, FMJ_CREATE_F64_RK4 = 8, FMJ_CREATE_F64_CONTACTS = 32, FMJ_CREATE_F64_TERRAIN = 128, FMJ_CREATE_F64_ELLIPTIC = 512,
-       FMJ_CREATE_F64_MESH = 2048 };
+       FMJ_CREATE_F64_MESH = 2048, FMJ_CREATE_F64_CONTACTS_RK4 = 8192 };
 typedef struct fmj_create_ext {
   int32_t size;           /* = sizeof(fmj_create_ext); anything else: FMJ_ERR_ARG */
   int32_t flags;          /* FMJ_CREATE_*, or 0 */

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Device assembly of every translation unit of libfmj_hip.so, and one sha256 per unit: the gate of a refactor that must not
-# change the generated code. Two trees that print the same 27 digests compile to the same kernels.
+# change the generated code. Two trees that print the same 29 digests compile to the same kernels.
 #   scripts/device_listing.sh [TREE] [OUTDIR]
 # TREE is a source tree holding farms_mujoco_amd/csrc and include/ (default: this checkout; for a revision,
 # `git archive REV farms_mujoco_amd/csrc include | tar -x -C DIR`), OUTDIR receives <unit>.s (default: a fresh temporary directory).
@@ -16,7 +16,7 @@ mkdir -p "$out"
 flags="--offload-arch=gfx950 -O3 -fno-slp-vectorize -mllvm -pragma-unroll-threshold=131072 -fPIC --cuda-device-only -S -Wno-unused-command-line-argument"
 units="host:"
 for n in $(seq 4 4 64); do units+=" k$n:-DFMJ_TU_MAXD=$n"; done
-units+=" kw32:-DFMJ_TU_WIDE=32 kw64:-DFMJ_TU_WIDE=64 kf64:-DFMJ_TU_F64 kf64l:-DFMJ_TU_F64=2 kf64r:-DFMJ_TU_F64=3 kf64c:-DFMJ_TU_F64=4 kf64t:-DFMJ_TU_F64=5 kf64e:-DFMJ_TU_F64=6 kf64m:-DFMJ_TU_F64=7 kf64me:-DFMJ_TU_F64=8"
+units+=" kw32:-DFMJ_TU_WIDE=32 kw64:-DFMJ_TU_WIDE=64 kf64:-DFMJ_TU_F64 kf64l:-DFMJ_TU_F64=2 kf64r:-DFMJ_TU_F64=3 kf64c:-DFMJ_TU_F64=4 kf64t:-DFMJ_TU_F64=5 kf64e:-DFMJ_TU_F64=6 kf64m:-DFMJ_TU_F64=7 kf64me:-DFMJ_TU_F64=8 kf64tr:-DFMJ_TU_F64=9 kf64er:-DFMJ_TU_F64=10"
 jobs=${MAX_JOBS:-$(nproc)}
 # run from the tree with a relative source path: the listing then holds no absolute path of the tree
 cd "$tree"

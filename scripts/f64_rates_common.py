@@ -1,5 +1,5 @@
 """What the fp64 rate scripts (f64_limits_rates.py, f64_rk4_rates.py, f64_contacts_rates.py, f64_terrain_rates.py,
-f64_elliptic_rates.py, f64_mesh_rates.py) share: a context on
+f64_elliptic_rates.py, f64_mesh_rates.py, f64_contacts_rk4_rates.py) share: a context on
 the synthetic batch, a sine ctrl tape, the walking centipede's stance, the alternating-sample loop and the line of medians over repeats."""
 import os
 import sys
